@@ -13,6 +13,9 @@ collated ids over RCCL, no collective inside the loop, tokens gathered to rank 0
   python -m torch.distributed.run ... bench.py --gpus N    runs as the rank the launcher made it
   default: weak scaling, --batch images per GPU;  --global-batch G (BASELINE configs[3]: 256 over 8 GPUs):
   strong scaling, G / N images per GPU.
+  --full                adds everything beyond the headline after the timed region (roofline passes, secondary
+                        workloads, CPU baseline, host probe, shard check, RCCL self-test); a plain run does none of it
+  --dump-outputs DIR    writes the last timed step's outputs (tokens, a seeded sample of the images) as .npy
 
 Prints ONE JSON line on rank 0 (see the driver contract in the task statement).
 """
@@ -34,6 +37,7 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/
 MFMA_PEAK_TFLOPS = 2500.0      # dense bf16 MFMA
 WEIGHT_PARAMS_LAYER = 51_380_224          # SURVEY App. A [probe]
 VQ_DECODE_GFLOP_PER_IMAGE = 567.40 + 4 * 0.68   # SURVEY 8d / App. C conv + AttnBlock FLOPs
+DUMP_IMAGES = 16               # --dump-outputs: images sampled from the batch (16 x 3 x 384 x 384 fp32 = 28 MB)
 
 
 def synth_prompts(B, L, vocab, pad_id, seed):
@@ -161,6 +165,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-rccl-selftest", action="store_true", help="N=1: skip the one-rank RCCL self-test child run after the timed region")
     ap.add_argument("--launch-check", action="store_true",
                     help="launcher dry run (no GPU): every rank checks its env, joins a gloo group, all-reduces, rank 0 prints JSON")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check everything beyond the headline: host launch-margin probe, shard check (N > 1), "
+                         "instrumented roofline pass + GEMM / norm phase, secondary workloads, CPU baseline, RCCL self-test (the --no-* switches "
+                         "still skip single parts).  Off: the run sets up, warms up, times the steps, dumps outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): the sampled image tokens of "
+                         "the whole batch and the pixels of a fixed, seeded sample of at most %d of rank 0's images" % DUMP_IMAGES)
     return ap.parse_args(argv)
 
 
@@ -595,6 +606,30 @@ def secondary_workloads(args, cfg, device):
     return out
 
 
+def dump_outputs(d, toks, img):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files in ``d``.  The inputs are seeded (same arguments,
+    same prompts, weights and sampling seeds), so two builds can be compared file for file:
+      image_tokens         [G, T]  the sampled image tokens of the whole batch (rank 0's gathered matrix; ids are exact in float32)
+      images_sample        [k, 3, S, S]  decoded pixels of k = min(B, DUMP_IMAGES) images of rank 0's batch, drawn with a fixed seed
+      images_sample_index  [k]     which images those are
+    At most 64 MB in all."""
+    import numpy as np
+    import torch
+    arrays = {"image_tokens": toks.cpu().numpy().astype(np.float32)}
+    if img is not None:
+        n = img.shape[0]
+        idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_IMAGES), replace=False))
+        arrays["images_sample"] = img[torch.as_tensor(idx, device=img.device)].float().cpu().numpy()
+        arrays["images_sample_index"] = idx.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total / 2 ** 20:.1f} MB (limit 64 MB)")
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return {"dir": d, "bytes": total, "arrays": {k: list(a.shape) for k, a in arrays.items()}}
+
+
 # ------------------------------------------------------------------------------------------ one rank
 def run_rank(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -694,8 +729,12 @@ def run_rank(args):
         step(1000 + w)
     fence()
     t0 = time.perf_counter()
+    last = None
     for k in range(args.steps):
-        step(k, record=True)
+        if k + 1 < args.steps:
+            step(k, record=True)
+        else:
+            last = step(k, record=True)          # only the last step's outputs are held (earlier ones are freed as before)
     fence()
     dt_local = time.perf_counter() - t0
     dt = dt_local
@@ -708,12 +747,16 @@ def run_rank(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     tm = eng.timing()
+    dumped = None
+    if args.dump_outputs and rank == 0 and last is not None:
+        dumped = dump_outputs(args.dump_outputs, *last)
+    last = None
     # Did the enqueue thread stay ahead of the GPU?  The enqueue call of a whole 576-step loop (~100 k launches) runs into the HIP queue's finite depth
     # and then proceeds at the GPU's pace, so its wall time says nothing (measured round 6: 1 494 ms of host time beside 1 622 ms of device time).  The probe:
     # after a fence, ONE 16-step decode (2.8 k launches: fits the queue) -- host time of the enqueue call against the device time of the same 16 steps.
-    # margin = 1 - host / device; <= 0 means this rank is launch-bound (the queue runs dry between kernels).  Outside the timed region.
+    # margin = 1 - host / device; <= 0 means this rank is launch-bound (the queue runs dry between kernels).  Outside the timed region; --full only.
     host = {"affinity": placement}
-    if T > 16:
+    if args.full and T > 16:
         eng.prefill(ids, pad, position_mode=0, uncond_shared=uncond_shared)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -754,12 +797,15 @@ def run_rank(args):
         "rank_ms_per_step": rank_ms,
         "host": host,
         "library": "libplangen_diag.so (MEASUREMENT BUILD: --diag-opt %s)" % " ".join(args.diag_opt) if args.diag_opt else "libplangen_hip.so",
+        "full": bool(args.full),
     }
+    if dumped:
+        out["dumped_outputs"] = dumped
     if not args.tiny and T > 1:
         out["loop_roofline"] = loop_roofline(cfg, args.dtype, B, L, T, pad, tm["decode_ms"], uncond_shared)
         out["loop_roofline_frac"] = out["loop_roofline"]["frac"]
 
-    if world > 1 and not args.no_shard_check:
+    if world > 1 and args.full and not args.no_shard_check:
         # The gathered token matrix must equal what ONE rank produces for the same seed: all ranks run a short
         # sampled pass (32 tokens), rank 0 then regenerates every other rank's shard itself (same prompts, same
         # global image indices in the RNG) and compares bit for bit.
@@ -784,7 +830,7 @@ def run_rank(args):
     if args.pipeline > 0 and rank == 0 and T == cfg.img_tokens:
         out["pipelined"] = pipelined_pass(eng, args, cfg, B, T, ids, pad, uncond_shared, args.pipeline)
         out["pipelined_images_per_s"] = out["pipelined"]["pipelined_images_per_s"]
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         rf = instrumented_pass(eng, args, cfg, B, L, T, ids, pad, tm, out.get("phase_ms"))
         if rf:
             out["roofline"] = rf
@@ -798,17 +844,17 @@ def run_rank(args):
             rf.pop("_class_sums", None)
     if world > 1:
         dist.barrier()
-    if rank == 0 and world == 1 and not args.no_secondary and not args.tiny and B == 64 and T == cfg.img_tokens and not args.diag_opt:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and not args.tiny and B == 64 and T == cfg.img_tokens and not args.diag_opt:
         eng.close()                                           # (idempotent: the GEMM-phase measurement above may have released it already)
         try:
             out["secondary"] = secondary_workloads(args, cfg, local)
         except Exception as ex:                               # noqa: BLE001 -- a secondary workload must never cost the headline line
             out["secondary"] = {"failed": repr(ex)[:400]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.tiny:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.tiny:
         # 16 threads: measured fastest for these small torch-CPU GEMMs on the 256-core bench host
         # (ms/step: 16 thr 89, 32 thr 144, 64 thr 298, 256 thr 42 466)
         out["cpu_baseline"] = cpu_baseline(L, args.cpu_steps, min(args.cpu_threads, os.cpu_count() or 1))
-    if rank == 0 and world == 1 and not args.no_rccl_selftest and not args.tiny:
+    if args.full and rank == 0 and world == 1 and not args.no_rccl_selftest and not args.tiny:
         # under rocprofv3 the child would inherit the profiler's preload and write a second results database into the same directory
         profiled = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
         out["rccl_selftest"] = {"rccl_one_rank": "skipped under a profiler"} if profiled else rccl_selftest()

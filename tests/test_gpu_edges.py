@@ -251,14 +251,14 @@ def test_two_handles_keep_their_own_tuning(tiny_cfg, tiny_weights):
 
 
 def test_bench_line_contract_tiny():
-    """`bench.py` prints ONE JSON line with the driver's keys, the dominant-kernel roofline (HIP-event timed), the per-class
+    """`bench.py --full` prints ONE JSON line with the driver's keys, the dominant-kernel roofline (HIP-event timed), the per-class
     table and the graph-replayed GEMM + norm phase (tiny config, a few seconds)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--tiny", "--steps", "2", "--warmup", "1", "--batch", "4",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -274,6 +274,35 @@ def test_bench_line_contract_tiny():
     assert "decode_attention" in r["classes"] and "decode_gemm_qkv" in r["classes"]
     ph = r["decode_gemm_norm_phase"]
     assert ph["ms_per_step"] > 0 and ph["events_ms_per_step"] > 0 and "method" in ph
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path, tiny_cfg):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, measures nothing beyond the headline, and --dump-outputs writes the
+    last timed step's tokens and a seeded sample of its images as float32 .npy files."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--tiny", "--steps", "3", "--warmup", "1", "--batch", "4",
+                        "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["full"] is False and j["ms_per_step"] > 0
+    assert abs(j["value"] - 4 * 1e3 / j["ms_per_step"]) < 1e-6 * j["value"]
+    for k in ("roofline", "secondary", "cpu_baseline", "rccl_selftest", "shard_check"):
+        assert k not in j, k
+    assert j["host"]["margin"] is None
+    tok = np.load(d / "image_tokens.npy")
+    img = np.load(d / "images_sample.npy")
+    idx = np.load(d / "images_sample_index.npy")
+    assert tok.dtype == np.float32 and tok.shape == (4, tiny_cfg.img_tokens)
+    assert (tok >= 0).all() and (tok < tiny_cfg.img_vocab).all() and (tok == np.round(tok)).all()
+    assert img.dtype == np.float32 and img.shape == (4, 3, tiny_cfg.img_size, tiny_cfg.img_size) and np.isfinite(img).all()
+    assert idx.tolist() == [0, 1, 2, 3]
+    assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
 
 
 def test_bf16_flash_prefill_at_tile_boundaries(tiny_cfg, tiny_weights):

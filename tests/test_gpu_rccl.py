@@ -46,7 +46,7 @@ def test_two_ranks_on_one_gpu_shard_check():
     """The N > 1 path of bench.py with REAL engines: two rank processes share this box's GPU (gloo transport, PG_FORCE_DEVICE: RCCL
     refuses two ranks on one device), rank 0 collates and broadcasts, each rank generates its contiguous shard, tokens are gathered to
     rank 0, and the shard check regenerates rank 1's shard on rank 0: zero mismatches, both ranks timed."""
-    rc, out, err = _bench("--gpus", "2", "--batch", "2", "--tokens", "24", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-roofline",
+    rc, out, err = _bench("--gpus", "2", "--batch", "2", "--tokens", "24", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-roofline",
                           env={"PG_FORCE_DEVICE": "0", "PG_DIST_BACKEND": "gloo", "PG_DIST_TIMEOUT_S": "300"})
     assert rc == 0, err[-2000:]
     assert out["n_gpus"] == 2 and out["rccl_ranks"] == 2 and out["dist_backend"] == "gloo" and len(out["rank_ms_per_step"]) == 2

@@ -1,12 +1,13 @@
 #!/bin/bash
-# the default bench line twice, with its wall time
+# the full bench line (--full: roofline passes, secondary workloads, CPU baseline, host probe) twice, with its wall time
 tag=${1:-final6}
-mkdir -p gpurun_out
+out=${OUT:-bench_out}
+mkdir -p "$out"
 for i in 1 2; do
-  t0=$(date +%s); python bench.py > gpurun_out/bench_${tag}_$i.json 2> gpurun_out/bench_${tag}_$i.err; echo "bench rc=$? wall $(( $(date +%s) - t0 )) s"
+  t0=$(date +%s); python bench.py --full > "$out/bench_${tag}_$i.json" 2> "$out/bench_${tag}_$i.err"; echo "bench rc=$? wall $(( $(date +%s) - t0 )) s"
   python - <<PY
 import json
-d = json.load(open("gpurun_out/bench_${tag}_$i.json"))
+d = json.load(open("$out/bench_${tag}_$i.json"))
 print("value", d["value"], "phase_ms", {k: round(v["mean"], 1) for k, v in d["phase_ms"].items()}, "loop_roofline", round(d["loop_roofline"]["frac"], 3), round(d["loop_roofline"]["moved_frac"], 3))
 rf = d.get("roofline", {})
 print("roofline", rf.get("frac"), "traffic", rf.get("traffic"), "rocprof_frac", rf.get("rocprof_frac"), "gemm_norm_phase", (rf.get("decode_gemm_norm_phase") or {}).get("frac"))
