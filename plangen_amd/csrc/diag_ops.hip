@@ -1,0 +1,126 @@
+// libplangen_diag.so only: operator entry points of the attention kernels for the operator tests (tests/test_gpu_attention.py).  Each one points
+// the calling thread's pg_tune at a local PgTune (no diagnostics hooks, one kernel-form selector set), calls the PRODUCTION launcher and restores
+// pg_tune.  Shapes the kernels do not support are refused with PG_ERR_ARG and never launched.  Head dimension: 128 for the LLM kernels (implied
+// by the [.., nh * 128] layouts), 64 for SigLIP (C / NH).  Row lengths, slots and token maps live in device memory; they are copied back and
+// checked on the host before anything is launched (these are test entry points: the synchronisation does not matter).
+#include <type_traits>
+#include <vector>
+#include "kernels.h"
+#include "diag.h"
+#include "../../include/plangen_hip.h"
+
+namespace {
+struct LocalTune {                  // the thread's pg_tune points at `t` for the lifetime of this object
+    PgTune t;
+    const PgTune* saved;
+    LocalTune() : saved(pg_tune) { t.diag = nullptr; pg_tune = &t; }
+    ~LocalTune() { pg_tune = saved; }
+};
+constexpr int kMaxGridYZ = 65535;
+bool to_host(std::vector<int32_t>& dst, const int32_t* src, int n) {
+    dst.assign(n > 0 ? n : 0, 0);
+    if (n <= 0) return true;
+    if (!src) return false;
+    return hipMemcpy(dst.data(), src, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess;
+}
+int launched(hipStream_t s) { (void)s; return hipGetLastError() == hipSuccess ? PG_OK : PG_ERR_HIP; }
+}  // namespace
+
+extern "C" {
+
+// Fused decode attention (path 0: launch_attn_decode_fused) or the unfused pair (path 1: launch_rope_kv mode 0 into qbuf, then launch_attn mode 0;
+// no shared-prompt aliasing in that pair, so shared_len must be 0).  form: 0 = the production choice, 4 = big (4-wave), 8 = small (8-wave).
+// qbuf: [M][nh * 128] T scratch for path 1, or null (allocated here).  len / pos_off: [rows] device, n_dec: [1] device, row_order: [M] or null.
+int pg_diag_op_attn_decode(int is_bf16, int form, int path, const float* qkv, int S, long slab, void* obuf, void* kc, void* vc,
+                           const float* cos_t, const float* sin_t, const int32_t* len, const int32_t* pos_off, const int32_t* n_dec,
+                           const int32_t* row_order, int shared_len, int shared_row, int M, int nh, int slots, int max_pos, float scale,
+                           void* qbuf, pg_stream stream) {
+    if (!qkv || !obuf || !kc || !vc || !cos_t || !sin_t || !len || !pos_off || !n_dec) return PG_ERR_ARG;
+    if (form != 0 && form != 4 && form != 8) return PG_ERR_ARG;
+    if (path != 0 && path != 1) return PG_ERR_ARG;
+    if (M < 1 || M > kMaxGridYZ || nh < 1 || nh > kMaxGridYZ || S < 1 || slab < (long)M * 3 * nh * 128 || slots < 1 || max_pos < 1) return PG_ERR_ARG;
+    if (shared_len < 0 || shared_len > slots || (path == 1 && shared_len > 0)) return PG_ERR_ARG;
+    std::vector<int32_t> hl, hn, ho;
+    if (!to_host(hl, len, M) || !to_host(hn, n_dec, 1) || !to_host(ho, row_order, row_order ? M : 0)) return PG_ERR_HIP;
+    for (int r = 0; r < M; ++r) {
+        const long slot = (long)hl[r] + hn[0];
+        if (hl[r] < 0 || hn[0] < 0 || slot >= slots) return PG_ERR_ARG;          // the append slot must exist
+    }
+    if (row_order) {                                                            // a permutation of [0, M)
+        std::vector<char> seen(M, 0);
+        for (int i = 0; i < M; ++i) {
+            if (ho[i] < 0 || ho[i] >= M || seen[ho[i]]) return PG_ERR_ARG;
+            seen[ho[i]] = 1;
+        }
+    }
+    LocalTune lt;
+    lt.t.attn_waves = form;
+    const hipStream_t s = (hipStream_t)stream;
+    SeqState st{len, pos_off, n_dec, nullptr, nullptr, shared_len, shared_row, row_order};
+    if (path == 0) {
+        if (is_bf16) launch_attn_decode_fused<bf16>(s, qkv, S, slab, (bf16*)obuf, (bf16*)kc, (bf16*)vc, cos_t, sin_t, st, M, nh, slots, max_pos, scale);
+        else launch_attn_decode_fused<float>(s, qkv, S, slab, (float*)obuf, (float*)kc, (float*)vc, cos_t, sin_t, st, M, nh, slots, max_pos, scale);
+        return launched(s);
+    }
+    void* q = qbuf;
+    if (!q && hipMalloc(&q, (size_t)M * nh * 128 * (is_bf16 ? 2 : 4)) != hipSuccess) return PG_ERR_HIP;
+    if (is_bf16) {
+        launch_rope_kv<bf16>(s, qkv, S, slab, (bf16*)q, (bf16*)kc, (bf16*)vc, cos_t, sin_t, st, 0, M, nh, slots, max_pos);
+        launch_attn<bf16>(s, (const bf16*)q, (bf16*)obuf, (const bf16*)kc, (const bf16*)vc, st, 0, M, nh, slots, scale);
+    } else {
+        launch_rope_kv<float>(s, qkv, S, slab, (float*)q, (float*)kc, (float*)vc, cos_t, sin_t, st, 0, M, nh, slots, max_pos);
+        launch_attn<float>(s, (const float*)q, (float*)obuf, (const float*)kc, (const float*)vc, st, 0, M, nh, slots, scale);
+    }
+    const int rc = launched(s);
+    if (!qbuf) { (void)hipStreamSynchronize(s); (void)hipFree(q); }
+    return rc;
+}
+
+// Prefill attention over the packed tokens: path 2 = attn_prefill_flash2_kernel, 1 = attn_prefill_flash_kernel (both bf16), 0 = attn_kernel mode 1.
+// qbuf / obuf: [Ntok][nh * 128] T; caches [R][nh][slots][128] T; row_off / len: [R] device (row_off -1: the row has no packed token);
+// tok_row / tok_j: [Ntok] device.  The packed tokens of row r must be row_off[r] .. row_off[r] + len[r] - 1 with tok_j = 0 .. len[r] - 1.
+int pg_diag_op_attn_prefill(int is_bf16, int path, const void* qbuf, void* obuf, const void* kc, const void* vc, const int32_t* row_off,
+                            const int32_t* len, const int32_t* tok_row, const int32_t* tok_j, int R, int max_len, int Ntok, int nh, int slots,
+                            float scale, pg_stream stream) {
+    if (!qbuf || !obuf || !kc || !vc || !row_off || !len || !tok_row || !tok_j) return PG_ERR_ARG;
+    if (path < 0 || path > 2 || (path > 0 && !is_bf16)) return PG_ERR_ARG;
+    if (R < 1 || R > kMaxGridYZ || nh < 1 || nh > kMaxGridYZ || Ntok < 1 || Ntok > 0x7fffffff / 8 || max_len < 1 || max_len > slots) return PG_ERR_ARG;
+    std::vector<int32_t> hoff, hlen, hrow, hj;
+    if (!to_host(hoff, row_off, R) || !to_host(hlen, len, R) || !to_host(hrow, tok_row, Ntok) || !to_host(hj, tok_j, Ntok)) return PG_ERR_HIP;
+    for (int m = 0; m < Ntok; ++m)
+        if (hrow[m] < 0 || hrow[m] >= R || hj[m] < 0 || hj[m] >= slots) return PG_ERR_ARG;
+    for (int r = 0; r < R; ++r) {
+        if (hlen[r] < 0 || hlen[r] > max_len) return PG_ERR_ARG;
+        if (hoff[r] < 0) continue;
+        if (hlen[r] < 1 || (long)hoff[r] + hlen[r] > Ntok) return PG_ERR_ARG;
+        for (int j = 0; j < hlen[r]; ++j)
+            if (hrow[hoff[r] + j] != r || hj[hoff[r] + j] != j) return PG_ERR_ARG;
+    }
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    if (path > 0) {
+        lt.t.prefill_attn = path;
+        launch_attn_prefill_flash(s, (const bf16*)qbuf, (bf16*)obuf, (const bf16*)kc, (const bf16*)vc, row_off, len, R, max_len, nh, slots, scale);
+        return launched(s);
+    }
+    SeqState st{len, nullptr, nullptr, tok_row, tok_j, 0, 1, nullptr};
+    if (is_bf16) launch_attn<bf16>(s, (const bf16*)qbuf, (bf16*)obuf, (const bf16*)kc, (const bf16*)vc, st, 1, Ntok, nh, slots, scale);
+    else launch_attn<float>(s, (const float*)qbuf, (float*)obuf, (const float*)kc, (const float*)vc, st, 1, Ntok, nh, slots, scale);
+    return launched(s);
+}
+
+// SigLIP attention (bf16, heads of 64, non-causal): qk [B * P][2C] (q | k), vt [B][C][P] (V transposed), o [B * P][C].
+// form 1 = the 64-key tile kernel; 4 / 8 / 12 / 16 = the LDS-resident kernel with that many waves (the launcher still falls back to the
+// tile kernel when K / V^T of a head do not fit the LDS).
+int pg_diag_op_attn_vit(int form, const void* qk, const void* vt, void* o, int B, int P, int C, int NH, float scale, pg_stream stream) {
+    if (!qk || !vt || !o) return PG_ERR_ARG;
+    if (form != 1 && form != 4 && form != 8 && form != 12 && form != 16) return PG_ERR_ARG;
+    if (B < 1 || B > kMaxGridYZ || NH < 1 || NH > kMaxGridYZ || C != NH * 64 || P < 64 || P % 64 || (long)B * P * 2 * C > 0x7fffffffL) return PG_ERR_ARG;
+    LocalTune lt;
+    lt.t.vit_attn = form;
+    const hipStream_t s = (hipStream_t)stream;
+    launch_attn_vit_flash(s, (const bf16*)qk, (const bf16*)vt, (bf16*)o, B, P, C, NH, scale);
+    return launched(s);
+}
+
+}  // extern "C"
