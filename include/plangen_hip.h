@@ -137,6 +137,24 @@ int pg_embed_tokens(pg_handle h, const int32_t* ids_dev, void* out_dev, int out_
 int pg_decode_image_tokens(pg_handle h, int T, float cfg_weight, float temperature, uint64_t seed,
                            const int32_t* force_tok_dev, const uint8_t* force_mask_dev,
                            int32_t* out_tok_dev, float* logits_out_dev, pg_stream s);
+/* pg_decode_image_tokens with top-k / top-p (nucleus) filtering of the sampled draw (an extension
+ * beyond the reference; HF generate order temperature -> top-k -> top-p).  Per image and step,
+ * x = mixed / temperature:
+ *   top_k > 0:      keep v iff #{u : x_u > x_v} < top_k (ties at the k-th value all kept;
+ *                   top_k >= V keeps everything); top_k == 0: off.
+ *   0 < top_p < 1:  on softmax(x) over the top-k survivors, keep v iff the mass of survivors
+ *                   with a strictly larger x is < top_p (ties at the boundary all kept; the top
+ *                   token always kept); top_p == 1: off.
+ * The token is drawn from softmax(x) over the kept set by the same Gumbel-max noise as
+ * pg_decode_image_tokens, so when the unfiltered draw survives the filter the filtered draw
+ * equals it.  NaN counts as -inf; -inf is never kept; if nothing is kept token 0 is emitted.
+ * temperature <= 0 (greedy) ignores top_k / top_p.  Forcing is unchanged (filters apply to the
+ * model's own draw only).  (top_k, top_p) = (0, 1) is exactly pg_decode_image_tokens.
+ * top_k < 0, top_p <= 0, top_p > 1 or NaN: PG_ERR_ARG, nothing launched.  The filtered
+ * sampler needs img_vocab <= 16384. */
+int pg_decode_image_tokens_filtered(pg_handle h, int T, float cfg_weight, float temperature, int32_t top_k, float top_p,
+                                    uint64_t seed, const int32_t* force_tok_dev, const uint8_t* force_mask_dev,
+                                    int32_t* out_tok_dev, float* logits_out_dev, pg_stream s);
 
 /* language_model.generate(inputs_embeds=..., do_sample=False, max_new_tokens=...,
  * eos_token_id=pad_token_id=eos) (System.x2t, plangen_base.py:513-523) after a
@@ -251,6 +269,11 @@ int pg_op_swiglu_gemm(pg_handle h, const void* a_dev, const void* wgu_dev, void*
 /* The sampler's RNG output stage: raw 64-bit generator outputs bits_dev [n] -> out_dev fp32 [2n] =
  * (uniform u in (0,1) | Gumbel noise -log(-log u)) exactly as cfg_scan_kernel computes them. */
 int pg_op_uniform(pg_handle h, const uint64_t* bits_dev, float* out_dev, int n, pg_stream s);
+/* The top-k / top-p selection of pg_decode_image_tokens_filtered on caller-given rows:
+ * logits_dev fp32 [B, V] (V <= img_vocab, <= 16384) -> keep_dev uint8 [B, V] = 1 where the entry
+ * is in the kept set of x = logits / temperature (same rule and device code).  temperature > 0. */
+int pg_op_sample_filter(pg_handle h, const float* logits_dev /*[B,V]*/, int B, int V, float temperature, int top_k,
+                        float top_p, uint8_t* keep_dev /*[B,V]*/, pg_stream s);
 
 /* 3x3 convolution over NHWC activations (compute dtype), the VQ-16 ResnetBlock / Upsample /
  * Downsample conv (vq_model.py:337-352, :417-427, :440-447).  w_dev is [Cout][9][Cin]

@@ -37,6 +37,8 @@ class PlanGenConfig:
     # sampling defaults (cfg/base.py:158-162)
     cfg_weight: float = 5.0
     temperature: float = 1.0
+    top_k: int = 0                 # top-k / top-p (nucleus) filtering of sampled draws: an extension beyond the reference, off by default
+    top_p: float = 1.0
     seed: int = 0
 
     @property

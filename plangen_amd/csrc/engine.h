@@ -103,6 +103,7 @@ struct pg_engine {
     hipEvent_t ev_stage[2] = {nullptr, nullptr}; bool stage_used[2] = {false, false}; int stage_sel = 0;
     int32_t* d_flag = nullptr; int32_t* h_flag = nullptr;        // uncond-sharing probe result
     float* cfg_pv = nullptr; int* cfg_pi = nullptr;              // sampler stage-1 winners
+    float* cfg_mix = nullptr;                                    // top-k / top-p sampler: CFG-mixed rows [max_rows/2, img_vocab] (first filtered call)
     SampleParams* d_sparams = nullptr; TextParams* d_tparams = nullptr;   // per-call parameters the graphs read from HBM
     int32_t *d_out_tok = nullptr, *d_force_tok = nullptr; uint8_t* d_force_mask = nullptr; int64_t* d_text_out = nullptr;
     int rng_image_offset = 0;                                    // pg_set_option("rng_image_offset", lo): this rank's first image in the global batch
@@ -200,8 +201,8 @@ struct pg_engine {
     template <typename T> void run_layers(hipStream_t s, int M, int mode, T* final_out, int32_t* advance = nullptr);
     template <typename T> void head_logits(hipStream_t s, const T* in, int M);
     void forward_decode(hipStream_t s);
-    int decode_image(int T, float cfgw, float temp, uint64_t seed, const int32_t* force_tok, const uint8_t* force_mask,
-                     int32_t* out_tok, float* logits_out, hipStream_t s);
+    int decode_image(int T, float cfgw, float temp, int top_k, float top_p, uint64_t seed, const int32_t* force_tok,
+                     const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s);
     int step(const void* emb, int emb_dtype, void* hidden_out, int hidden_dtype, hipStream_t s);
     int gen_head(const void* h_dev, int h_dtype, float* logits, int R_, hipStream_t s);
     int text_greedy(int max_new, int min_new, int eos, int64_t* out, int* out_len, hipStream_t s);

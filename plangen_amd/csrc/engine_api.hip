@@ -91,7 +91,13 @@ int pg_decode_image_tokens(pg_handle h, int T, float cfg_weight, float temperatu
                            const int32_t* force_tok_dev, const uint8_t* force_mask_dev, int32_t* out_tok_dev,
                            float* logits_out_dev, pg_stream s) { TuneGuard _tg(h);
     if (!h || !out_tok_dev) return PG_ERR_ARG;
-    return h->decode_image(T, cfg_weight, temperature, seed, force_tok_dev, force_mask_dev, out_tok_dev, logits_out_dev, (hipStream_t)s);
+    return h->decode_image(T, cfg_weight, temperature, 0, 1.f, seed, force_tok_dev, force_mask_dev, out_tok_dev, logits_out_dev, (hipStream_t)s);
+}
+int pg_decode_image_tokens_filtered(pg_handle h, int T, float cfg_weight, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                                    const int32_t* force_tok_dev, const uint8_t* force_mask_dev, int32_t* out_tok_dev,
+                                    float* logits_out_dev, pg_stream s) { TuneGuard _tg(h);
+    if (!h || !out_tok_dev) return PG_ERR_ARG;
+    return h->decode_image(T, cfg_weight, temperature, top_k, top_p, seed, force_tok_dev, force_mask_dev, out_tok_dev, logits_out_dev, (hipStream_t)s);
 }
 int pg_generate_text_greedy(pg_handle h, int max_new, int min_new, int eos_id, int64_t* out_dev, int* out_len_host, pg_stream s) { TuneGuard _tg(h);
     if (!h || !out_dev) return PG_ERR_ARG;
@@ -235,6 +241,17 @@ int pg_op_uniform(pg_handle h, const uint64_t* bits_dev, float* out_dev, int n, 
     if (!h || !bits_dev || !out_dev) return PG_ERR_ARG;
     (void)hipSetDevice(h->dev);
     launch_uniform_from_bits((hipStream_t)s, bits_dev, out_dev, n);
+    return hipGetLastError() == hipSuccess ? PG_OK : PG_ERR_HIP;
+}
+int pg_op_sample_filter(pg_handle h, const float* logits_dev, int B, int V, float temperature, int top_k, float top_p, uint8_t* keep_dev,
+                        pg_stream s) {
+    if (!h || !logits_dev || !keep_dev) return PG_ERR_ARG;
+    if (B < 1 || V < 1 || V > h->cfg.img_vocab || V > SEL_MAXV) { h->err = "pg_op_sample_filter: needs B >= 1 and 1 <= V <= img_vocab (<= 16384)"; return PG_ERR_ARG; }
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) {
+        h->err = "pg_op_sample_filter: needs temperature > 0, top_k >= 0, top_p in (0, 1]"; return PG_ERR_ARG;
+    }
+    (void)hipSetDevice(h->dev);
+    launch_sample_filter((hipStream_t)s, logits_dev, B, V, temperature, top_k, top_p, keep_dev);
     return hipGetLastError() == hipSuccess ? PG_OK : PG_ERR_HIP;
 }
 int pg_op_conv3x3(pg_handle h, const void* x_dev, const void* w_dev, const float* bias_dev, const void* residual_dev,

@@ -270,8 +270,9 @@ void pg_engine::forward_decode(hipStream_t s) {
     if (bf) run_layers<bf16>(s, R, 0, (bf16*)hfin, d_ndec); else run_layers<float>(s, R, 0, (float*)hfin, d_ndec);
 }
 
-int pg_engine::decode_image(int T, float cfgw, float temp, uint64_t seed, const int32_t* force_tok,
+int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_p, uint64_t seed, const int32_t* force_tok,
                             const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s) {
+    if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(PG_ERR_ARG, "top_k=%d must be >= 0 and top_p=%g in (0, 1]", top_k, (double)top_p);
     if (!prefilled) FAIL(PG_ERR_STATE, "pg_decode_image_tokens before pg_prefill");
     if (R % 2) FAIL(PG_ERR_ARG, "CFG decode needs an even number of rows (got %d)", R);
     if (n_dec_host != 0) FAIL(PG_ERR_STATE, "decode loop needs a fresh prefill");
@@ -286,6 +287,12 @@ int pg_engine::decode_image(int T, float cfgw, float temp, uint64_t seed, const 
     int nl = lanes_opt > 0 ? lanes_opt : 1;
     if (Rtot % 4 || (long)decode_part_elems <= 0) nl = 1;
     const bool graph = use_graph && !time_attn && T > 2;
+    // top-k / top-p only act on sampled draws (greedy ignores them, as HF's warpers do)
+    const bool filtered = temp > 0.f && (top_k > 0 || top_p < 1.f);
+    if (filtered) {
+        if (cfg.img_vocab > SEL_MAXV) FAIL(PG_ERR_CAPACITY, "top-k / top-p sampler supports img_vocab <= %d (got %d)", SEL_MAXV, cfg.img_vocab);
+        if (!cfg_mix) TRY(dalloc(&cfg_mix, (size_t)(cfg.max_rows / 2) * cfg.img_vocab * 4, false));
+    }
     struct LaneDef { int r0, nrows; float* part; int32_t* ndec; };
     LaneDef ld[2];
     ld[0] = {0, nl == 2 ? Rtot / 2 : Rtot, part, d_ndec};
@@ -293,18 +300,19 @@ int pg_engine::decode_image(int T, float cfgw, float temp, uint64_t seed, const 
     // saved whole-batch views (a lane = pointer rebasing of the row-indexed buffers)
     float* const x0 = x; void* const xn0 = xn; void* const q0 = qbuf; void* const o0 = obuf; void* const hb0 = hbuf;
     void* const hf0 = hfin; void* const gm0 = gh_mid; float* const p0 = part; int32_t* const len0 = d_len;
-    int32_t* const po0 = d_pos_off; int32_t* const nd0 = d_ndec; float* const pv0 = cfg_pv; int* const pi0 = cfg_pi;
+    int32_t* const po0 = d_pos_off; int32_t* const nd0 = d_ndec; float* const pv0 = cfg_pv; int* const pi0 = cfg_pi; float* const mx0 = cfg_mix;
     const int Hh = H(), HDm = HD(), G = cfg.gen_head_dim, I = cfg.inter;
     auto enter = [&](const LaneDef& L) {
         const size_t r = (size_t)L.r0;
         x = x0 + r * Hh; xn = (char*)xn0 + r * Hh * esz; qbuf = (char*)q0 + r * HDm * esz; obuf = (char*)o0 + r * HDm * esz;
         hbuf = (char*)hb0 + r * I * esz; hfin = (char*)hf0 + r * Hh * esz; gh_mid = (char*)gm0 + r * G * esz;
         part = L.part; d_len = len0 + r; d_pos_off = po0 + r; d_ndec = L.ndec; cfg_pv = pv0 + r * 8; cfg_pi = pi0 + r * 8;
+        if (mx0) cfg_mix = mx0 + (r / 2) * cfg.img_vocab;
         kv_row_off = r * cfg.n_heads * (size_t)slots * 128 * esz; shared_row = 1 - L.r0; h_len_off = L.r0; R = L.nrows;
     };
     auto leave = [&]() {
         x = x0; xn = xn0; qbuf = q0; obuf = o0; hbuf = hb0; hfin = hf0; gh_mid = gm0; part = p0; d_len = len0; d_pos_off = po0;
-        d_ndec = nd0; cfg_pv = pv0; cfg_pi = pi0; kv_row_off = 0; shared_row = 1; h_len_off = 0; R = Rtot;
+        d_ndec = nd0; cfg_pv = pv0; cfg_pi = pi0; cfg_mix = mx0; kv_row_off = 0; shared_row = 1; h_len_off = 0; R = Rtot;
     };
     if (force_mask && !force_tok) FAIL(PG_ERR_ARG, "force_mask needs force_tok");
     SampleArgs sa{};
@@ -318,7 +326,8 @@ int pg_engine::decode_image(int T, float cfgw, float temp, uint64_t seed, const 
         toc(st, TC_HEAD, ((double)G * Hh + (double)cfg.img_vocab * G) * (double)esz);
         sa.logits_partial = part; sa.S = S_last; sa.slab = slab_last; sa.x = x; sa.n_dec = d_ndec; sa.b_off = L.r0 / 2;
         tic(st);
-        launch_cfg_sample(st, sa, R / 2, cfg_pv, cfg_pi);
+        if (filtered) launch_cfg_sample_filtered(st, sa, R / 2, cfg_pv, cfg_pi, cfg_mix);
+        else launch_cfg_sample(st, sa, R / 2, cfg_pv, cfg_pi);
         toc(st, TC_SAMPLE, (double)S_last * R * cfg.img_vocab * 4.0);
         tc_on = false;
     };
@@ -349,6 +358,7 @@ int pg_engine::decode_image(int T, float cfgw, float temp, uint64_t seed, const 
     {   // per-call parameters and the caller's forcing tensors -> library-owned device memory (what the graph reads)
         SampleParams sp{}; sp.cfg_weight = cfgw; sp.temperature = temp; sp.seed = seed; sp.T = T;
         sp.has_force = force_tok != nullptr; sp.has_mask = force_mask != nullptr; sp.img_off = rng_image_offset;
+        sp.top_k = top_k; sp.top_p = top_p;
         launch_set_sample_params(ws, d_sparams, sp);
         if (force_tok) HIPCHK(hipMemcpyAsync(d_force_tok, force_tok, (size_t)B * T * 4, hipMemcpyDeviceToDevice, ws));
         if (force_mask) HIPCHK(hipMemcpyAsync(d_force_mask, force_mask, (size_t)B * T, hipMemcpyDeviceToDevice, ws));
@@ -360,7 +370,7 @@ int pg_engine::decode_image(int T, float cfgw, float temp, uint64_t seed, const 
         // shapes and kernel selection only: seeds, temperatures, T and the caller's buffers reach the kernels through
         // device memory, so a bench / serving loop replays ONE instantiated graph across calls
         std::vector<int64_t> key = {Rtot, (int64_t)bf, (int64_t)logits_out, (int64_t)shared_len, (int64_t)fuse_rope, (int64_t)nl,
-                                    (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch, (int64_t)skip_attn};
+                                    (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch, (int64_t)skip_attn, (int64_t)filtered};
         if (!gexec || key != gkey) {
             if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
             hipGraph_t g = nullptr;

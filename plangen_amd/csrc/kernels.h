@@ -180,7 +180,7 @@ void launch_bias_f32(hipStream_t s, const float* partial, int S, long slab, cons
 // Per-call sampling parameters live in DEVICE memory (written by a 1-thread kernel at the top of
 // pg_decode_image_tokens), so the captured decode-step graph depends on shapes only and is replayed
 // across calls with different seeds / temperatures / caller buffers.
-struct SampleParams { float cfg_weight, temperature; uint64_t seed; int32_t T, has_force, has_mask, img_off; };   // img_off: global index of this engine's image 0 (prompt-sharded runs draw the same noise as one big batch)
+struct SampleParams { float cfg_weight, temperature; uint64_t seed; int32_t T, has_force, has_mask, img_off; int32_t top_k; float top_p; };   // img_off: global index of this engine's image 0 (prompt-sharded runs draw the same noise as one big batch)
 struct SampleArgs {
     const float* logits_partial; int S; long slab; const float* bias; int V;
     const SampleParams* p;
@@ -195,6 +195,19 @@ struct SampleArgs {
 void launch_set_sample_params(hipStream_t s, SampleParams* dst, SampleParams v);
 // scratch: >= 16*B floats and ints
 void launch_cfg_sample(hipStream_t s, const SampleArgs& a, int B, float* scratch_v, int* scratch_i);
+// top-k / top-p sampler (temperature > 0; p->top_k, p->top_p): the scan writes the CFG-mixed rows to mix [B, V] (V <= SEL_MAXV),
+// one 1024-thread block per image selects the kept set and draws from it, then the same pick / feedback tail as launch_cfg_sample
+#define SEL_MAXV 16384
+struct FilterArgs {
+    const float* mix; int V;                                      // rows [gridDim, V]
+    const SampleParams* p;                                        // sampler: temperature / top_k / top_p / seed from device memory
+    float temperature; int top_k; float top_p;                    // operator (p == null): from the host
+    uint8_t* keep;                                                // [gridDim, V] kept mask or null
+    float* pv; int* pi;                                           // sampler: winner -> stage-1 winner slots (null: no draw)
+    const int32_t* n_dec; int b_off;
+};
+void launch_cfg_sample_filtered(hipStream_t s, const SampleArgs& a, int B, float* scratch_v, int* scratch_i, float* mix);
+void launch_sample_filter(hipStream_t s, const float* rows, int B, int V, float temperature, int top_k, float top_p, uint8_t* keep);
 // greedy text: argmax over vocab of (sum_s partial) per row + EOS bookkeeping, writes
 // out[b, step] (int64) and next-token embedding into x.
 struct TextParams { int32_t eos, min_new, max_new, pad; };

@@ -401,7 +401,15 @@ __device__ __forceinline__ void argmax_combine(float& v, int& i, float ov, int o
 // local (value, index) winner; stage 2 (one block per image) combines the winners, applies the
 // forcing rules and gathers the next embedding.
 #define CFG_CHUNKS 16
-__global__ __launch_bounds__(256) void cfg_scan_kernel(SampleArgs a, float* __restrict__ pv, int* __restrict__ pi) {
+// the sampler's perturbed value: Gumbel-max over mixed / T (cfg_scan_kernel and the filtered sampler's cfg_select_kernel
+// draw through this one expression, so a filtered draw equals the unfiltered one whenever that one survives the filter)
+__device__ __forceinline__ float gumbel_perturb(float mixed, float invT, uint64_t seed, uint64_t stream, int v) {
+    const float uu = rng_uniform(seed, stream, v);
+    return mixed * invT - __logf(-__logf(uu));
+}
+// STORE (filtered sampler): also write the CFG-mixed row to mix [B, V] and leave the draw to cfg_select_kernel
+template <bool STORE>
+__global__ __launch_bounds__(256) void cfg_scan_kernel(SampleArgs a, float* __restrict__ pv, int* __restrict__ pi, float* __restrict__ mix) {
     __shared__ float sv[4]; __shared__ int si[4];
     const int b = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x, step = *a.n_dec;
     const int bg = b + a.b_off, B = a.B_total;            // global image index (lane-independent results)
@@ -450,14 +458,13 @@ __global__ __launch_bounds__(256) void cfg_scan_kernel(SampleArgs a, float* __re
                 const float c = cu[it][0], u = cu[it][1];
                 float mixed = u + cfg_weight * (c - u);
                 if (a.logits_out) a.logits_out[((long)step * B + bg) * a.V + v] = mixed;
-                if (temperature > 0.f) {
-                    const float uu = rng_uniform(seed, (uint64_t)(bg + a.p->img_off) * 1000003ull + step, v);
-                    mixed = mixed * invT - __logf(-__logf(uu));
-                }
+                if (STORE) { mix[(long)b * a.V + v] = mixed; continue; }
+                if (temperature > 0.f) mixed = gumbel_perturb(mixed, invT, seed, (uint64_t)(bg + a.p->img_off) * 1000003ull + step, v);
                 if (mixed > best) { best = mixed; bi = v; }
             }
         }
     }
+    if (STORE) return;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
@@ -504,8 +511,198 @@ void launch_set_sample_params(hipStream_t s, SampleParams* dst, SampleParams v) 
 __global__ void set_text_params_kernel(TextParams* dst, TextParams v) { *dst = v; }
 void launch_set_text_params(hipStream_t s, TextParams* dst, TextParams v) { hipLaunchKernelGGL(set_text_params_kernel, dim3(1), dim3(1), 0, s, dst, v); }
 void launch_cfg_sample(hipStream_t s, const SampleArgs& a, int B, float* scratch_v, int* scratch_i) {
-    hipLaunchKernelGGL(cfg_scan_kernel, dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i);
+    hipLaunchKernelGGL(cfg_scan_kernel<false>, dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i, (float*)nullptr);
     hipLaunchKernelGGL(cfg_pick_kernel, dim3(B), dim3(256), 0, s, a, scratch_v, scratch_i);
+}
+
+// ------------------------------------------------------------------------------- top-k / top-p sampler
+// One 1024-thread block per image over its row x = mixed * invT (kept in LDS as the raw mixed values).
+// Keys: order-preserving fp32 -> uint32 (NaN -> -inf, -0 -> +0).  top-k threshold tk = the k-th largest key, by an
+// MSB-first radix select (8-bit digits, LDS count histograms, wave-0 prefix over the 256 buckets).  top-p threshold
+// tp = the smallest key whose strictly-larger survivors (key >= tk) hold < top_p of their exp-mass: the same radix walk
+// over mass histograms.  Masses are w = exp(x - max) in 2^-40 fixed point (64-bit integer sums: the result does not depend
+// on the order of the LDS atomics).  Kept: key >= max(tk, tp) and x > -inf.  Then the Gumbel-max of cfg_scan_kernel
+// over the kept set (same noise, same tie rule) -> slot 0 of the stage-1 winners cfg_pick_kernel combines.
+__device__ __forceinline__ uint32_t sel_key(float mixed, float invT) {
+    float x = mixed * invT;
+    if (x != x) x = -INFINITY;
+    if (x == 0.f) x = 0.f;
+    const uint32_t u = __float_as_uint(x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float sel_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+#define SEL_THREADS 1024
+#define SEL_KEY_NEGINF 0x007fffffu                   // sel_key(-inf)
+#define SEL_MASS_ONE 1099511627776.f                 // 2^40
+__device__ __forceinline__ unsigned long long sel_mass(uint32_t key, float m) {
+    const float x = sel_unkey(key);
+    const float w = m == INFINITY ? (x == INFINITY ? 1.f : 0.f) : expf(x - m);
+    return (unsigned long long)(w * SEL_MASS_ONE);
+}
+__device__ __forceinline__ unsigned long long shfl_up_u64(unsigned long long v, int o) {
+    const uint32_t lo = __shfl_up((uint32_t)v, o, 64), hi = __shfl_up((uint32_t)(v >> 32), o, 64);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int o) {
+    const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)(v >> 32), o, 64);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__global__ __launch_bounds__(SEL_THREADS) void cfg_select_kernel(FilterArgs f) {
+    __shared__ float vals[SEL_MAXV];
+    __shared__ uint32_t hist[256];
+    __shared__ unsigned long long mhist[256];
+    __shared__ uint32_t s_max, s_digit, s_rem;
+    __shared__ unsigned long long s_z, s_above;
+    __shared__ float wv[SEL_THREADS / 64]; __shared__ int wi[SEL_THREADS / 64];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, V = f.V;
+    const float temperature = f.p ? f.p->temperature : f.temperature;
+    const int top_k = f.p ? f.p->top_k : f.top_k;
+    const float top_p = f.p ? f.p->top_p : f.top_p;
+    const float invT = temperature > 0.f ? 1.f / temperature : 1.f;
+    const float* row = f.mix + (long)b * V;
+    if (tid == 0) { s_max = 0; s_z = 0; }
+    uint32_t kmax = 0;
+    for (int v = tid; v < V; v += SEL_THREADS) {
+        const float m = row[v];
+        vals[v] = m;
+        const uint32_t k = sel_key(m, invT);
+        kmax = k > kmax ? k : kmax;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const uint32_t t = __shfl_xor(kmax, o, 64); kmax = t > kmax ? t : kmax; }
+    __syncthreads();
+    if (lane == 0) atomicMax(&s_max, kmax);
+    // ---- top-k: the key of the k-th largest entry
+    uint32_t tk = 0;
+    if (top_k > 0 && top_k < V) {
+        uint32_t prefix = 0, pmask = 0, rem = (uint32_t)top_k;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) hist[tid] = 0;
+            __syncthreads();
+            for (int v = tid; v < V; v += SEL_THREADS) {
+                const uint32_t k = sel_key(vals[v], invT);
+                if ((k & pmask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
+            }
+            __syncthreads();
+            if (tid < 64) {          // lane l holds digits 255-4l .. 252-4l (descending): bucket of the rem-th largest
+                uint32_t h[4], sum = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { h[j] = hist[255 - 4 * lane - j]; sum += h[j]; }
+                uint32_t incl = sum;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+                uint32_t before = incl - sum;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (before < rem && before + h[j] >= rem) { s_digit = 255 - 4 * lane - j; s_rem = rem - before; }
+                    before += h[j];
+                }
+            }
+            __syncthreads();
+            prefix |= s_digit << shift; pmask |= 255u << shift; rem = s_rem;
+        }
+        tk = prefix;
+    }
+    __syncthreads();
+    const uint32_t kmx = s_max;
+    // ---- top-p over the top-k survivors
+    uint32_t tp = 0;
+    if (top_p < 1.f && kmx > SEL_KEY_NEGINF) {
+        const float m = sel_unkey(kmx);
+        unsigned long long z = 0;
+        for (int v = tid; v < V; v += SEL_THREADS) {
+            const uint32_t k = sel_key(vals[v], invT);
+            if (k >= tk) z += sel_mass(k, m);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) z += shfl_xor_u64(z, o);
+        if (lane == 0) atomicAdd(&s_z, z);
+        __syncthreads();
+        const double limit = (double)top_p * (double)s_z;
+        uint32_t prefix = 0, pmask = 0;
+        unsigned long long above = 0;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) { hist[tid] = 0; mhist[tid] = 0; }
+            __syncthreads();
+            for (int v = tid; v < V; v += SEL_THREADS) {
+                const uint32_t k = sel_key(vals[v], invT);
+                if (k >= tk && (k & pmask) == prefix) {
+                    const uint32_t d = (k >> shift) & 255u;
+                    atomicAdd(&hist[d], 1u);
+                    const unsigned long long q = sel_mass(k, m);
+                    if (q) atomicAdd(&mhist[d], q);
+                }
+            }
+            __syncthreads();
+            if (tid < 64) {          // lowest non-empty bucket whose strictly-larger mass is < limit
+                uint32_t c[4]; unsigned long long mm[4], sum = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { c[j] = hist[255 - 4 * lane - j]; mm[j] = mhist[255 - 4 * lane - j]; sum += mm[j]; }
+                unsigned long long incl = sum;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) { const unsigned long long t = shfl_up_u64(incl, o); if (lane >= o) incl += t; }
+                unsigned long long cum = above + incl - sum;
+                int dj = -1; unsigned long long cj = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (c[j] && (double)cum < limit) { dj = 255 - 4 * lane - j; cj = cum; }
+                    cum += mm[j];
+                }
+                const unsigned long long has = __ballot(dj >= 0);
+                if (dj >= 0 && lane == 63 - __clzll(has)) { s_digit = (uint32_t)dj; s_above = cj; }
+            }
+            __syncthreads();
+            prefix |= s_digit << shift; pmask |= 255u << shift; above = s_above;
+        }
+        tp = prefix;
+    }
+    uint32_t tau = tk > tp ? tk : tp;
+    tau = tau > SEL_KEY_NEGINF + 1 ? tau : SEL_KEY_NEGINF + 1;
+    // ---- kept mask (operator) / Gumbel-max over the kept set (sampler)
+    float best = -INFINITY; int bi = 0x7fffffff;
+    uint64_t seed = 0, stream = 0;
+    if (f.pv) {
+        const int step = *f.n_dec;
+        seed = f.p->seed; stream = (uint64_t)(b + f.b_off + f.p->img_off) * 1000003ull + step;
+    }
+    for (int v = tid; v < V; v += SEL_THREADS) {
+        const float mv = vals[v];
+        const bool kept = sel_key(mv, invT) >= tau;
+        if (f.keep) f.keep[(long)b * V + v] = kept;
+        if (f.pv && kept) {
+            const float g = gumbel_perturb(mv, invT, seed, stream, v);
+            if (g > best) { best = g; bi = v; }
+        }
+    }
+    if (!f.pv) return;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
+        argmax_combine(best, bi, ov, oi);
+    }
+    if (lane == 0) { wv[tid >> 6] = best; wi[tid >> 6] = bi; }
+    __syncthreads();
+    if (tid < CFG_CHUNKS) {
+        float v = -INFINITY; int i = 0x7fffffff;
+        if (tid == 0) {
+            v = wv[0]; i = wi[0];
+            for (int w = 1; w < SEL_THREADS / 64; ++w) argmax_combine(v, i, wv[w], wi[w]);
+            if (i == 0x7fffffff) i = 0;          // nothing kept (every entry -inf / NaN): token 0
+        }
+        f.pv[b * CFG_CHUNKS + tid] = v; f.pi[b * CFG_CHUNKS + tid] = i;
+    }
+}
+void launch_cfg_sample_filtered(hipStream_t s, const SampleArgs& a, int B, float* scratch_v, int* scratch_i, float* mix) {
+    hipLaunchKernelGGL(cfg_scan_kernel<true>, dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i, mix);
+    FilterArgs f{};
+    f.mix = mix; f.V = a.V; f.p = a.p; f.pv = scratch_v; f.pi = scratch_i; f.n_dec = a.n_dec; f.b_off = a.b_off;
+    hipLaunchKernelGGL(cfg_select_kernel, dim3(B), dim3(SEL_THREADS), 0, s, f);
+    hipLaunchKernelGGL(cfg_pick_kernel, dim3(B), dim3(256), 0, s, a, scratch_v, scratch_i);
+}
+void launch_sample_filter(hipStream_t s, const float* rows, int B, int V, float temperature, int top_k, float top_p, uint8_t* keep) {
+    FilterArgs f{};
+    f.mix = rows; f.V = V; f.temperature = temperature; f.top_k = top_k; f.top_p = top_p; f.keep = keep;
+    hipLaunchKernelGGL(cfg_select_kernel, dim3(B), dim3(SEL_THREADS), 0, s, f);
 }
 
 // greedy text token (HF generate, do_sample=False): argmax over vocab, finished rows emit

@@ -385,16 +385,24 @@ class Engine:
 
     def decode_image_tokens(self, T: Optional[int] = None, cfg_weight: float = 5.0, temperature: float = 0.0,
                             seed: int = 0, force_tokens: Optional[torch.Tensor] = None,
-                            force_mask: Optional[torch.Tensor] = None, return_logits: bool = False):
+                            force_mask: Optional[torch.Tensor] = None, return_logits: bool = False,
+                            top_k: int = 0, top_p: float = 1.0):
+        """The fused CFG decode loop.  top_k / top_p filter the sampled draws (temperature > 0; HF order temperature ->
+        top-k -> top-p); (0, 1.0) is the unfiltered sampler.  Semantics: include/plangen_hip.h."""
         T = self.cfg.img_tokens if T is None else T
         B = self.R // 2
         out = torch.zeros((B, T), dtype=torch.int32, device=self.device)
         ft = self._dev(force_tokens, torch.int32) if force_tokens is not None else None
         fm = self._dev(force_mask, torch.uint8) if force_mask is not None else None
         lg = torch.zeros((T, B, self.cfg.img_vocab), dtype=torch.float32, device=self.device) if return_logits else None
-        self._check(self.lib.pg_decode_image_tokens(self.h, T, float(cfg_weight), float(temperature), int(seed),
-                                                    self._p(ft), self._p(fm), self._p(out), self._p(lg), self.stream),
-                    "pg_decode_image_tokens")
+        if int(top_k) == 0 and float(top_p) == 1.0:
+            self._check(self.lib.pg_decode_image_tokens(self.h, T, float(cfg_weight), float(temperature), int(seed),
+                                                        self._p(ft), self._p(fm), self._p(out), self._p(lg), self.stream),
+                        "pg_decode_image_tokens")
+        else:
+            self._check(self.lib.pg_decode_image_tokens_filtered(self.h, T, float(cfg_weight), float(temperature), int(top_k),
+                                                                 float(top_p), int(seed), self._p(ft), self._p(fm), self._p(out),
+                                                                 self._p(lg), self.stream), "pg_decode_image_tokens_filtered")
         self._keep = [ft, fm, out, lg]
         return (out, lg) if return_logits else out
 
@@ -494,6 +502,16 @@ class Engine:
         self._check(self.lib.pg_op_uniform(self.h, self._p(b), self._p(out), n, self.stream), "pg_op_uniform")
         torch.cuda.synchronize()
         return out[:n], out[n:]
+
+    def sample_filter(self, logits: torch.Tensor, temperature: float, top_k: int = 0, top_p: float = 1.0) -> torch.Tensor:
+        """pg_op_sample_filter: kept mask (bool [B, V]) of the top-k / top-p sampler over fp32 rows ``logits`` [B, V]."""
+        x = self._dev(logits, torch.float32).reshape(-1, logits.shape[-1]).contiguous()
+        B, V = x.shape
+        keep = torch.zeros((B, V), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.pg_op_sample_filter(self.h, self._p(x), B, V, float(temperature), int(top_k), float(top_p),
+                                                 self._p(keep), self.stream), "pg_op_sample_filter")
+        self._keep = [x, keep]
+        return keep.bool().reshape(logits.shape)
 
     def op_conv3x3(self, x_nhwc: torch.Tensor, w_oihw: torch.Tensor, bias: torch.Tensor, residual=None, up: int = 0,
                    stride2: int = 0) -> torch.Tensor:

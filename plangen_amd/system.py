@@ -71,7 +71,7 @@ class System:
     """Inference half of PlanGen's System on one MI355X.
 
     args carries the cfg keys the path reads (cfg/base.py): seed, parallel_size, cfg_weight,
-    temperature, use_teacher_forcing, debug_max_seq_len, janus_hw.
+    temperature, use_teacher_forcing, debug_max_seq_len, janus_hw; optionally top_k / top_p (sampling filters, off when absent).
     """
 
     def __init__(self, cfg: PlanGenConfig, engine: Engine, args: Optional[SimpleNamespace] = None, codec=None):
@@ -81,7 +81,7 @@ class System:
         self.last_generated_tokens = None
         self.vl_gpt = MultiModalityCausalLM(engine)
         self.args = args or SimpleNamespace(seed=cfg.seed, parallel_size=1, cfg_weight=cfg.cfg_weight,
-                                            temperature=cfg.temperature, use_teacher_forcing=False,
+                                            temperature=cfg.temperature, top_k=cfg.top_k, top_p=cfg.top_p, use_teacher_forcing=False,
                                             debug_max_seq_len=None, janus_hw=cfg.img_size, neg_prompt="", use_neg_box=False)
         self.image_token_num_per_image = cfg.img_tokens
         self.device = engine.device
@@ -99,9 +99,13 @@ class System:
     def sample_image(self, tokens: torch.Tensor, mask: torch.Tensor, cfg_weight: float, temperature: float,
                      seed: int = 0, edit_region: Optional[torch.Tensor] = None,
                      gt_labels: Optional[torch.Tensor] = None, force_tokens: Optional[torch.Tensor] = None,
-                     n_tokens: Optional[int] = None, return_logits: bool = False):
+                     n_tokens: Optional[int] = None, return_logits: bool = False, top_k: Optional[int] = None,
+                     top_p: Optional[float] = None):
         """The 576-step CFG loop, fused on device (one pg_prefill + one pg_decode_image_tokens).
-        tokens int32 [2B, L] CFG-interleaved ids, mask [2B, L+T].  temperature<=0 -> greedy."""
+        tokens int32 [2B, L] CFG-interleaved ids, mask [2B, L+T].  temperature<=0 -> greedy.
+        top_k / top_p (default: self.args, else off) filter the sampled draws."""
+        top_k = getattr(self.args, "top_k", 0) if top_k is None else top_k
+        top_p = getattr(self.args, "top_p", 1.0) if top_p is None else top_p
         L = tokens.shape[1]
         pad = Engine.pad_len_from_mask(mask, L)
         self.engine.prefill(tokens, pad, position_mode=0)
@@ -110,7 +114,7 @@ class System:
             ft, fm = gt_labels, (edit_region != 0).to(torch.uint8)
         elif force_tokens is not None:
             ft = force_tokens
-        return self.engine.decode_image_tokens(n_tokens, cfg_weight, temperature, seed, ft, fm, return_logits)
+        return self.engine.decode_image_tokens(n_tokens, cfg_weight, temperature, seed, ft, fm, return_logits, top_k=top_k, top_p=top_p)
 
     @torch.no_grad()
     def sample_image_stepwise(self, inputs_embeds: torch.Tensor, mask: torch.Tensor, cfg_weight: float,
@@ -137,7 +141,8 @@ class System:
     @torch.no_grad()
     def t2i(self, tokens: torch.Tensor, mask: torch.Tensor, cfg_weight: Optional[float] = None,
             temperature: Optional[float] = None, gt_image: Optional[torch.Tensor] = None,
-            edit_region: Optional[torch.Tensor] = None, parallel_size: Optional[int] = None):
+            edit_region: Optional[torch.Tensor] = None, parallel_size: Optional[int] = None,
+            top_k: Optional[int] = None, top_p: Optional[float] = None):
         """System.t2i (plangen_base.py:525-565): (teacher forcing: VQ-encode the ground truth :528-532) -> replicate x
         parallel_size (:547) -> sample_image -> decode_code (:555).  Returns ``(dec, mask_image)`` like the reference:
         dec [B*p,3,S,S] fp32; mask_image = the edit region resized to janus_hw (:557-560) under use_teacher_forcing,
@@ -146,6 +151,8 @@ class System:
         cfg_weight = a.cfg_weight if cfg_weight is None else cfg_weight
         temperature = a.temperature if temperature is None else temperature
         p = a.parallel_size if parallel_size is None else parallel_size
+        top_k = getattr(a, "top_k", 0) if top_k is None else top_k
+        top_p = getattr(a, "top_p", 1.0) if top_p is None else top_p
         gt_labels = None
         if a.use_teacher_forcing and gt_image is not None:
             bs = gt_image.shape[0]
@@ -163,7 +170,7 @@ class System:
                 gt_labels = torch.cat([gt_labels] * p)
                 force_region = torch.cat([edit_region] + [torch.ones_like(edit_region)] * (p - 1))
         toks = self.sample_image(tokens, mask, cfg_weight, temperature, a.seed,
-                                 force_region if gt_labels is not None else None, gt_labels)
+                                 force_region if gt_labels is not None else None, gt_labels, top_k=top_k, top_p=top_p)
         num_gen = tokens.shape[0] // 2
         dec = self.vl_gpt.gen_vision_model.decode_code(toks.to(dtype=torch.int),
                                                        shape=[num_gen, self.cfg.img_dim, self.cfg.grid, self.cfg.grid])

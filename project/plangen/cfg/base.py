@@ -10,6 +10,8 @@ janus_hw = 384                         # base.py:83
 parallel_size = 1                      # base.py:158
 cfg_weight = 5.0                       # base.py:162
 temperature = 1.0
+top_k = 0                              # top-k filtering of sampled image tokens (0: off); an extension beyond the reference
+top_p = 1.0                            # top-p (nucleus) filtering of sampled image tokens (1.0: off); an extension beyond the reference
 use_teacher_forcing = False            # base.py:36
 use_neg_box = False                    # base.py:121
 neg_prompt = ""                        # base.py:129: wrapped as wrap_uni_prompt(neg_prompt, '') for every uncond CFG row (:673)

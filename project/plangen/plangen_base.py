@@ -52,6 +52,7 @@ class System(_HotPath):
             raise PlanGenError(f"test_data.task_type={task!r}: expected one of {TASKS} (plangen_base.py:1112-1127)")
         cfg = PlanGenConfig.janus_pro_1b() if not getattr(args, "tiny", False) else PlanGenConfig.tiny()
         cfg.seed, cfg.cfg_weight, cfg.temperature = args.seed, args.cfg_weight, args.temperature
+        cfg.top_k, cfg.top_p = int(getattr(args, "top_k", 0)), float(getattr(args, "top_p", 1.0))
         bs = int(args.test_batch_size)
         device = int(os.environ.get("LOCAL_RANK", "0"))
         self.synthetic = td.get("data_name") == "synthetic" or bool(getattr(args, "synthetic", False))
@@ -70,7 +71,8 @@ class System(_HotPath):
                      max_images=bs * int(args.parallel_size), with_lm_head=task in ("uni_2stage", "mmu", "plan"),
                      with_vq_encoder=bool(args.use_teacher_forcing), with_vision=task == "mmu", device=device)
         super().__init__(cfg, eng, SimpleNamespace(seed=args.seed, parallel_size=args.parallel_size, cfg_weight=args.cfg_weight,
-                                                   temperature=args.temperature, use_teacher_forcing=args.use_teacher_forcing,
+                                                   temperature=args.temperature, top_k=cfg.top_k, top_p=cfg.top_p,
+                                                   use_teacher_forcing=args.use_teacher_forcing,
                                                    debug_max_seq_len=args.debug_max_seq_len, janus_hw=args.janus_hw,
                                                    neg_prompt=getattr(args, "neg_prompt", ""),
                                                    use_neg_box=bool(getattr(args, "use_neg_box", False))), codec=codec)
