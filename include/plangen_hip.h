@@ -15,7 +15,7 @@
  *     "host" pointers are small per-row metadata in host memory.
  *   - the library owns weights, KV cache and workspaces (hipMalloc at pg_create).
  *   - every call is asynchronous on the caller's hipStream_t; no hidden device syncs
- *     except where stated (pg_generate_text_greedy polls its finished-flag; pg_prefill reads ONE
+ *     except where stated (pg_generate_text_greedy / _sampled poll the finished-flag; pg_prefill reads ONE
  *     4-byte flag back when it probes for a batch-constant negative prompt -- ONLY when the caller
  *     did not supply the answer through the one-shot ``uncond_shared_hint`` option (0 / 1): with
  *     the hint set, pg_prefill performs no device->host read and no stream synchronisation).
@@ -165,6 +165,30 @@ int pg_decode_image_tokens_filtered(pg_handle h, int T, float cfg_weight, float 
  * the all-finished flag. */
 int pg_generate_text_greedy(pg_handle h, int max_new, int min_new, int eos_id, int64_t* out_dev,
                             int* out_len_host, pg_stream s);
+/* language_model.generate(..., do_sample=True, temperature=, top_k=, top_p=): the same loop with a
+ * sampled token (an extension beyond the reference, whose x2t is greedy).  HF's order: min_new EOS
+ * suppression -> temperature -> top-k -> top-p -> draw.  Per row and step, on
+ * x = logits / temperature (formed as logits * (1 / temperature) in fp32):
+ *   top_k > 0     : keep v iff fewer than top_k entries are strictly larger (ties at the k-th
+ *                   value all kept; top_k >= vocab keeps all); top_k == 0: off.
+ *   0 < top_p < 1 : on softmax(x) over the top-k survivors keep v iff the mass of survivors with
+ *                   a strictly larger x is < top_p (boundary ties kept; the top token always
+ *                   kept); top_p == 1: off.
+ * The token is the Gumbel-max over the kept set, with the noise expression of the image sampler
+ * keyed on (seed, global row = row + the "rng_image_offset" option, step): a draw that survives
+ * the filter equals the unfiltered draw for the same key; a row's tokens depend on neither the
+ * other rows of the batch nor on how a batch is split over handles.  Two rows with the same
+ * prompt have different global rows and draw different texts.  NaN counts as -inf; -inf is never
+ * kept; EOS while step < min_new is -inf before the filters; nothing kept: token 0.
+ * temperature <= 0 is pg_generate_text_greedy bit for bit (same kernels, same launches; top_k /
+ * top_p ignored).  Finished rows emit eos and the loop stops when every row is finished, as there.
+ * All five values live in device memory: a captured step graph replays with new ones.
+ * top_k < 0, top_p <= 0, top_p > 1 or NaN: PG_ERR_ARG, nothing launched.
+ * logits_out_dev: fp32 [max_new, B, vocab] or NULL (tests): the logits each emitted token was
+ * drawn from, after EOS suppression, before temperature; steps the loop did not run stay untouched. */
+int pg_generate_text_sampled(pg_handle h, int max_new, int min_new, int eos_id, float temperature, int32_t top_k,
+                             float top_p, uint64_t seed, int64_t* out_dev, int* out_len_host,
+                             float* logits_out_dev, pg_stream s);
 
 /* -- VQ-16 tokenizer ---------------------------------------------------------------------- */
 /* gen_vision_model.decode_code(codes, shape=[B,8,g,g]) (vq_model.py:505-508; call site
@@ -274,6 +298,14 @@ int pg_op_uniform(pg_handle h, const uint64_t* bits_dev, float* out_dev, int n, 
  * is in the kept set of x = logits / temperature (same rule and device code).  temperature > 0. */
 int pg_op_sample_filter(pg_handle h, const float* logits_dev /*[B,V]*/, int B, int V, float temperature, int top_k,
                         float top_p, uint8_t* keep_dev /*[B,V]*/, pg_stream s);
+
+/* The selection and draw of pg_generate_text_sampled on caller-given rows (same device code):
+ * logits_dev fp32 [B, V], 1 <= V <= vocab -> keep_dev uint8 [B, V] (or NULL) = 1 where the entry is
+ * in the kept set, tok_dev int32 [B] (or NULL) = the token drawn for key (seed, row + row_offset,
+ * step).  temperature > 0. */
+int pg_op_text_sample(pg_handle h, const float* logits_dev /*[B,V]*/, int B, int V, float temperature, int top_k,
+                      float top_p, uint64_t seed, int row_offset, int step, uint8_t* keep_dev /*[B,V]*/,
+                      int32_t* tok_dev /*[B]*/, pg_stream s);
 
 /* 3x3 convolution over NHWC activations (compute dtype), the VQ-16 ResnetBlock / Upsample /
  * Downsample conv (vq_model.py:337-352, :417-427, :440-447).  w_dev is [Cout][9][Cin]

@@ -52,6 +52,7 @@ SYMBOLS = [
     ("pg_decode_image_tokens", C.c_int, [_P, C.c_int, C.c_float, C.c_float, C.c_uint64, _P, _P, _P, _P, _P]),
     ("pg_decode_image_tokens_filtered", C.c_int, [_P, C.c_int, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_uint64, _P, _P, _P, _P, _P]),
     ("pg_generate_text_greedy", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int), _P]),
+    ("pg_generate_text_sampled", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int32, C.c_float, C.c_uint64, _P, C.POINTER(C.c_int), _P, _P]),
     ("pg_vq_decode", C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     ("pg_vq_encode", C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P]),
     ("pg_vision_encode", C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
@@ -65,6 +66,7 @@ SYMBOLS = [
     ("pg_op_swiglu_gemm", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     ("pg_op_uniform", C.c_int, [_P, _P, _P, C.c_int, _P]),
     ("pg_op_sample_filter", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, _P, _P]),
+    ("pg_op_text_sample", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, _P, _P, _P]),
     ("pg_op_conv3x3", C.c_int, [_P, _P, _P, _P, _P, _P] + [C.c_int] * 7 + [_P]),
     ("pg_op_groupnorm", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
 ]

@@ -39,6 +39,9 @@ class PlanGenConfig:
     temperature: float = 1.0
     top_k: int = 0                 # top-k / top-p (nucleus) filtering of sampled draws: an extension beyond the reference, off by default
     top_p: float = 1.0
+    text_temperature: float = 0.0  # text / layout decode: 0 = greedy (the reference); > 0 samples, with text_top_k / text_top_p (extension, off by default)
+    text_top_k: int = 0
+    text_top_p: float = 1.0
     seed: int = 0
 
     @property

@@ -103,6 +103,7 @@ struct pg_engine {
     hipEvent_t ev_stage[2] = {nullptr, nullptr}; bool stage_used[2] = {false, false}; int stage_sel = 0;
     int32_t* d_flag = nullptr; int32_t* h_flag = nullptr;        // uncond-sharing probe result
     float* cfg_pv = nullptr; int* cfg_pi = nullptr;              // sampler stage-1 winners
+    float* txt_mix = nullptr;                                    // top-k / top-p text sampler: reduced logit rows [max_rows, vocab] (first filtered call)
     float* cfg_mix = nullptr;                                    // top-k / top-p sampler: CFG-mixed rows [max_rows/2, img_vocab] (first filtered call)
     SampleParams* d_sparams = nullptr; TextParams* d_tparams = nullptr;   // per-call parameters the graphs read from HBM
     int32_t *d_out_tok = nullptr, *d_force_tok = nullptr; uint8_t* d_force_mask = nullptr; int64_t* d_text_out = nullptr;
@@ -205,7 +206,11 @@ struct pg_engine {
                      const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s);
     int step(const void* emb, int emb_dtype, void* hidden_out, int hidden_dtype, hipStream_t s);
     int gen_head(const void* h_dev, int h_dtype, float* logits, int R_, hipStream_t s);
-    int text_greedy(int max_new, int min_new, int eos, int64_t* out, int* out_len, hipStream_t s);
+    int text_greedy(int max_new, int min_new, int eos, int64_t* out, int* out_len, hipStream_t s) {
+        return text_generate(max_new, min_new, eos, 0.f, 0, 1.f, 0, out, out_len, nullptr, s);
+    }
+    int text_generate(int max_new, int min_new, int eos, float temp, int top_k, float top_p, uint64_t seed, int64_t* out, int* out_len,
+                      float* logits_out, hipStream_t s);
     template <typename T> int vq_decode(const int32_t* codes, void* img_out, int out_dtype, int B, hipStream_t s);
     template <typename T> int vq_encode(const void* img, int img_dtype, int64_t* idx, int B, hipStream_t s);
     template <typename T> void conv3(hipStream_t s, const ConvW& cw, const T* in, void* out, int out_f32, const void* residual, int res_f32, int B, int Hi, int Wi, int up, int stride2, int feeds_gn = -1);

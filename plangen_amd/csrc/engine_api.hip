@@ -103,6 +103,11 @@ int pg_generate_text_greedy(pg_handle h, int max_new, int min_new, int eos_id, i
     if (!h || !out_dev) return PG_ERR_ARG;
     return h->text_greedy(max_new, min_new, eos_id, out_dev, out_len_host, (hipStream_t)s);
 }
+int pg_generate_text_sampled(pg_handle h, int max_new, int min_new, int eos_id, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                             int64_t* out_dev, int* out_len_host, float* logits_out_dev, pg_stream s) { TuneGuard _tg(h);
+    if (!h || !out_dev) return PG_ERR_ARG;
+    return h->text_generate(max_new, min_new, eos_id, temperature, top_k, top_p, seed, out_dev, out_len_host, logits_out_dev, (hipStream_t)s);
+}
 int pg_vq_decode(pg_handle h, const int32_t* codes_dev, void* img_out_dev, int out_dtype, int B, pg_stream s) { TuneGuard _tg(h);
     if (!h || !codes_dev || !img_out_dev) return PG_ERR_ARG;
     return h->bf ? h->vq_decode<bf16>(codes_dev, img_out_dev, out_dtype, B, (hipStream_t)s)
@@ -252,6 +257,20 @@ int pg_op_sample_filter(pg_handle h, const float* logits_dev, int B, int V, floa
     }
     (void)hipSetDevice(h->dev);
     launch_sample_filter((hipStream_t)s, logits_dev, B, V, temperature, top_k, top_p, keep_dev);
+    return hipGetLastError() == hipSuccess ? PG_OK : PG_ERR_HIP;
+}
+int pg_op_text_sample(pg_handle h, const float* logits_dev, int B, int V, float temperature, int top_k, float top_p, uint64_t seed, int row_offset,
+                      int step, uint8_t* keep_dev, int32_t* tok_dev, pg_stream s) {
+    if (!h || !logits_dev || (!keep_dev && !tok_dev)) return PG_ERR_ARG;
+    if (B < 1 || V < 1 || V > h->cfg.vocab) { h->err = "pg_op_text_sample: needs B >= 1 and 1 <= V <= vocab"; return PG_ERR_ARG; }
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) {
+        h->err = "pg_op_text_sample: needs temperature > 0, top_k >= 0, top_p in (0, 1]"; return PG_ERR_ARG;
+    }
+    (void)hipSetDevice(h->dev);
+    TextSelectArgs f{};
+    f.rows = logits_dev; f.V = V; f.temperature = temperature; f.top_k = top_k; f.top_p = top_p; f.seed = seed; f.row_off = row_offset; f.step = step;
+    f.keep = keep_dev; f.tok = tok_dev;
+    launch_text_select((hipStream_t)s, f, B);
     return hipGetLastError() == hipSuccess ? PG_OK : PG_ERR_HIP;
 }
 int pg_op_conv3x3(pg_handle h, const void* x_dev, const void* w_dev, const float* bias_dev, const void* residual_dev,

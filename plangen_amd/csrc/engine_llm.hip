@@ -432,23 +432,29 @@ int pg_engine::gen_head(const void* h_dev, int h_dtype, float* logits, int R_, h
     return PG_OK;
 }
 
-int pg_engine::text_greedy(int max_new, int min_new, int eos, int64_t* out, int* out_len, hipStream_t s) {
-    if (!prefilled) FAIL(PG_ERR_STATE, "pg_generate_text_greedy before pg_prefill");
+int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int top_k, float top_p, uint64_t seed, int64_t* out, int* out_len,
+                             float* logits_out, hipStream_t s) {
+    if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(PG_ERR_ARG, "top_k=%d must be >= 0 and top_p=%g in (0, 1]", top_k, (double)top_p);
+    if (!prefilled) FAIL(PG_ERR_STATE, "text decode before pg_prefill");
     if (!cfg.with_lm_head) FAIL(PG_ERR_STATE, "engine created without lm_head");
     if (n_dec_host != 0) FAIL(PG_ERR_STATE, "text decode needs a fresh prefill");
     if (max_new < 1 || max_new > cfg.max_new || max_new > 1000) FAIL(PG_ERR_CAPACITY, "max_new=%d exceeds capacity %d", max_new, cfg.max_new);
     HIPCHK(hipSetDevice(dev));
     const int B = R;
+    // launch structure: greedy argmax (temperature <= 0 ignores the filters, as HF's warpers do) / Gumbel-max folded into the scan /
+    // scan -> workspace -> select.  Everything else about sampling is a value in TextParams.
+    const int mode = !(temp > 0.f) ? 0 : ((top_k > 0 || top_p < 1.f) ? 2 : 1);
+    if (mode == 2 && !txt_mix) TRY(dalloc(&txt_mix, (size_t)cfg.max_rows * cfg.vocab * 4, false));
     std::vector<int32_t> ones(B, 1);
     HIPCHK(hipMemcpyAsync(d_unf, ones.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(d_anyunf, 0, 1024 * 4, s));
     HIPCHK(hipStreamSynchronize(s));
     TextArgs ta{};
     ta.V = cfg.vocab; ta.p = d_tparams; ta.out = d_text_out; ta.unfinished = d_unf;
-    ta.any_unfinished = d_anyunf; ta.embed_table = embed; ta.x = x; ta.H = H(); ta.n_dec = d_ndec;
+    ta.any_unfinished = d_anyunf; ta.embed_table = embed; ta.x = x; ta.H = H(); ta.n_dec = d_ndec; ta.logits_out = logits_out;
     std::vector<int32_t> flags(1024);
     int checked = 0, done_len = -1;
-    // one step = lm_head GEMM -> argmax / EOS bookkeeping (device step counter) -> the stack on the new
+    // one step = lm_head GEMM -> argmax or draw / EOS bookkeeping (device step counter) -> the stack on the new
     // token's embedding.  Like the image loop it is captured once and replayed; every 8th step the
     // any-unfinished flags come back to the host (HF generate stops when every row has emitted EOS).
     hipStream_t ws = s;
@@ -457,18 +463,26 @@ int pg_engine::text_greedy(int max_new, int min_new, int eos, int64_t* out, int*
         HIPCHK(hipStreamWaitEvent(istream, ev_in, 0));
         ws = istream;
     }
-    { TextParams tp{}; tp.eos = eos; tp.min_new = min_new; tp.max_new = max_new; launch_set_text_params(ws, d_tparams, tp); }
+    {
+        TextParams tp{}; tp.eos = eos; tp.min_new = min_new; tp.max_new = max_new;
+        tp.temperature = temp; tp.top_k = top_k; tp.top_p = top_p; tp.seed = seed; tp.row_off = rng_image_offset;
+        launch_set_text_params(ws, d_tparams, tp);
+    }
     auto iteration = [&](bool with_forward) {
         if (bf) gemm_llm<bf16>(ws, (const bf16*)hfin, (const bf16*)lm_head, B, cfg.vocab, H(), true, lm_head_t);
         else gemm_llm<float>(ws, (const float*)hfin, (const float*)lm_head, B, cfg.vocab, H(), true);
         ta.logits_partial = part; ta.S = S_last; ta.slab = slab_last;
-        launch_text_argmax(ws, ta, B, cfg_pv, cfg_pi);
+        if (mode == 2) launch_text_sample_filtered(ws, ta, B, cfg_pv, cfg_pi, txt_mix);
+        else if (mode == 1) launch_text_sample(ws, ta, B, cfg_pv, cfg_pi);
+        else launch_text_argmax(ws, ta, B, cfg_pv, cfg_pi);
         if (with_forward) forward_decode(ws);
     };
     for (int step_i = 0; step_i < max_new; ++step_i) {
         const bool last = step_i == max_new - 1;
         if (use_graph && !last && step_i > 0) {
-            std::vector<int64_t> key = {R, (int64_t)bf, (int64_t)fuse_rope, (int64_t)shared_len, (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch};
+            // shapes and kernel selection only: temperature, top_k, top_p, seed and the row offset reach the kernels through TextParams
+            std::vector<int64_t> key = {R, (int64_t)bf, (int64_t)fuse_rope, (int64_t)shared_len, (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch,
+                                        (int64_t)mode, (int64_t)logits_out};
             if (!gexec_txt || key != gkey_txt) {
                 if (gexec_txt) { (void)hipGraphExecDestroy(gexec_txt); gexec_txt = nullptr; }
                 hipGraph_t g = nullptr;

@@ -208,18 +208,36 @@ struct FilterArgs {
 };
 void launch_cfg_sample_filtered(hipStream_t s, const SampleArgs& a, int B, float* scratch_v, int* scratch_i, float* mix);
 void launch_sample_filter(hipStream_t s, const float* rows, int B, int V, float temperature, int top_k, float top_p, uint8_t* keep);
-// greedy text: argmax over vocab of (sum_s partial) per row + EOS bookkeeping, writes
-// out[b, step] (int64) and next-token embedding into x.
-struct TextParams { int32_t eos, min_new, max_new, pad; };
+// text token: argmax over vocab of (sum_s partial) per row + EOS bookkeeping, writes out[b, step] (int64) and next-token embedding into x.
+// Per-call parameters (device memory, like SampleParams): temperature <= 0 is the greedy argmax; temperature > 0 draws by Gumbel-max over
+// logits / temperature keyed on (seed, row + row_off, step), optionally restricted to the top-k / top-p kept set (launch_text_sample_filtered).
+struct TextParams { int32_t eos, min_new, max_new, top_k; float temperature, top_p; int32_t row_off, pad; uint64_t seed; };
 struct TextArgs {
     const float* logits_partial; int S; long slab; int V;
     const TextParams* p;
     int64_t* out;                                                 // [B, max_new] library-owned
     int32_t* unfinished; int32_t* any_unfinished;
     const float* embed_table; float* x; int H; const int32_t* n_dec;
+    float* logits_out;                                            // [max_new, B, V] or null (tests): the row after EOS suppression
 };
 void launch_set_text_params(hipStream_t s, TextParams* dst, TextParams v);
 void launch_text_argmax(hipStream_t s, const TextArgs& a, int B, float* scratch_v, int* scratch_i);   // scratch: B * 16 entries each
+// unfiltered sampling (p->temperature > 0): the same two launches, the scan perturbs every logit with the sampler's Gumbel noise
+void launch_text_sample(hipStream_t s, const TextArgs& a, int B, float* scratch_v, int* scratch_i);
+// top-k / top-p sampling for rows of any length (no row-in-LDS assumption): the scan writes the reduced rows to mix [B, V] and the per-chunk
+// maxima to scratch_v; text_select_kernel (one 1024-thread block per row) finds the kept set and draws from it; then text_argmax_kernel
+struct TextSelectArgs {
+    const float* rows; int V;                                     // [gridDim, V] fp32
+    const float* chunk_max;                                       // [gridDim, 16] maxima of the row's chunks, or null (the kernel scans for the maximum)
+    const TextParams* p;                                          // loop: temperature / top_k / top_p / seed / row_off from device memory
+    float temperature; int top_k; float top_p; uint64_t seed; int row_off, step;    // operator (p == null): from the host
+    const int32_t* n_dec;                                         // loop: device step counter
+    uint8_t* keep;                                                // [gridDim, V] kept mask or null
+    float* pv; int* pi;                                           // loop: winner -> stage-1 winner slots
+    int32_t* tok;                                                 // operator: [gridDim] drawn token or null
+};
+void launch_text_sample_filtered(hipStream_t s, const TextArgs& a, int B, float* scratch_v, int* scratch_i, float* mix);
+void launch_text_select(hipStream_t s, const TextSelectArgs& f, int B);
 void launch_advance(hipStream_t s, int32_t* n_dec);
 void launch_rows_differ(hipStream_t s, const int32_t* ids, int L, int first, int stride, int ref, int n, int from, int32_t* flag);
 void launch_uniform_from_bits(hipStream_t s, const uint64_t* z, float* out, int n);

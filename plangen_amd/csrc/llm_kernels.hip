@@ -705,12 +705,17 @@ void launch_sample_filter(hipStream_t s, const float* rows, int B, int V, float 
     hipLaunchKernelGGL(cfg_select_kernel, dim3(B), dim3(SEL_THREADS), 0, s, f);
 }
 
-// greedy text token (HF generate, do_sample=False): argmax over vocab, finished rows emit
-// eos, unfinished &= (tok != eos).  Two stages like the image sampler: grid (CFG_CHUNKS, B) scans V/CFG_CHUNKS logits with
+// text token (HF generate): greedy = argmax over vocab; sampled = Gumbel-max over logits / T (== multinomial(softmax(logits / T)));
+// finished rows emit eos, unfinished &= (tok != eos).  Two stages like the image sampler: grid (CFG_CHUNKS, B) scans V/CFG_CHUNKS logits with
 // 16-byte loads (split-K slabs summed in slab order), one block per row combines the winners (lowest index on ties =
 // torch.argmax), does the EOS bookkeeping and gathers the next embedding.  (One block per row over 102 400 logits with
 // scalar loads was 160 us per step at 64 rows; this pair is ~10.)
-__global__ __launch_bounds__(256) void text_scan_kernel(TextArgs a, float* __restrict__ pv, int* __restrict__ pi) {
+// MODE: TEXT_GREEDY (the argmax, as before), TEXT_SAMPLE (every logit perturbed by gumbel_perturb with p->temperature / seed / row_off: no extra
+// pass), TEXT_STORE (filtered sampler: the reduced row, EOS suppression applied, goes to mix [B, V]; the winners are the chunk MAXIMA of the
+// unperturbed row, which text_select_kernel reads as the softmax shift).  TAP: also write the row to logits_out [max_new, B, V].
+enum { TEXT_GREEDY = 0, TEXT_SAMPLE = 1, TEXT_STORE = 2 };
+template <int MODE, bool TAP>
+__global__ __launch_bounds__(256) void text_scan_kernel(TextArgs a, float* __restrict__ pv, int* __restrict__ pi, float* __restrict__ mix) {
     __shared__ float sv[4]; __shared__ int si[4];
     const int ch = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, step = *a.n_dec;
     const int ban = step < a.p->min_new ? a.p->eos : -1;
@@ -718,6 +723,13 @@ __global__ __launch_bounds__(256) void text_scan_kernel(TextArgs a, float* __res
     const int v0 = ch * chunk, v1 = v0 + chunk < a.V ? v0 + chunk : a.V;
     const float* lp = a.logits_partial + (long)b * a.V;
     float best = -INFINITY; int bi = 0x7fffffff;
+    float invT = 1.f; uint64_t seed = 0, stream = 0;
+    if (MODE == TEXT_SAMPLE) {
+        invT = 1.f / a.p->temperature; seed = a.p->seed;
+        stream = (uint64_t)(b + a.p->row_off) * 1000003ull + step;
+    }
+    float* tap = TAP ? a.logits_out + ((long)step * gridDim.y + b) * a.V : nullptr;
+    float* mrow = MODE == TEXT_STORE ? mix + (long)b * a.V : nullptr;
     if (((a.V | (int)(a.slab & 3)) & 3) == 0) {
         // eight independent 16-byte loads per slab in flight per thread (addresses clamped into the chunk, validity applied to the
         // compare): a plain `for v` / `for s` nest is one dependent round trip per vector and slab
@@ -742,9 +754,19 @@ __global__ __launch_bounds__(256) void text_scan_kernel(TextArgs a, float* __res
 #pragma unroll
             for (int it = 0; it < IT; ++it) {
                 const int v = vb + it * 1024;
+                if (MODE == TEXT_STORE || TAP) {
+                    if (v < v1) {                                  // V % 4 == 0: a vector is wholly inside the chunk or wholly outside
+                        f32x4 w = c[it];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) if (v + j == ban) w[j] = -INFINITY;
+                        if (TAP) *(f32x4*)(tap + v) = w;
+                        if (MODE == TEXT_STORE) *(f32x4*)(mrow + v) = w;
+                    }
+                }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float cj = (v + j == ban || v >= v1) ? -INFINITY : c[it][j];
+                    float cj = (v + j == ban || v >= v1) ? -INFINITY : c[it][j];
+                    if (MODE == TEXT_SAMPLE && v < v1) cj = gumbel_perturb(cj, invT, seed, stream, v + j);
                     if (cj > best) { best = cj; bi = v + j; }
                 }
             }
@@ -754,6 +776,9 @@ __global__ __launch_bounds__(256) void text_scan_kernel(TextArgs a, float* __res
             float c = 0.f;
             for (int s = 0; s < a.S; ++s) c += lp[(long)s * a.slab + v];
             if (v == ban) c = -INFINITY;
+            if (TAP) tap[v] = c;
+            if (MODE == TEXT_STORE) mrow[v] = c;
+            if (MODE == TEXT_SAMPLE) c = gumbel_perturb(c, invT, seed, stream, v);
             if (c > best) { best = c; bi = v; }
         }
     }
@@ -791,8 +816,305 @@ __global__ __launch_bounds__(256) void text_argmax_kernel(TextArgs a, const floa
     float* x0 = a.x + (long)b * a.H;
     for (int i = tid * 4; i < a.H; i += 1024) *(f32x4*)(x0 + i) = *(const f32x4*)(src + i);
 }
+template <int MODE>
+static void launch_text_scan(hipStream_t s, const TextArgs& a, int B, float* scratch_v, int* scratch_i, float* mix) {
+    if (a.logits_out) hipLaunchKernelGGL((text_scan_kernel<MODE, true>), dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i, mix);
+    else hipLaunchKernelGGL((text_scan_kernel<MODE, false>), dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i, mix);
+}
 void launch_text_argmax(hipStream_t s, const TextArgs& a, int B, float* scratch_v, int* scratch_i) {
-    hipLaunchKernelGGL(text_scan_kernel, dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i);
+    launch_text_scan<TEXT_GREEDY>(s, a, B, scratch_v, scratch_i, nullptr);
+    hipLaunchKernelGGL(text_argmax_kernel, dim3(B), dim3(256), 0, s, a, scratch_v, scratch_i);
+}
+void launch_text_sample(hipStream_t s, const TextArgs& a, int B, float* scratch_v, int* scratch_i) {
+    launch_text_scan<TEXT_SAMPLE>(s, a, B, scratch_v, scratch_i, nullptr);
+    hipLaunchKernelGGL(text_argmax_kernel, dim3(B), dim3(256), 0, s, a, scratch_v, scratch_i);
+}
+
+// ------------------------------------------------------------------------------- top-k / top-p text sampler
+// The rule of cfg_select_kernel (same keys, same 2^-40 fixed-point masses, same Gumbel noise) for rows that do not fit in LDS
+// (vocab 102 400 = 400 KiB): one 1024-thread block per row over the fp32 row in global memory (written by the scan just before: L2 resident).
+//   1. m = row maximum (from the scan's chunk maxima, or one pass), the softmax shift.
+//   2. one pass: histogram of the 12 leading key bits (sign, exponent, 3 mantissa bits): counts, and exp-masses when top-p acts alone.
+//   3. floor bucket = the bucket that holds the k-th largest entry (top_k on: the top-p threshold lies at or above it too), else the
+//      bucket that holds the top-p threshold (exact from the bucket masses: no top-k, so Z is the whole row's mass).
+//   4. entries at or above the floor are compacted into LDS (<= TSEL_CAND of them: 50 for top_k = 50, ~14 000 for top_p = 0.9 on a
+//      Gaussian row) and text_thresholds -- the 8-bit radix walks of cfg_select_kernel -- runs over them.  More candidates than fit
+//      (top_p just below 1 on a flat row): the same walks run over the row in global memory instead.  Both give the same thresholds,
+//      which depend on the multiset of values only (compaction order does not matter; all mass sums are 64-bit integers).
+//   5. one pass: kept = key >= tau; kept mask (operator) and Gumbel-max over the kept set -> slot 0 of the winners text_argmax_kernel combines.
+#define TSEL_BITS 12
+#define TSEL_BUCKETS (1 << TSEL_BITS)
+#define TSEL_CAND 16384
+struct TextWalkShm {
+    uint32_t hist[256]; unsigned long long mhist[256];
+    uint32_t digit, rem; unsigned long long z, above;
+};
+// f(v, value) over a row with 16-byte loads when the row allows it (V % 4 == 0 and a 16-byte aligned base)
+template <class F>
+__device__ __forceinline__ void text_row_each(const float* __restrict__ row, int V, int tid, F f) {
+    if (((V & 3) | (int)((uintptr_t)row & 15)) == 0) {
+        for (int v = tid * 4; v < V; v += SEL_THREADS * 4) {
+            const f32x4 c = *(const f32x4*)(row + v);
+            f(v, c[0]); f(v + 1, c[1]); f(v + 2, c[2]); f(v + 3, c[3]);
+        }
+    } else {
+        for (int v = tid; v < V; v += SEL_THREADS) f(v, row[v]);
+    }
+}
+struct TextSrcRow {          // the whole row in global memory
+    const float* row; int V;
+    template <class F> __device__ __forceinline__ void each(int tid, F f) const { text_row_each(row, V, tid, [&](int, float x) { f(x); }); }
+};
+struct TextSrcLds {          // the compacted candidates
+    const float* p; int n;
+    template <class F> __device__ __forceinline__ void each(int tid, F f) const { for (int i = tid; i < n; i += SEL_THREADS) f(p[i]); }
+};
+// tau = max(top-k threshold, top-p threshold) over the entries of src (cfg_select_kernel's walks).  rem_k: rank of the top-k threshold
+// (0: top-k off); have_z: Z is z_in (top-k off: the caller knows the row's whole mass), else it is summed over the top-k survivors.
+template <class Src>
+__device__ __forceinline__ uint32_t text_thresholds(const Src src, TextWalkShm& w, float invT, uint32_t rem_k, float top_p, uint32_t kmx, bool have_z,
+                                    unsigned long long z_in) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    uint32_t tk = 0;
+    if (rem_k > 0) {
+        uint32_t prefix = 0, pmask = 0, rem = rem_k;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) w.hist[tid] = 0;
+            __syncthreads();
+            src.each(tid, [&](float x) {
+                const uint32_t k = sel_key(x, invT);
+                if ((k & pmask) == prefix) atomicAdd(&w.hist[(k >> shift) & 255u], 1u);
+            });
+            __syncthreads();
+            if (tid < 64) {          // lane l holds digits 255-4l .. 252-4l (descending): bucket of the rem-th largest
+                uint32_t h[4], sum = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { h[j] = w.hist[255 - 4 * lane - j]; sum += h[j]; }
+                uint32_t incl = sum;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+                uint32_t before = incl - sum;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (before < rem && before + h[j] >= rem) { w.digit = 255 - 4 * lane - j; w.rem = rem - before; }
+                    before += h[j];
+                }
+            }
+            __syncthreads();
+            prefix |= w.digit << shift; pmask |= 255u << shift; rem = w.rem;
+        }
+        tk = prefix;
+    }
+    uint32_t tp = 0;
+    if (top_p < 1.f && kmx > SEL_KEY_NEGINF) {
+        const float m = sel_unkey(kmx);
+        if (tid == 0) w.z = have_z ? z_in : 0;
+        __syncthreads();
+        if (!have_z) {
+            unsigned long long z = 0;
+            src.each(tid, [&](float x) {
+                const uint32_t k = sel_key(x, invT);
+                if (k >= tk) z += sel_mass(k, m);
+            });
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) z += shfl_xor_u64(z, o);
+            if (lane == 0) atomicAdd(&w.z, z);
+            __syncthreads();
+        }
+        const double limit = (double)top_p * (double)w.z;
+        uint32_t prefix = 0, pmask = 0;
+        unsigned long long above = 0;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) { w.hist[tid] = 0; w.mhist[tid] = 0; }
+            __syncthreads();
+            src.each(tid, [&](float x) {
+                const uint32_t k = sel_key(x, invT);
+                if (k >= tk && (k & pmask) == prefix) {
+                    const uint32_t d = (k >> shift) & 255u;
+                    atomicAdd(&w.hist[d], 1u);
+                    const unsigned long long q = sel_mass(k, m);
+                    if (q) atomicAdd(&w.mhist[d], q);
+                }
+            });
+            __syncthreads();
+            if (tid < 64) {          // lowest non-empty bucket whose strictly-larger mass is < limit
+                uint32_t c[4]; unsigned long long mm[4], sum = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { c[j] = w.hist[255 - 4 * lane - j]; mm[j] = w.mhist[255 - 4 * lane - j]; sum += mm[j]; }
+                unsigned long long incl = sum;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) { const unsigned long long t = shfl_up_u64(incl, o); if (lane >= o) incl += t; }
+                unsigned long long cum = above + incl - sum;
+                int dj = -1; unsigned long long cj = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (c[j] && (double)cum < limit) { dj = 255 - 4 * lane - j; cj = cum; }
+                    cum += mm[j];
+                }
+                const unsigned long long has = __ballot(dj >= 0);
+                if (dj >= 0 && lane == 63 - __clzll(has)) { w.digit = (uint32_t)dj; w.above = cj; }
+            }
+            __syncthreads();
+            prefix |= w.digit << shift; pmask |= 255u << shift; above = w.above;
+        }
+        tp = prefix;
+    }
+    __syncthreads();
+    uint32_t tau = tk > tp ? tk : tp;
+    return tau > SEL_KEY_NEGINF + 1 ? tau : SEL_KEY_NEGINF + 1;
+}
+__global__ __launch_bounds__(SEL_THREADS) void text_select_kernel(TextSelectArgs f) {
+    // phase 2-3: cnt[TSEL_BUCKETS] u32 | mass[TSEL_BUCKETS] u64 (48 KiB); phase 4: cand[TSEL_CAND] fp32 (64 KiB)
+    __shared__ __attribute__((aligned(16))) unsigned char buf[TSEL_CAND * 4];
+    __shared__ TextWalkShm w;
+    __shared__ uint32_t s_max, s_floor, s_nc, s_fill;
+    __shared__ uint32_t wcnt[SEL_THREADS / 64]; __shared__ unsigned long long wmass[SEL_THREADS / 64];
+    __shared__ float wv[SEL_THREADS / 64]; __shared__ int wi[SEL_THREADS / 64];
+    uint32_t* cnt = (uint32_t*)buf;
+    unsigned long long* mass = (unsigned long long*)(buf + TSEL_BUCKETS * 4);
+    float* cand = (float*)buf;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, V = f.V;
+    const float temperature = f.p ? f.p->temperature : f.temperature;
+    const int top_k = f.p ? f.p->top_k : f.top_k;
+    const float top_p = f.p ? f.p->top_p : f.top_p;
+    const float invT = temperature > 0.f ? 1.f / temperature : 1.f;
+    const float* row = f.rows + (long)b * V;
+    // ---- 1. the row maximum
+    if (tid == 0) { s_max = 0; s_floor = TSEL_BUCKETS; s_nc = 0; s_fill = 0; }
+    __syncthreads();
+    if (f.chunk_max) {
+        if (tid < CFG_CHUNKS) atomicMax(&s_max, sel_key(f.chunk_max[b * CFG_CHUNKS + tid], invT));
+    } else {
+        uint32_t kmax = 0;
+        text_row_each(row, V, tid, [&](int, float x) { const uint32_t k = sel_key(x, invT); kmax = k > kmax ? k : kmax; });
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const uint32_t t = __shfl_xor(kmax, o, 64); kmax = t > kmax ? t : kmax; }
+        if (lane == 0) atomicMax(&s_max, kmax);
+    }
+    __syncthreads();
+    const uint32_t kmx = s_max;
+    const bool k_on = top_k > 0 && top_k < V;
+    const bool p_on = top_p < 1.f && kmx > SEL_KEY_NEGINF;
+    uint32_t tau = SEL_KEY_NEGINF + 1;
+    if (k_on || p_on) {
+        // ---- 2. first-digit histogram
+        const bool need_mass = !k_on;
+        const float m = sel_unkey(kmx);
+        for (int i = tid; i < TSEL_BUCKETS; i += SEL_THREADS) { cnt[i] = 0; mass[i] = 0; }
+        __syncthreads();
+        text_row_each(row, V, tid, [&](int, float x) {
+            const uint32_t k = sel_key(x, invT), d = k >> (32 - TSEL_BITS);
+            atomicAdd(&cnt[d], 1u);
+            if (need_mass) { const unsigned long long q = sel_mass(k, m); if (q) atomicAdd(&mass[d], q); }
+        });
+        __syncthreads();
+        // ---- 3. the floor bucket: thread t holds buckets top-4t .. top-4t-3 (descending); block-wide exclusive prefix from the top
+        constexpr int top = TSEL_BUCKETS - 1;
+        uint32_t h[4], hs = 0; unsigned long long mm[4], ms = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { h[j] = cnt[top - 4 * tid - j]; mm[j] = mass[top - 4 * tid - j]; hs += h[j]; ms += mm[j]; }
+        uint32_t hin = hs; unsigned long long min_ = ms;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t t = __shfl_up(hin, o, 64); const unsigned long long u = shfl_up_u64(min_, o);
+            if (lane >= o) { hin += t; min_ += u; }
+        }
+        if (lane == 63) { wcnt[wave] = hin; wmass[wave] = min_; }
+        __syncthreads();
+        uint32_t before = hin - hs; unsigned long long cum = min_ - ms, ztot = 0;
+        for (int i = 0; i < SEL_THREADS / 64; ++i) {
+            if (i < wave) { before += wcnt[i]; cum += wmass[i]; }
+            ztot += wmass[i];
+        }
+        if (k_on) {
+            uint32_t bf = before;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (bf < (uint32_t)top_k && bf + h[j] >= (uint32_t)top_k) { s_floor = top - 4 * tid - j; s_nc = bf + h[j]; }
+                bf += h[j];
+            }
+        } else {
+            const double limit = (double)top_p * (double)ztot;
+            int dj = -1;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (h[j] && (double)cum < limit) dj = top - 4 * tid - j;
+                cum += mm[j];
+            }
+            if (dj >= 0) atomicMin(&s_floor, (uint32_t)dj);
+        }
+        __syncthreads();
+        const uint32_t floor_d = s_floor;
+        if (!k_on) {          // candidates at or above the floor: the inclusive count at that bucket
+            uint32_t bf = before;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { bf += h[j]; if ((uint32_t)(top - 4 * tid - j) == floor_d) s_nc = bf; }
+        }
+        __syncthreads();
+        const uint32_t nc = s_nc;
+        if (nc <= TSEL_CAND) {
+            // ---- 4. compact (one LDS atomic per wave and element slot), then the walks over LDS
+            text_row_each(row, V, tid, [&](int, float x) {
+                const bool in = (sel_key(x, invT) >> (32 - TSEL_BITS)) >= floor_d;
+                const unsigned long long bal = __ballot(in);
+                if (bal) {
+                    uint32_t base = 0;
+                    const int leader = __ffsll((long long)bal) - 1;
+                    if (lane == leader) base = atomicAdd(&s_fill, (uint32_t)__popcll(bal));
+                    base = __shfl(base, leader, 64);
+                    if (in) cand[base + __popcll(bal & ((1ull << lane) - 1ull))] = x;
+                }
+            });
+            __syncthreads();
+            tau = text_thresholds(TextSrcLds{cand, (int)nc}, w, invT, k_on ? (uint32_t)top_k : 0u, top_p, kmx, !k_on, ztot);
+        } else {
+            tau = text_thresholds(TextSrcRow{row, V}, w, invT, k_on ? (uint32_t)top_k : 0u, top_p, kmx, false, 0ull);
+        }
+    }
+    // ---- 5. kept mask (operator) / Gumbel-max over the kept set
+    const bool draw = f.pv || f.tok;
+    float best = -INFINITY; int bi = 0x7fffffff;
+    uint64_t seed = 0, stream = 0;
+    if (draw) {
+        const int step = f.n_dec ? *f.n_dec : f.step;
+        seed = f.p ? f.p->seed : f.seed;
+        stream = (uint64_t)(b + (f.p ? f.p->row_off : f.row_off)) * 1000003ull + step;
+    }
+    uint8_t* keep = f.keep ? f.keep + (long)b * V : nullptr;
+    text_row_each(row, V, tid, [&](int v, float x) {
+        const bool kept = sel_key(x, invT) >= tau;
+        if (keep) keep[v] = kept;
+        if (draw && kept) {
+            const float g = gumbel_perturb(x, invT, seed, stream, v);
+            if (g > best) { best = g; bi = v; }
+        }
+    });
+    if (!draw) return;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
+        argmax_combine(best, bi, ov, oi);
+    }
+    if (lane == 0) { wv[wave] = best; wi[wave] = bi; }
+    __syncthreads();
+    if (tid < CFG_CHUNKS) {
+        float v = -INFINITY; int i = 0x7fffffff;
+        if (tid == 0) {
+            v = wv[0]; i = wi[0];
+            for (int k = 1; k < SEL_THREADS / 64; ++k) argmax_combine(v, i, wv[k], wi[k]);
+            if (f.tok) f.tok[b] = i == 0x7fffffff ? 0 : i;          // nothing kept (every entry -inf / NaN): token 0
+        }
+        if (f.pv) { f.pv[b * CFG_CHUNKS + tid] = v; f.pi[b * CFG_CHUNKS + tid] = i; }
+    }
+}
+void launch_text_select(hipStream_t s, const TextSelectArgs& f, int B) {
+    hipLaunchKernelGGL(text_select_kernel, dim3(B), dim3(SEL_THREADS), 0, s, f);
+}
+void launch_text_sample_filtered(hipStream_t s, const TextArgs& a, int B, float* scratch_v, int* scratch_i, float* mix) {
+    launch_text_scan<TEXT_STORE>(s, a, B, scratch_v, scratch_i, mix);
+    TextSelectArgs f{};
+    f.rows = mix; f.V = a.V; f.chunk_max = scratch_v; f.p = a.p; f.n_dec = a.n_dec; f.pv = scratch_v; f.pi = scratch_i;
+    launch_text_select(s, f, B);
     hipLaunchKernelGGL(text_argmax_kernel, dim3(B), dim3(256), 0, s, a, scratch_v, scratch_i);
 }
 

@@ -406,6 +406,22 @@ class Engine:
         self._keep = [ft, fm, out, lg]
         return (out, lg) if return_logits else out
 
+    def generate_text(self, max_new_tokens: int, eos_id: int, min_new_tokens: int = 0, temperature: float = 0.0, top_k: int = 0,
+                      top_p: float = 1.0, seed: int = 0, return_logits: bool = False):
+        """The text decode loop after a ``prefill*(position_mode=1)``: new tokens only, int64 [R, n <= max_new_tokens], finished rows
+        padded with eos.  temperature <= 0: greedy (``generate_text_greedy``, bit for bit).  temperature > 0: sampled in HF's order
+        (min_new EOS suppression -> temperature -> top-k -> top-p -> draw), keyed on (seed, row + the ``rng_image_offset`` option, step):
+        a row's tokens do not depend on the other rows, and two rows that carry the same prompt draw different texts.
+        return_logits: also fp32 [n, R, vocab], the logits every emitted token was drawn from.  Semantics: include/plangen_hip.h."""
+        out = torch.full((self.R, max_new_tokens), eos_id, dtype=torch.int64, device=self.device)
+        lg = torch.zeros((max_new_tokens, self.R, self.cfg.vocab), dtype=torch.float32, device=self.device) if return_logits else None
+        n = C.c_int(0)
+        self._check(self.lib.pg_generate_text_sampled(self.h, max_new_tokens, min_new_tokens, eos_id, float(temperature), int(top_k),
+                                                      float(top_p), int(seed), self._p(out), C.byref(n), self._p(lg), self.stream),
+                    "pg_generate_text_sampled")
+        self._keep = [out, lg]
+        return (out[:, :n.value], lg[:n.value]) if return_logits else out[:, :n.value]
+
     def generate_text_greedy(self, max_new_tokens: int, eos_id: int, min_new_tokens: int = 0) -> torch.Tensor:
         out = torch.full((self.R, max_new_tokens), eos_id, dtype=torch.int64, device=self.device)
         n = C.c_int(0)
@@ -512,6 +528,19 @@ class Engine:
                                                  self._p(keep), self.stream), "pg_op_sample_filter")
         self._keep = [x, keep]
         return keep.bool().reshape(logits.shape)
+
+    def text_sample(self, logits: torch.Tensor, temperature: float, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
+                    row_offset: int = 0, step: int = 0):
+        """pg_op_text_sample: the text sampler's selection and draw over fp32 rows ``logits`` [B, V], V <= vocab ->
+        (kept mask bool [B, V], drawn token int32 [B]) for the keys (seed, row + row_offset, step)."""
+        x = self._dev(logits, torch.float32).reshape(-1, logits.shape[-1]).contiguous()
+        B, V = x.shape
+        keep = torch.zeros((B, V), dtype=torch.uint8, device=self.device)
+        tok = torch.full((B,), -1, dtype=torch.int32, device=self.device)
+        self._check(self.lib.pg_op_text_sample(self.h, self._p(x), B, V, float(temperature), int(top_k), float(top_p), int(seed),
+                                               int(row_offset), int(step), self._p(keep), self._p(tok), self.stream), "pg_op_text_sample")
+        self._keep = [x, keep, tok]
+        return keep.bool(), tok
 
     def op_conv3x3(self, x_nhwc: torch.Tensor, w_oihw: torch.Tensor, bias: torch.Tensor, residual=None, up: int = 0,
                    stride2: int = 0) -> torch.Tensor:

@@ -93,18 +93,28 @@ class _LanguageModel:
     def generate(self, inputs_embeds: torch.Tensor = None, attention_mask: Optional[torch.Tensor] = None,
                  pad_token_id: Optional[int] = None, bos_token_id: Optional[int] = None,
                  eos_token_id: Optional[int] = None, max_new_tokens: int = 512, do_sample: bool = False,
-                 use_cache: bool = True, min_new_tokens: int = 0, **kw) -> torch.Tensor:
-        """HF GenerationMixin.generate, greedy (System.x2t, plangen_base.py:513-523): returns the
-        NEW tokens only, int64 [B, n<=max_new_tokens], finished rows padded with eos."""
-        if do_sample:
-            raise PlanGenError("only greedy decoding (do_sample=False) is what the reference uses")
+                 use_cache: bool = True, min_new_tokens: int = 0, temperature: float = 1.0, top_k: int = 0,
+                 top_p: float = 1.0, seed: int = 0, **kw) -> torch.Tensor:
+        """HF GenerationMixin.generate (System.x2t, plangen_base.py:513-523): returns the NEW tokens only, int64
+        [B, n<=max_new_tokens], finished rows padded with eos.  do_sample=False (the reference's call) is greedy and
+        ignores temperature / top_k / top_p like HF; do_sample=True draws with them (temperature -> top-k -> top-p,
+        0 / 1.0 = filter off) from the engine's counter RNG keyed on (``seed``, row, step) -- not torch's generator."""
+        if do_sample and not temperature > 0:
+            raise PlanGenError(f"do_sample=True needs temperature > 0 (got {temperature})")
+        if do_sample and top_k is None:
+            top_k = 0
+        if do_sample and top_p is None:
+            top_p = 1.0
         if eos_token_id is None:
             raise PlanGenError("eos_token_id is required")
         R, L, _ = inputs_embeds.shape
         pad = [0] * R if attention_mask is None else Engine.pad_len_from_mask(attention_mask, L)
         self.eng.prefill_embeds(inputs_embeds, pad, position_mode=1)
         self.model.epoch += 1          # invalidates any sample_image cache token
-        return self.eng.generate_text_greedy(max_new_tokens, int(eos_token_id), min_new_tokens)
+        if not do_sample:
+            return self.eng.generate_text_greedy(max_new_tokens, int(eos_token_id), min_new_tokens)
+        return self.eng.generate_text(max_new_tokens, int(eos_token_id), min_new_tokens, temperature=float(temperature),
+                                      top_k=int(top_k), top_p=float(top_p), seed=int(seed))
 
 
 class _GenVisionModel:

@@ -71,7 +71,8 @@ class System:
     """Inference half of PlanGen's System on one MI355X.
 
     args carries the cfg keys the path reads (cfg/base.py): seed, parallel_size, cfg_weight,
-    temperature, use_teacher_forcing, debug_max_seq_len, janus_hw; optionally top_k / top_p (sampling filters, off when absent).
+    temperature, use_teacher_forcing, debug_max_seq_len, janus_hw; optionally top_k / top_p (image sampling filters, off when absent)
+    and text_temperature / text_top_k / text_top_p (sampled layout / caption decode, greedy when absent).
     """
 
     def __init__(self, cfg: PlanGenConfig, engine: Engine, args: Optional[SimpleNamespace] = None, codec=None):
@@ -222,7 +223,7 @@ class System:
         """System.uni_generate (plangen_base.py:327-458) without the box-drawing tail (PIL visualisation is outside the path).
 
         task_type 'uni'        : pred_layout=False -> t2i on batch['uni_inputs_ids'/'uni_attention_mask'].
-        task_type 'uni_2stage' : stage 1 greedy layout tokens from batch['uni_stage1_inputs_ids'/'uni_stage1_attention_mask']
+        task_type 'uni_2stage' : stage 1 layout tokens (greedy; sampled when args.text_temperature > 0, see x2t) from batch['uni_stage1_inputs_ids'/'uni_stage1_attention_mask']
             (x2t, :371-377) -> decode_plan_text_batch (:382) -> wrap_uni_prompt(base_caption, layout) per sample
             (:385-388) -> pad_input_ids (:389) -> t2i.  ``layout_to_prompt(i, new_ids) -> list[int]`` replaces the tokenizer
             round trip when the caller wants to stay on ids.
@@ -300,9 +301,20 @@ class System:
 
     @torch.no_grad()
     def x2t(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
-            max_new_tokens: int = 512, min_new_tokens: int = 0) -> torch.Tensor:
-        """System.x2t (:513-523): greedy text / layout-token decode."""
+            max_new_tokens: int = 512, min_new_tokens: int = 0, temperature: Optional[float] = None,
+            top_k: Optional[int] = None, top_p: Optional[float] = None) -> torch.Tensor:
+        """System.x2t (:513-523): text / layout-token decode.  Greedy like the reference unless ``text_temperature`` > 0 (argument,
+        else self.args, else 0): then every row is sampled with ``text_top_k`` / ``text_top_p`` (HF order temperature -> top-k -> top-p)
+        from seed = args.seed, the seed t2i uses.  The draw is keyed on the row's index in the batch, so two rows that carry the same
+        prompt get different layouts: repeat a caption N times in one batch for N layouts of it."""
+        a = self.args
+        temperature = float(getattr(a, "text_temperature", 0.0)) if temperature is None else float(temperature)
+        top_k = int(getattr(a, "text_top_k", 0)) if top_k is None else int(top_k)
+        top_p = float(getattr(a, "text_top_p", 1.0)) if top_p is None else float(top_p)
+        kw = dict(do_sample=False)
+        if temperature > 0:
+            kw = dict(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, seed=int(getattr(a, "seed", 0)))
         return self.vl_gpt.language_model.generate(inputs_embeds=inputs_embeds, attention_mask=attention_mask,
                                                    pad_token_id=self.cfg.eos_id, bos_token_id=None,
                                                    eos_token_id=self.cfg.eos_id, max_new_tokens=max_new_tokens,
-                                                   do_sample=False, use_cache=True, min_new_tokens=min_new_tokens)
+                                                   use_cache=True, min_new_tokens=min_new_tokens, **kw)

@@ -12,6 +12,9 @@ cfg_weight = 5.0                       # base.py:162
 temperature = 1.0
 top_k = 0                              # top-k filtering of sampled image tokens (0: off); an extension beyond the reference
 top_p = 1.0                            # top-p (nucleus) filtering of sampled image tokens (1.0: off); an extension beyond the reference
+text_temperature = 0.0                 # layout / caption decode (x2t): 0 = greedy like the reference; > 0 samples (an extension beyond the reference)
+text_top_k = 0                         # top-k filtering of sampled text tokens (0: off)
+text_top_p = 1.0                       # top-p (nucleus) filtering of sampled text tokens (1.0: off)
 use_teacher_forcing = False            # base.py:36
 use_neg_box = False                    # base.py:121
 neg_prompt = ""                        # base.py:129: wrapped as wrap_uni_prompt(neg_prompt, '') for every uncond CFG row (:673)

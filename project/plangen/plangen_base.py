@@ -53,6 +53,8 @@ class System(_HotPath):
         cfg = PlanGenConfig.janus_pro_1b() if not getattr(args, "tiny", False) else PlanGenConfig.tiny()
         cfg.seed, cfg.cfg_weight, cfg.temperature = args.seed, args.cfg_weight, args.temperature
         cfg.top_k, cfg.top_p = int(getattr(args, "top_k", 0)), float(getattr(args, "top_p", 1.0))
+        cfg.text_temperature = float(getattr(args, "text_temperature", 0.0))
+        cfg.text_top_k, cfg.text_top_p = int(getattr(args, "text_top_k", 0)), float(getattr(args, "text_top_p", 1.0))
         bs = int(args.test_batch_size)
         device = int(os.environ.get("LOCAL_RANK", "0"))
         self.synthetic = td.get("data_name") == "synthetic" or bool(getattr(args, "synthetic", False))
@@ -72,6 +74,7 @@ class System(_HotPath):
                      with_vq_encoder=bool(args.use_teacher_forcing), with_vision=task == "mmu", device=device)
         super().__init__(cfg, eng, SimpleNamespace(seed=args.seed, parallel_size=args.parallel_size, cfg_weight=args.cfg_weight,
                                                    temperature=args.temperature, top_k=cfg.top_k, top_p=cfg.top_p,
+                                                   text_temperature=cfg.text_temperature, text_top_k=cfg.text_top_k, text_top_p=cfg.text_top_p,
                                                    use_teacher_forcing=args.use_teacher_forcing,
                                                    debug_max_seq_len=args.debug_max_seq_len, janus_hw=args.janus_hw,
                                                    neg_prompt=getattr(args, "neg_prompt", ""),
