@@ -33,7 +33,7 @@ extern "C" {
 typedef struct pg_engine* pg_handle;
 typedef void* pg_stream;              /* hipStream_t */
 
-typedef enum { PG_F32 = 0, PG_BF16 = 1, PG_I32 = 2, PG_I64 = 3 } pg_dtype;
+typedef enum { PG_F32 = 0, PG_BF16 = 1, PG_I32 = 2, PG_I64 = 3, PG_FP8_E4M3 = 4 /* pg_config.kv_dtype only */ } pg_dtype;
 
 typedef enum {
     PG_OK = 0,
@@ -67,7 +67,23 @@ typedef struct pg_config {
        width 1024, 24 layers, 16 heads (64 each), MLP 4096, patch 16, image 384 (siglip_vit.py:628-637) */
     int32_t with_vision, vit_width, vit_layers, vit_heads, vit_mlp, vit_patch, vit_img;
     int32_t max_vision_images;   /* images per pg_vision_encode call */
+    int32_t kv_dtype;        /* 0 = compute dtype (default); PG_FP8_E4M3 = 4: the opt-in FP8 KV cache (below).  Zero-initialised
+                                callers keep the compute-dtype cache and every result bit of it. */
 } pg_config;
+
+/* The FP8 KV cache (kv_dtype = PG_FP8_E4M3; compute_dtype must be PG_BF16, PG_F32 is PG_ERR_ARG at pg_create).
+ * Every 128-element K row (after RoPE) and V row of a (row, head, slot) -- the bf16-rounded values the bf16 cache would
+ * hold -- is stored as 128 one-byte codes and one fp32 scale, K and V separately:
+ *   codes  OCP e4m3fn (the gfx950-native format, not MI300X fnuz), code = e4m3_rne(x * 2^-e), round to nearest even;
+ *   scale  s = 2^e, e the smallest integer with amax(|x[0:128]|) * 2^-e <= 448, clamped to [-100, 100]; amax == 0: e = 0.
+ * Power-of-two scales make x * 2^-e and code * 2^e exact in fp32 (no division, nothing that can round differently on host
+ * and device), lose nothing against amax / 448 (e4m3's relative precision is the same in every binade) and keep the scaled
+ * value at or below 448, so saturation never happens.  Quantisation is idempotent.  Non-finite K / V are not covered.
+ * Prefill attention runs on the exact bf16 K / V (a one-layer bf16 scratch, quantised into the cache after each layer's
+ * attention); a decode step attends to its own new key / value unquantised and appends their codes at its end; cached keys
+ * are read as code * scale.  The K/V bytes a decode step streams drop to 264 / 512 of the bf16 cache's, the cache footprint
+ * with them.  Results differ from the bf16 cache's (this is why the mode is in the config, not an option).  Not supported:
+ * the "lanes" = 2 decode (PG_ERR_ARG at decode time). */
 
 /* -- lifetime ------------------------------------------------------------------------ */
 /* Replaces AutoModelForCausalLM.from_pretrained(...).cuda() (plangen_base.py:95). */
@@ -274,7 +290,8 @@ int pg_set_option(pg_handle h, const char* key, int64_t value);
 /* Bytes of device memory the handle owns (weights + KV + workspace). */
 int64_t pg_device_bytes(pg_handle h);
 /* Debug taps for parity tests: copy an internal buffer to dst_dev.
- * name: "kcache"/"vcache" (layer in ``index``), "x" (residual stream), "xn", "hfin", "gen_table", "pq_table", "qbuf", "obuf",
+ * name: "kcache"/"vcache" (layer in ``index``; compute dtype [max_rows, heads, slots, 128] -- with the FP8 KV cache the uint8 codes of
+ * the same shape, and "kscale"/"vscale" return the scales as fp32 [max_rows, heads, slots]), "x" (residual stream), "xn", "hfin", "gen_table", "pq_table", "qbuf", "obuf",
  * "vit_feat" (SigLIP features of the last pg_vision_encode, after the final LayerNorm, compute dtype [B, P, vit_width]). */
 int pg_debug_read(pg_handle h, const char* name, int index, void* dst_dev, int64_t max_bytes, pg_stream s);
 
@@ -306,6 +323,11 @@ int pg_op_sample_filter(pg_handle h, const float* logits_dev /*[B,V]*/, int B, i
 int pg_op_text_sample(pg_handle h, const float* logits_dev /*[B,V]*/, int B, int V, float temperature, int top_k,
                       float top_p, uint64_t seed, int row_offset, int step, uint8_t* keep_dev /*[B,V]*/,
                       int32_t* tok_dev /*[B]*/, pg_stream s);
+
+/* The quantiser of the FP8 KV cache (the device code the decode append and the prefill conversion run; format above):
+ * x_dev bf16 [n, 128] -> codes_dev uint8 [n, 128] (e4m3fn), scale_dev fp32 [n] (powers of two).  Works on any handle. */
+int pg_op_kv_quantize(pg_handle h, const void* x_dev /*bf16 [n,128]*/, uint8_t* codes_dev /*[n,128]*/, float* scale_dev /*[n]*/,
+                      int64_t n, pg_stream s);
 
 /* 3x3 convolution over NHWC activations (compute dtype), the VQ-16 ResnetBlock / Upsample /
  * Downsample conv (vq_model.py:337-352, :417-427, :440-447).  w_dev is [Cout][9][Cin]

@@ -9,7 +9,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libp
 # compute something else): loaded only by tools/, bench.py's instrumented pass and a few GPU tests -- never by the product path.
 DIAG_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libplangen_diag.so")
 
-PG_F32, PG_BF16, PG_I32, PG_I64 = 0, 1, 2, 3
+PG_F32, PG_BF16, PG_I32, PG_I64, PG_FP8_E4M3 = 0, 1, 2, 3, 4
 PG_MAX_VQ_LEVELS = 8
 STATUS = {0: "PG_OK", -1: "PG_ERR_ARG", -2: "PG_ERR_HIP", -3: "PG_ERR_STATE", -4: "PG_ERR_NAME", -5: "PG_ERR_CAPACITY"}
 
@@ -27,6 +27,7 @@ class pg_config(C.Structure):
         ("with_vq_encoder", C.c_int32),
         ("with_vision", C.c_int32), ("vit_width", C.c_int32), ("vit_layers", C.c_int32), ("vit_heads", C.c_int32),
         ("vit_mlp", C.c_int32), ("vit_patch", C.c_int32), ("vit_img", C.c_int32), ("max_vision_images", C.c_int32),
+        ("kv_dtype", C.c_int32),
     ]
 
 
@@ -67,6 +68,7 @@ SYMBOLS = [
     ("pg_op_uniform", C.c_int, [_P, _P, _P, C.c_int, _P]),
     ("pg_op_sample_filter", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, _P, _P]),
     ("pg_op_text_sample", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, _P, _P, _P]),
+    ("pg_op_kv_quantize", C.c_int, [_P, _P, _P, _P, C.c_int64, _P]),
     ("pg_op_conv3x3", C.c_int, [_P, _P, _P, _P, _P, _P] + [C.c_int] * 7 + [_P]),
     ("pg_op_groupnorm", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
 ]

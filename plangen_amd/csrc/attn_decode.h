@@ -3,6 +3,7 @@
 #pragma once
 #include <type_traits>
 #include "kernels.h"
+#include "kv8.h"
 
 // acc[v] += sum_s p[s*slab + offs[v]] with the loads of 4 slabs x NV values issued together
 // (hipcc does not unroll a runtime-S loop: a plain loop costs S dependent memory round trips).
@@ -303,5 +304,236 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fused_kernel(const int32_
         }
     }
     if constexpr (NIT > 1) __syncthreads();          // the append and the merge have read this item's LDS state
+    }
+}
+
+// ------------------------------------------------------------------------------- fused decode attention over the FP8 KV cache
+// pg_config.kv_dtype = PG_FP8_E4M3 (format: kv8.h).  The compute type stays bf16 (q, this step's key / value in LDS, obuf); only the cache
+// and its loads are 8-bit: one 16-byte load holds 16 codes, so 8 lanes cover a key, a wave load covers KPI = 8 keys and a score takes 3
+// shuffle steps.  The dot product runs on the unscaled codes and is multiplied by the key's K scale; every p is multiplied by the key's V
+// scale before the PV FMAs (both exact: the scales are powers of two).  The append quantises the new row from LDS as the block's last act.
+// Structure as attn_decode_fused_kernel's production form (ABL = 16): peeled first chunk issued before the prologue, non-temporal
+// software-pipelined private stream, cached loads of the shared uncond prefix, first-14-dwords kernarg order (the scale pointer is
+// dwords 15-16, still preloaded).  Occupancy is pinned per form (kernels.h: KV8_UN_*): 3 waves per SIMD for the 4-wave block, 2 for the 8-wave block.
+template <int UN, int NW>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 4 ? 3 : 2, NW == 4 ? 3 : 2))) void attn_decode_kv8_kernel(const int32_t* __restrict__ row_order, const int32_t* __restrict__ len_p,
+                                                            const int32_t* __restrict__ n_dec_p, uint8_t* __restrict__ kc, uint8_t* __restrict__ vc,
+                                                            int nh, int slots, int shared_len, int shared_row, float* __restrict__ kvs,
+                                                            const float* __restrict__ qkv, long slab, bf16* __restrict__ obuf,
+                                                            const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+                                                            const int32_t* __restrict__ pos_off_p, int S, int max_pos, float scale) {
+    constexpr int EPV = 16, LPK = 8, KPI = 8, NST = NW * KPI, KPW = KPI * UN;
+    __shared__ float s_o[NST][128];
+    __shared__ float s_m[NST], s_l[NST];
+    __shared__ __attribute__((aligned(16))) float s_q[128];
+    __shared__ __attribute__((aligned(16))) float s_k[128];
+    __shared__ __attribute__((aligned(16))) float s_v[128];
+    __shared__ float s_new;
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
+    const int head = blockIdx.x;
+    const int yi = (int)blockIdx.y;
+    const int row = row_order ? row_order[yi] : yi;
+    const int grp = l / LPK, lk = l % LPK;
+    const int slot = len_p[row] + *n_dec_p;
+    const int nprev = slot < slots ? slot : slots - 1;
+    const int HD = nh * 128;
+    const long rbase = ((long)row * nh + head) * slots;              // first slot of this (row, head)
+    const long cbase = rbase * 128;
+    const bool sh = shared_len > 0 && (row & 1);
+    const int kstart = sh ? (shared_len < nprev ? shared_len : nprev) : 0;
+    const long srow = ((long)shared_row * nh + head) * (long)slots;
+    const uint8_t* const kpriv = kc + cbase + lk * EPV; const uint8_t* const vpriv = vc + cbase + lk * EPV;
+    const uint8_t* const kshr = kc + srow * 128 + lk * EPV; const uint8_t* const vshr = vc + srow * 128 + lk * EPV;
+    const float* const spriv = kvs + rbase * 2; const float* const sshr = kvs + srow * 2;
+
+    u32x4 kv[UN], vv[UN];
+    float ks[UN], vs[UN];
+    auto clampk = [&](int base, int u, int k1) {
+        int key = base + u * KPI + grp;
+        key = key < k1 ? key : k1 - 1;
+        return key < 0 ? 0 : key;                                    // k1 == 0 (peeled issue of an empty segment): slot 0 is always mapped
+    };
+    // ONE key -> (wave, group, chunk) map for every row: chunk i of wave w holds keys [w * KPW + i * NW * KPW, +KPW) of 0 .. nprev - 1 whether
+    // or not the row's first kstart keys are the shared uncond prompt, so share_uncond 1 and 0 run the same arithmetic in the same order
+    // on the same values and agree bit for bit.  Only the loads differ: chunks that start below kstart are loaded cached, every lane
+    // taking its key from the shared row (key < kstart) or from the row's own stream; the chunks behind them are the non-temporal stream.
+    auto issueK = [&](int base, auto ntl) {
+        constexpr bool NTL = decltype(ntl)::value;
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const int key = clampk(base, u, nprev);
+            if constexpr (NTL) {
+                kv[u] = __builtin_nontemporal_load((const u32x4*)(kpriv + (long)key * 128));
+                ks[u] = __builtin_nontemporal_load(spriv + 2 * (long)key);
+            } else {
+                const bool shr = key < kstart;
+                kv[u] = *(const u32x4*)((shr ? kshr : kpriv) + (long)key * 128);
+                ks[u] = (shr ? sshr : spriv)[2 * (long)key];
+            }
+        }
+    };
+    auto issueV = [&](int base, auto ntl) {
+        constexpr bool NTL = decltype(ntl)::value;
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const int key = clampk(base, u, nprev);
+            if constexpr (NTL) {
+                vv[u] = __builtin_nontemporal_load((const u32x4*)(vpriv + (long)key * 128));
+                vs[u] = __builtin_nontemporal_load(spriv + 2 * (long)key + 1);
+            } else {
+                const bool shr = key < kstart;
+                vv[u] = *(const u32x4*)((shr ? vshr : vpriv) + (long)key * 128);
+                vs[u] = (shr ? sshr : spriv)[2 * (long)key + 1];
+            }
+        }
+    };
+    // first chunk (cached with the shared prefix in it for uncond rows, private stream otherwise): no dependence on q
+    const int base0 = w * KPW;
+    const bool have0 = base0 < nprev;
+    // wave 0: slab / cos / sin loads first and straight-line, then every wave's first K/V chunk (see attn_decode_fused_kernel)
+    const int o6[6] = {0, 64, HD, HD + 64, 2 * HD, 2 * HD + 64};
+    float t4[4][6], cs = 0.f, sn = 0.f;
+    int pos = pos_off_p[row] + slot;
+    if (pos >= max_pos) pos = max_pos - 1;
+    const float* const qrow = qkv + (long)row * 3 * HD + head * 128 + (tid & 63);
+    if (tid < 64) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float* qq = qrow + (long)(u < S ? u : S - 1) * slab;
+#pragma unroll
+            for (int v = 0; v < 6; ++v) t4[u][v] = qq[o6[v]];
+        }
+        cs = cos_t[(long)pos * 64 + tid]; sn = sin_t[(long)pos * 64 + tid];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (sh) { issueK(base0, std::false_type{}); issueV(base0, std::false_type{}); }
+    else { issueK(base0, std::true_type{}); issueV(base0, std::true_type{}); }
+    __builtin_amdgcn_sched_barrier(0);
+
+    if (tid < 64) {
+        const int j = tid;
+        float a6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int v = 0; v < 6; ++v) asm volatile("" : "+v"(t4[u][v])::"memory");
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (u < S) {
+#pragma unroll
+                for (int v = 0; v < 6; ++v) a6[v] += t4[u][v];
+            }
+        if (S > 4) sum_slabs<6>(qrow + 4 * slab, slab, S - 4, o6, a6);
+        const float q0 = a6[0], q1 = a6[1], k0 = a6[2], k1 = a6[3], v0 = a6[4], v1 = a6[5];
+        const float c = cs;
+        s_q[j] = ET<bf16>::round(q0 * c - q1 * sn) * scale;
+        s_q[j + 64] = ET<bf16>::round(q1 * c + q0 * sn) * scale;
+        s_k[j] = ET<bf16>::round(k0 * c - k1 * sn); s_k[j + 64] = ET<bf16>::round(k1 * c + k0 * sn);
+        s_v[j] = ET<bf16>::round(v0); s_v[j + 64] = ET<bf16>::round(v1);
+    }
+    __syncthreads();
+    if (w == 0) {
+        float d = s_q[l] * s_k[l] + s_q[l + 64] * s_k[l + 64];
+        d = wave_sum(d);
+        if (l == 0) s_new = d;
+    }
+    float q[EPV];
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) q[e] = s_q[lk * EPV + e];
+    float m_run = -INFINITY, l_run = 0.f, o[EPV];
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) o[e] = 0.f;
+    // scores / update: the one copy of the online-softmax arithmetic, used by the cached chunks and by the pipelined stream alike
+    // (contraction off: no product here may be fused into a neighbouring add in one caller and not in the other)
+    auto scores = [&](float (&sc)[UN], int base) {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            float kf[EPV]; kv8_unpack16(kv[u], kf);
+            float d = 0.f;
+#pragma unroll
+            for (int e = 0; e < EPV; ++e) d = fmaf(q[e], kf[e], d);
+#pragma unroll
+            for (int o_ = LPK / 2; o_ > 0; o_ >>= 1) d += __shfl_xor(d, o_, 64);
+            sc[u] = (base + u * KPI + grp < nprev) ? d * ks[u] : -INFINITY;
+        }
+    };
+    auto update = [&](const float (&sc)[UN]) {
+#pragma clang fp contract(off)
+        float mx = m_run;
+#pragma unroll
+        for (int u = 0; u < UN; ++u) mx = fmaxf(mx, sc[u]);
+        const float mxs = (mx > -INFINITY) ? mx : 0.f;               // a group whose keys are all masked so far: alpha = p = 0, the state stays empty
+        const float alpha = __expf(m_run - mxs);
+        l_run *= alpha;
+#pragma unroll
+        for (int e = 0; e < EPV; ++e) o[e] *= alpha;
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const float p = __expf(sc[u] - mxs);                     // -inf -> 0
+            l_run += p;
+            const float pv = p * vs[u];
+            float vf[EPV]; kv8_unpack16(vv[u], vf);
+#pragma unroll
+            for (int e = 0; e < EPV; ++e) o[e] = fmaf(pv, vf[e], o[e]);
+        }
+        m_run = mx;
+    };
+    auto consume = [&](int base) {
+        float sc[UN];
+        scores(sc, base);
+        update(sc);
+    };
+    // private stream: K(i+1) goes out before the wait for V(i); loads unconditional (clamped) so the counted waits stay exact
+    auto run_pipe = [&](int kfirst) {
+        if (kfirst >= nprev) return;
+        issueK(kfirst, std::true_type{});
+        for (int base = kfirst; base < nprev; base += NW * KPW) {
+            issueV(base, std::true_type{});
+            float sc[UN];
+            scores(sc, base);
+            __builtin_amdgcn_sched_barrier(0);
+            issueK(base + NW * KPW, std::true_type{});               // next chunk's K (clamped to the last key past the end)
+            __builtin_amdgcn_sched_barrier(0);
+            update(sc);
+        }
+    };
+    if (have0) consume(base0);
+    int base = base0 + NW * KPW;
+    for (; base < kstart; base += NW * KPW) {                        // uncond rows: the chunks that hold keys of the shared prefix (kstart <= nprev)
+        issueK(base, std::false_type{}); issueV(base, std::false_type{});
+        consume(base);
+    }
+    run_pipe(base);
+    const int stt = w * KPI + grp;
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) s_o[stt][lk * EPV + e] = o[e];
+    if (lk == 0) { s_m[stt] = m_run; s_l[stt] = l_run; }
+    __syncthreads();
+    if (tid < 128) {
+        float Mx = s_new;
+#pragma unroll
+        for (int i = 0; i < NST; ++i) Mx = fmaxf(Mx, s_m[i]);
+        const float fn = __expf(s_new - Mx);
+        float num = fn * s_v[tid], den = fn;
+#pragma unroll
+        for (int i = 0; i < NST; ++i) {
+            const float f = (s_m[i] > -INFINITY) ? __expf(s_m[i] - Mx) : 0.f;
+            num = fmaf(f, s_o[i][tid], num);
+            den = fmaf(f, s_l[i], den);
+        }
+        ET<bf16>::st(obuf + (long)row * HD + head * 128 + tid, num / den);
+    }
+    // K/V append, the block's last act: lanes 0-31 quantise the K row, lanes 32-63 the V row (4 elements each) from the bf16-rounded
+    // values in LDS -- amax over the 32 lanes, the exponent, 4 codes per lane in one dword store; lanes 0 and 32 store the two scales.
+    if (tid < 64 && slot < slots) {
+        const f32x4 x = *(const f32x4*)((l < 32 ? s_k : s_v) + (l & 31) * 4);
+        float am = fmaxf(fmaxf(fabsf(x.x), fabsf(x.y)), fmaxf(fabsf(x.z), fabsf(x.w)));
+#pragma unroll
+        for (int o_ = 16; o_ > 0; o_ >>= 1) am = fmaxf(am, __shfl_xor(am, o_, 64));
+        const int e = kv8_exponent(am);
+        uint8_t* dst = (l < 32 ? kc : vc) + cbase + (long)slot * 128 + (l & 31) * 4;
+        *(uint32_t*)dst = kv8_pack4(x.x, x.y, x.z, x.w, kv8_pow2(-e));
+        if ((l & 31) == 0) kvs[(rbase + slot) * 2 + (l >> 5)] = kv8_pow2(e);
     }
 }

@@ -76,6 +76,37 @@ int pg_diag_op_attn_decode(int is_bf16, int form, int path, const float* qkv, in
     return rc;
 }
 
+// Fused decode attention over the FP8 KV cache (launch_attn_decode_kv8, bf16 compute): arguments as pg_diag_op_attn_decode with the e4m3fn codes
+// kc8 / vc8 [rows][nh][slots][128] and the interleaved scales kvs fp32 [rows][nh][slots][2] = (K, V) in place of kc / vc.  form as above.
+int pg_diag_op_attn_decode_kv8(int form, const float* qkv, int S, long slab, void* obuf, void* kc8, void* vc8, float* kvs,
+                               const float* cos_t, const float* sin_t, const int32_t* len, const int32_t* pos_off, const int32_t* n_dec,
+                               const int32_t* row_order, int shared_len, int shared_row, int M, int nh, int slots, int max_pos, float scale,
+                               pg_stream stream) {
+    if (!qkv || !obuf || !kc8 || !vc8 || !kvs || !cos_t || !sin_t || !len || !pos_off || !n_dec) return PG_ERR_ARG;
+    if (form != 0 && form != 4 && form != 8) return PG_ERR_ARG;
+    if (M < 1 || M > kMaxGridYZ || nh < 1 || nh > kMaxGridYZ || S < 1 || slab < (long)M * 3 * nh * 128 || slots < 1 || max_pos < 1) return PG_ERR_ARG;
+    if (shared_len < 0 || shared_len > slots) return PG_ERR_ARG;
+    std::vector<int32_t> hl, hn, ho;
+    if (!to_host(hl, len, M) || !to_host(hn, n_dec, 1) || !to_host(ho, row_order, row_order ? M : 0)) return PG_ERR_HIP;
+    for (int r = 0; r < M; ++r) {
+        const long slot = (long)hl[r] + hn[0];
+        if (hl[r] < 0 || hn[0] < 0 || slot >= slots) return PG_ERR_ARG;          // the append slot must exist
+    }
+    if (row_order) {                                                            // a permutation of [0, M)
+        std::vector<char> seen(M, 0);
+        for (int i = 0; i < M; ++i) {
+            if (ho[i] < 0 || ho[i] >= M || seen[ho[i]]) return PG_ERR_ARG;
+            seen[ho[i]] = 1;
+        }
+    }
+    LocalTune lt;
+    lt.t.attn_waves = form;
+    const hipStream_t s = (hipStream_t)stream;
+    SeqState st{len, pos_off, n_dec, nullptr, nullptr, shared_len, shared_row, row_order};
+    launch_attn_decode_kv8(s, qkv, S, slab, (bf16*)obuf, (uint8_t*)kc8, (uint8_t*)vc8, kvs, cos_t, sin_t, st, M, nh, slots, max_pos, scale);
+    return launched(s);
+}
+
 // Prefill attention over the packed tokens: path 2 = attn_prefill_flash2_kernel, 1 = attn_prefill_flash_kernel (both bf16), 0 = attn_kernel mode 1.
 // qbuf / obuf: [Ntok][nh * 128] T; caches [R][nh][slots][128] T; row_off / len: [R] device (row_off -1: the row has no packed token);
 // tok_row / tok_j: [Ntok] device.  The packed tokens of row r must be row_off[r] .. row_off[r] + len[r] - 1 with tok_j = 0 .. len[r] - 1.

@@ -169,8 +169,16 @@ struct pg_engine {
     int img_tokens() const { return cfg.grid * cfg.grid; }
     int img_size() const { return cfg.grid << (cfg.vq_levels - 1); }
     size_t kv_layer_elems() const { return (size_t)cfg.max_rows * cfg.n_heads * slots * 128; }
-    void* kc(int layer) const { return (char*)kv + ((size_t)layer * 2 + 0) * kv_layer_elems() * esz + kv_row_off; }
-    void* vc(int layer) const { return (char*)kv + ((size_t)layer * 2 + 1) * kv_layer_elems() * esz + kv_row_off; }
+    // FP8 KV cache (cfg.kv_dtype = PG_FP8_E4M3, bf16 compute only; format: kv8.h): ``kv`` holds the e4m3fn codes of every layer, ``kv_scale`` the
+    // interleaved (K, V) fp32 scales, and kc(li) / vc(li) -- used by the PREFILL kernels only in this mode -- resolve to ONE layer-sized bf16
+    // scratch that every layer reuses: prefill runs unchanged on bf16 and kv_quantize_kernel converts the packed tokens after each layer's attention.
+    bool kv8 = false; float* kv_scale = nullptr; void* kv_scratch = nullptr;
+    size_t kv_layer_slots() const { return (size_t)cfg.max_rows * cfg.n_heads * slots; }
+    void* kc(int layer) const { return kv8 ? kv_scratch : (char*)kv + ((size_t)layer * 2 + 0) * kv_layer_elems() * esz + kv_row_off; }
+    void* vc(int layer) const { return kv8 ? (char*)kv_scratch + kv_layer_elems() * 2 : (char*)kv + ((size_t)layer * 2 + 1) * kv_layer_elems() * esz + kv_row_off; }
+    uint8_t* kc8(int layer) const { return (uint8_t*)kv + ((size_t)layer * 2 + 0) * kv_layer_elems(); }
+    uint8_t* vc8(int layer) const { return (uint8_t*)kv + ((size_t)layer * 2 + 1) * kv_layer_elems(); }
+    float* kvs(int layer) const { return kv_scale + (size_t)layer * 2 * kv_layer_slots(); }
     int shared_len = 0, shared_row = 1; bool share_uncond = true;
     int uncond_hint = -1;             // next pg_prefill only: 1 = caller guarantees every odd row carries row 1's ids, 0 = it does not, -1 = probe on the device (one 4-byte read + stream sync)
     // decode lanes: the batch's rows split into independent chains on separate streams

@@ -178,8 +178,19 @@ int pg_debug_read(pg_handle h, const char* name, int index, void* dst_dev, int64
     if (!h || !name || !dst_dev) return PG_ERR_ARG;
     const void* src = nullptr; int64_t n = 0;
     const std::string nm = name;
-    if (nm == "kcache") { src = h->kc(index); n = (int64_t)h->kv_layer_elems() * h->esz; }
-    else if (nm == "vcache") { src = h->vc(index); n = (int64_t)h->kv_layer_elems() * h->esz; }
+    if ((nm == "kcache" || nm == "vcache" || nm == "kscale" || nm == "vscale") && (index < 0 || index >= h->cfg.n_layers)) {
+        h->err = "pg_debug_read: layer index out of range"; return PG_ERR_ARG;
+    }
+    if (nm == "kscale" || nm == "vscale") {         // FP8 KV cache only: fp32 [max_rows, heads, slots]
+        if (!h->kv8) { h->err = "pg_debug_read: " + nm + " needs kv_dtype PG_FP8_E4M3"; return PG_ERR_NAME; }
+        int64_t cnt = (int64_t)h->kv_layer_slots();
+        if (cnt * 4 > max_bytes) cnt = max_bytes / 4;
+        (void)hipSetDevice(h->dev);
+        launch_kv8_scale_plane((hipStream_t)s, h->kvs(index), nm == "vscale", (float*)dst_dev, cnt);
+        return hipGetLastError() == hipSuccess ? PG_OK : PG_ERR_HIP;
+    }
+    if (nm == "kcache") { src = h->kv8 ? (void*)h->kc8(index) : h->kc(index); n = (int64_t)h->kv_layer_elems() * (h->kv8 ? 1 : h->esz); }
+    else if (nm == "vcache") { src = h->kv8 ? (void*)h->vc8(index) : h->vc(index); n = (int64_t)h->kv_layer_elems() * (h->kv8 ? 1 : h->esz); }
     else if (nm == "x") { src = h->x; n = (int64_t)h->max_tok * h->H() * 4; }
     else if (nm == "xn") { src = h->xn; n = (int64_t)h->max_tok * h->H() * h->esz; }
     else if (nm == "hfin") { src = h->hfin; n = (int64_t)h->cfg.max_rows * h->H() * h->esz; }
@@ -271,6 +282,12 @@ int pg_op_text_sample(pg_handle h, const float* logits_dev, int B, int V, float 
     f.rows = logits_dev; f.V = V; f.temperature = temperature; f.top_k = top_k; f.top_p = top_p; f.seed = seed; f.row_off = row_offset; f.step = step;
     f.keep = keep_dev; f.tok = tok_dev;
     launch_text_select((hipStream_t)s, f, B);
+    return hipGetLastError() == hipSuccess ? PG_OK : PG_ERR_HIP;
+}
+int pg_op_kv_quantize(pg_handle h, const void* x_dev, uint8_t* codes_dev, float* scale_dev, int64_t n, pg_stream s) {
+    if (!h || !x_dev || !codes_dev || !scale_dev || n < 0) return PG_ERR_ARG;
+    (void)hipSetDevice(h->dev);
+    launch_kv_quantize_rows((hipStream_t)s, (const bf16*)x_dev, codes_dev, scale_dev, (long)n);
     return hipGetLastError() == hipSuccess ? PG_OK : PG_ERR_HIP;
 }
 int pg_op_conv3x3(pg_handle h, const void* x_dev, const void* w_dev, const float* bias_dev, const void* residual_dev,

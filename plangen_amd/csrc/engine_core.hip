@@ -163,6 +163,10 @@ int pg_engine::build_vision() {
 int pg_engine::create() {
     bf = cfg.compute_dtype == PG_BF16;
     esz = bf ? 2 : 4;
+    if (cfg.kv_dtype != 0 && cfg.kv_dtype != PG_FP8_E4M3 && cfg.kv_dtype != cfg.compute_dtype)
+        FAIL(PG_ERR_ARG, "kv_dtype must be 0 (the compute dtype) or PG_FP8_E4M3 (got %d)", cfg.kv_dtype);
+    kv8 = cfg.kv_dtype == PG_FP8_E4M3;
+    if (kv8 && !bf) FAIL(PG_ERR_ARG, "the FP8 KV cache needs compute_dtype PG_BF16");
     if (cfg.head_dim != 128) FAIL(PG_ERR_ARG, "head_dim must be 128 (got %d)", cfg.head_dim);
     if (cfg.hidden % 128 || cfg.inter % 128 || cfg.gen_head_dim % 128)
         FAIL(PG_ERR_ARG, "hidden/inter/gen_head_dim must be multiples of 128");
@@ -248,7 +252,13 @@ int pg_engine::create() {
     slots = cfg.max_prompt + cfg.max_new;
     max_pos = 2 * cfg.max_prompt + cfg.max_new + 64;
     max_tok = (long)cfg.max_rows * cfg.max_prompt;
-    TRY(dalloc(&kv, (size_t)cfg.n_layers * 2 * kv_layer_elems() * esz, false));
+    if (kv8) {       // codes of every layer + (K, V) scales + the one-layer bf16 prefill scratch; no bf16 cache
+        TRY(dalloc(&kv, (size_t)cfg.n_layers * 2 * kv_layer_elems(), false));
+        TRY(dalloc(&kv_scale, (size_t)cfg.n_layers * 2 * kv_layer_slots() * 4, false));
+        TRY(dalloc(&kv_scratch, (size_t)2 * kv_layer_elems() * 2, false));
+    } else {
+        TRY(dalloc(&kv, (size_t)cfg.n_layers * 2 * kv_layer_elems() * esz, false));
+    }
     TRY(dalloc(&cos_t, (size_t)max_pos * 64 * 4));
     TRY(dalloc(&sin_t, (size_t)max_pos * 64 * 4));
     TRY(dalloc(&zeros, 1024));

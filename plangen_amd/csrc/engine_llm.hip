@@ -92,6 +92,10 @@ void pg_engine::run_layers(hipStream_t s, int M, int mode, T* final_out, int32_t
             // nothing: the GEMM + norm phase alone (outputs are garbage by construction)
         } else if (mode == 0 && fuse_rope) {
             tic(s);
+            if (kv8)
+                launch_attn_decode_kv8(s, part, S_last, slab_last, (bf16*)obuf, kc8(li), vc8(li), kvs(li), cos_t, sin_t, seq(), M, cfg.n_heads,
+                                       slots, max_pos, scale);
+            else
             launch_attn_decode_fused<T>(s, part, S_last, slab_last, (T*)obuf, (T*)kc(li), (T*)vc(li), cos_t, sin_t, seq(), M,
                                         cfg.n_heads, slots, max_pos, scale);
         } else {
@@ -109,11 +113,14 @@ void pg_engine::run_layers(hipStream_t s, int M, int mode, T* final_out, int32_t
             }
             if (!done)
                 launch_attn<T>(s, (const T*)qbuf, (T*)obuf, (const T*)kc(li), (const T*)vc(li), seq(), mode, M, cfg.n_heads, slots, scale);
+            // FP8 KV cache: this layer's K/V of the packed tokens, bf16 scratch -> codes + scales (prefill only: decode never takes this branch)
+            if (kv8 && mode == 1)
+                launch_kv_quantize(s, (const bf16*)kc(li), (const bf16*)vc(li), kc8(li), vc8(li), kvs(li), d_tok_row, d_tok_j, M, cfg.n_heads, slots);
         }
         if (tc_on && !(mode == 0 && skip_attn)) {
             double keys = shared_len;       // the shared uncond prompt is read from HBM once per launch
             for (int r = 0; r < R; ++r) keys += (double)(h_len[h_len_off + r] + n_dec_host + 1) - ((shared_len > 0 && (r & 1)) ? shared_len : 0);
-            toc(s, TC_ATTN, keys * cfg.n_heads * 128 * 2 * (double)esz);
+            toc(s, TC_ATTN, keys * cfg.n_heads * 2 * (kv8 ? 128.0 + 4.0 : 128.0 * (double)esz));      // FP8 cache: 128 codes + one fp32 scale per key, K and V
         }
         tic(s);
         if (!sk && prefill_res_epi) gemm_residual<T>(s, (const T*)obuf, (const T*)ly.wo, M, Hh, HDm);      // prefill: x += o . Wo^T in the GEMM's epilogue
@@ -274,6 +281,8 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
                             const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s) {
     if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(PG_ERR_ARG, "top_k=%d must be >= 0 and top_p=%g in (0, 1]", top_k, (double)top_p);
     if (!prefilled) FAIL(PG_ERR_STATE, "pg_decode_image_tokens before pg_prefill");
+    if (kv8 && !fuse_rope) FAIL(PG_ERR_ARG, "the FP8 KV cache needs the fused decode attention (fuse_rope)");
+    if (kv8 && lanes_opt == 2) FAIL(PG_ERR_ARG, "the FP8 KV cache does not support lanes = 2");
     if (R % 2) FAIL(PG_ERR_ARG, "CFG decode needs an even number of rows (got %d)", R);
     if (n_dec_host != 0) FAIL(PG_ERR_STATE, "decode loop needs a fresh prefill");
     if (T < 1 || T - 1 > cfg.max_new) FAIL(PG_ERR_CAPACITY, "T=%d exceeds max_new=%d", T, cfg.max_new);
@@ -401,6 +410,7 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
 
 int pg_engine::step(const void* emb, int emb_dtype, void* hidden_out, int hidden_dtype, hipStream_t s) {
     if (!prefilled) FAIL(PG_ERR_STATE, "pg_step before pg_prefill");
+    if (kv8 && !fuse_rope) FAIL(PG_ERR_ARG, "the FP8 KV cache needs the fused decode attention (fuse_rope)");
     if (n_dec_host + 1 > cfg.max_new) FAIL(PG_ERR_CAPACITY, "decode capacity max_new=%d exhausted", cfg.max_new);
     HIPCHK(hipSetDevice(dev));
     launch_rows_to_f32(s, emb, emb_dtype == PG_BF16, nullptr, x, R, H());
@@ -436,6 +446,7 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
                              float* logits_out, hipStream_t s) {
     if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(PG_ERR_ARG, "top_k=%d must be >= 0 and top_p=%g in (0, 1]", top_k, (double)top_p);
     if (!prefilled) FAIL(PG_ERR_STATE, "text decode before pg_prefill");
+    if (kv8 && !fuse_rope) FAIL(PG_ERR_ARG, "the FP8 KV cache needs the fused decode attention (fuse_rope)");
     if (!cfg.with_lm_head) FAIL(PG_ERR_STATE, "engine created without lm_head");
     if (n_dec_host != 0) FAIL(PG_ERR_STATE, "text decode needs a fresh prefill");
     if (max_new < 1 || max_new > cfg.max_new || max_new > 1000) FAIL(PG_ERR_CAPACITY, "max_new=%d exceeds capacity %d", max_new, cfg.max_new);

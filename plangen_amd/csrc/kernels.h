@@ -166,6 +166,20 @@ template <typename T>
 void launch_attn_decode_fused(hipStream_t s, const float* qkv, int S, long slab, T* obuf, T* kc, T* vc,
                               const float* cos_t, const float* sin_t, SeqState st, int M, int nh, int slots,
                               int max_pos, float scale);
+// FP8 KV cache (pg_config.kv_dtype = PG_FP8_E4M3; format: kv8.h).  kc / vc: e4m3fn codes [R][nh][slots][128]; kvs: fp32 power-of-two scales
+// [R][nh][slots][2] = (K, V).  The decode step (bf16 compute): block forms 4 waves x KV8_UN_BIG / 8 waves x KV8_UN_SMALL 16-byte loads in flight.
+// 16 elements per lane (q, o and the unpacked codes) cost registers the bf16 kernel does not need: 4 deep is what fits 3 waves per SIMD without
+// spilling (157 VGPRs; 5 deep spills 10, 6 deep 41), and no depth fits 4 waves; the 8-wave form runs 2 waves per SIMD (195 VGPRs at 5 deep).
+#define KV8_UN_BIG 4
+#define KV8_UN_SMALL 5
+void launch_attn_decode_kv8(hipStream_t s, const float* qkv, int S, long slab, bf16* obuf, uint8_t* kc, uint8_t* vc, float* kvs,
+                            const float* cos_t, const float* sin_t, SeqState st, int M, int nh, int slots, int max_pos, float scale);
+// prefill: the packed tokens' K / V rows of a one-layer bf16 scratch (cache layout) -> codes + scales of one layer
+void launch_kv_quantize(hipStream_t s, const bf16* ksrc, const bf16* vsrc, uint8_t* kc, uint8_t* vc, float* kvs, const int32_t* tok_row,
+                        const int32_t* tok_j, int ntok, int nh, int slots);
+void launch_kv8_scale_plane(hipStream_t s, const float* kvs, int which, float* dst, long n);      // dst[i] = kvs[2 i + which]
+// operator: x bf16 [n][128] -> codes [n][128], scale [n]
+void launch_kv_quantize_rows(hipStream_t s, const bf16* x, uint8_t* codes, float* scale, long n);
 // h = silu(g) * u from gate-up partial fp32 [S, M, 2I] whose columns are interleaved in
 // blocks of 8 (8 gate, 8 up, ...: every 16-column MFMA n-tile holds matching gate/up columns)
 template <typename T>

@@ -330,6 +330,59 @@ void launch_attn_decode_fused(hipStream_t s, const float* qkv, int S, long slab,
 template void launch_attn_decode_fused<float>(hipStream_t, const float*, int, long, float*, float*, float*, const float*, const float*, SeqState, int, int, int, int, float);
 template void launch_attn_decode_fused<bf16>(hipStream_t, const float*, int, long, bf16*, bf16*, bf16*, const float*, const float*, SeqState, int, int, int, int, float);
 
+// FP8 KV cache (kv8.h): the same two block forms as launch_attn_decode_fused, chosen the same way.  kvs: interleaved (K, V) scales.
+void launch_attn_decode_kv8(hipStream_t s, const float* qkv, int S, long slab, bf16* obuf, uint8_t* kc, uint8_t* vc, float* kvs,
+                            const float* cos_t, const float* sin_t, SeqState st, int M, int nh, int slots, int max_pos, float scale) {
+    if (M <= 0) return;
+#define ATT8_LAUNCH(U, W) hipLaunchKernelGGL((attn_decode_kv8_kernel<U, W>), dim3(nh, M), dim3(64 * W), 0, s, st.row_order, st.len, st.n_dec, kc, vc, nh, slots, st.shared_len, st.shared_row, kvs, qkv, slab, obuf, cos_t, sin_t, st.pos_off, S, max_pos, scale)
+    const bool small = (M * nh <= 512 && pg_tune->attn_waves != 4) || pg_tune->attn_waves == 8;
+    if (small) ATT8_LAUNCH(KV8_UN_SMALL, 8);
+    else ATT8_LAUNCH(KV8_UN_BIG, 4);
+#undef ATT8_LAUNCH
+}
+
+// n rows of 128 bf16 -> 128 codes + one scale each (one wave per row)
+__global__ __launch_bounds__(256) void kv_quantize_rows_kernel(const bf16* __restrict__ x, uint8_t* __restrict__ codes, float* __restrict__ scale, long n) {
+    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    kv8_quant_row(x + i * 128, codes + i * 128, scale + i, threadIdx.x & 63);
+}
+void launch_kv_quantize_rows(hipStream_t s, const bf16* x, uint8_t* codes, float* scale, long n) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(kv_quantize_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, x, codes, scale, n);
+}
+// prefill -> FP8 cache: one wave per (packed token, head, K | V) converts that row of the one-layer bf16 scratch [R][nh][slots][128] into
+// the layer's codes (same layout) and scale.  Indexed by the packed tokens, so aliased uncond rows and empty slots are never touched.
+__global__ __launch_bounds__(256) void kv_quantize_kernel(const bf16* __restrict__ ksrc, const bf16* __restrict__ vsrc, uint8_t* __restrict__ kc,
+                                                         uint8_t* __restrict__ vc, float* __restrict__ kvs, const int32_t* __restrict__ tok_row,
+                                                         const int32_t* __restrict__ tok_j, long nitems, int nh, int slots) {
+    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= nitems) return;
+    const int isv = (int)(i & 1);
+    const long th = i >> 1;
+    const int head = (int)(th % nh);
+    const long tok = th / nh;
+    const int j = tok_j[tok];
+    if (j >= slots) return;                                       // capacity guard, as rope_kv_kernel
+    const long idx = ((long)tok_row[tok] * nh + head) * slots + j;
+    kv8_quant_row((isv ? vsrc : ksrc) + idx * 128, (isv ? vc : kc) + idx * 128, kvs + idx * 2 + isv, threadIdx.x & 63);
+}
+// debug tap: dst[i] = kvs[2 i + which] (the K or the V scales out of the interleaved array)
+__global__ void kv8_scale_plane_kernel(const float* __restrict__ kvs, int which, float* __restrict__ dst, long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = kvs[2 * i + which];
+}
+void launch_kv8_scale_plane(hipStream_t s, const float* kvs, int which, float* dst, long n) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(kv8_scale_plane_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kvs, which, dst, n);
+}
+void launch_kv_quantize(hipStream_t s, const bf16* ksrc, const bf16* vsrc, uint8_t* kc, uint8_t* vc, float* kvs, const int32_t* tok_row,
+                        const int32_t* tok_j, int ntok, int nh, int slots) {
+    const long nitems = (long)ntok * nh * 2;
+    if (nitems <= 0) return;
+    hipLaunchKernelGGL(kv_quantize_kernel, dim3((unsigned)((nitems + 3) / 4)), dim3(256), 0, s, ksrc, vsrc, kc, vc, kvs, tok_row, tok_j, nitems, nh, slots);
+}
+
 template <typename T>
 void launch_attn(hipStream_t s, const T* qbuf, T* obuf, const T* kc, const T* vc, SeqState st, int mode,
                  int M, int nh, int slots, float scale) {

@@ -11,7 +11,7 @@ from typing import Dict, Iterable, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import PG_BF16, PG_F32
+from ._lib import PG_BF16, PG_F32, PG_FP8_E4M3
 from .config import PlanGenConfig
 
 
@@ -36,12 +36,16 @@ class Engine:
 
     dtype 'bf16' (production: bf16 weights / activations / KV, fp32 accumulate, fp32 residual
     stream) or 'f32' (parity mode, BASELINE config 1).
+
+    kv_dtype 'bf16' (default: the KV cache holds the compute dtype) or 'fp8': the opt-in FP8 (e4m3fn codes + one power-of-two scale
+    per 128-element row) KV cache of the decode loop -- about half the cache bytes; results differ from the default's.  Needs
+    dtype 'bf16'.  Format: include/plangen_hip.h.
     """
 
     def __init__(self, cfg: PlanGenConfig, dtype: str = "bf16", max_rows: int = 16, max_prompt: int = 256,
                  max_new: Optional[int] = None, max_images: Optional[int] = None, with_lm_head: bool = False,
                  with_vq_encoder: bool = False, with_vision: bool = False, max_vision_images: Optional[int] = None,
-                 device: int = 0, diag: bool = False):
+                 device: int = 0, diag: bool = False, kv_dtype: str = "bf16"):
         if not torch.cuda.is_available():
             raise PlanGenError("plangen_amd.Engine needs an MI355X (no CPU fallback)")
         # diag=True (tools/, bench.py's instrumented pass, hazard-screen tests): the handle lives in libplangen_diag.so -- the same object
@@ -51,6 +55,9 @@ class Engine:
         self.cfg = cfg
         self.dtype = dtype
         self.code = PG_BF16 if dtype == "bf16" else PG_F32
+        if kv_dtype not in ("bf16", "fp8"):
+            raise PlanGenError(f"kv_dtype must be 'bf16' or 'fp8' (got {kv_dtype!r})")
+        self.kv_dtype = kv_dtype
         self.tdtype = _torch_dt(self.code)
         self.device = torch.device("cuda", device)
         self.max_rows = max_rows
@@ -73,6 +80,7 @@ class Engine:
         for k in ("vit_width", "vit_layers", "vit_heads", "vit_mlp", "vit_patch", "vit_img"):
             setattr(c, k, int(getattr(cfg, k)))
         c.max_vision_images = max_vision_images if max_vision_images is not None else self.max_images
+        c.kv_dtype = PG_FP8_E4M3 if kv_dtype == "fp8" else 0
         self._c = c
         h = C.c_void_p()
         rc = self.lib.pg_create(C.byref(h), C.byref(c), device)
@@ -459,10 +467,22 @@ class Engine:
 
     # ------------------------------------------------------------------ test taps
     def debug_read(self, name: str, index: int, numel: int, dtype) -> torch.Tensor:
+        """Debug taps (include/plangen_hip.h).  With kv_dtype 'fp8', "kcache" / "vcache" are the uint8 codes (pass dtype=torch.uint8) and
+        "kscale" / "vscale" the fp32 scales [max_rows, heads, slots]."""
         out = torch.zeros((numel,), dtype=dtype, device=self.device)       # the library copies min(numel, buffer size): the rest stays zero
         self._check(self.lib.pg_debug_read(self.h, name.encode(), index, self._p(out), out.numel() * out.element_size(),
                                            self.stream), "pg_debug_read")
         return out
+
+    def op_kv_quantize(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """pg_op_kv_quantize: the FP8 KV cache's quantiser over bf16 rows ``x`` [n, 128] -> (codes uint8 [n, 128], scale fp32 [n])."""
+        x = self._dev(x, torch.bfloat16).reshape(-1, 128).contiguous()
+        n = x.shape[0]
+        codes = torch.zeros((n, 128), dtype=torch.uint8, device=self.device)
+        scale = torch.zeros((n,), dtype=torch.float32, device=self.device)
+        self._check(self.lib.pg_op_kv_quantize(self.h, self._p(x), self._p(codes), self._p(scale), n, self.stream), "pg_op_kv_quantize")
+        torch.cuda.synchronize()
+        return codes, scale
 
     def op_rmsnorm(self, x: torch.Tensor, w: torch.Tensor, eps: float, partial: Optional[torch.Tensor] = None):
         x = self._dev(x, torch.float32).clone()

@@ -55,6 +55,7 @@ class System(_HotPath):
         cfg.top_k, cfg.top_p = int(getattr(args, "top_k", 0)), float(getattr(args, "top_p", 1.0))
         cfg.text_temperature = float(getattr(args, "text_temperature", 0.0))
         cfg.text_top_k, cfg.text_top_p = int(getattr(args, "text_top_k", 0)), float(getattr(args, "text_top_p", 1.0))
+        cfg.kv_dtype = str(getattr(args, "kv_dtype", "bf16"))
         bs = int(args.test_batch_size)
         device = int(os.environ.get("LOCAL_RANK", "0"))
         self.synthetic = td.get("data_name") == "synthetic" or bool(getattr(args, "synthetic", False))
@@ -71,7 +72,8 @@ class System(_HotPath):
         eng = Engine(cfg, dtype=args.dtype, max_rows=2 * bs * int(args.parallel_size), max_prompt=int(getattr(args, "max_prompt", 768)),
                      max_new=max(cfg.img_tokens if needs_image else 1, text_new if task != "uni" and task != "t2i" else 1),
                      max_images=bs * int(args.parallel_size), with_lm_head=task in ("uni_2stage", "mmu", "plan"),
-                     with_vq_encoder=bool(args.use_teacher_forcing), with_vision=task == "mmu", device=device)
+                     with_vq_encoder=bool(args.use_teacher_forcing), with_vision=task == "mmu", device=device,
+                     kv_dtype=cfg.kv_dtype)
         super().__init__(cfg, eng, SimpleNamespace(seed=args.seed, parallel_size=args.parallel_size, cfg_weight=args.cfg_weight,
                                                    temperature=args.temperature, top_k=cfg.top_k, top_p=cfg.top_p,
                                                    text_temperature=cfg.text_temperature, text_top_k=cfg.text_top_k, text_top_p=cfg.text_top_p,
