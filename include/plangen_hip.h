@@ -115,6 +115,28 @@ int pg_finalize_weights(pg_handle h, int* missing, pg_stream s);
  * zero). */
 int pg_prefill(pg_handle h, const int32_t* ids_dev, const int32_t* pad_len_host, int R, int L,
                int position_mode, void* hidden_out_dev, int hidden_dtype, pg_stream s);
+/* pg_prefill of ``replicas`` copies of one CFG batch -- t2i's  tokens = torch.cat([tokens] * parallel_size)  (plangen_base.py:547)
+ * followed by the first language_model.model call -- with every distinct prompt prefilled ONCE.  ids_dev int32 [R0, L] and
+ * pad_len_host [R0] are the UN-replicated, left-padded, CFG-interleaved batch, exactly what pg_prefill takes.  Afterwards the handle
+ * is in the state of pg_prefill(R = R0 * replicas rows, position_mode 0, no hidden output) of the replicated ids: row t * R0 + r is
+ * replica t of row r (the reference's [all pairs] x p layout), and pg_decode_image_tokens* / pg_step run on R rows.  Only the rows
+ * that own a prompt are packed and run through the layer stack: owner(row) = the shared negative prompt's row for odd rows when the
+ * negative prompt is shared (decided as pg_prefill decides it on the R replicated rows: share_uncond, uncond_shared_hint, the device
+ * probe; R0 = 2 with replicas = 2 qualifies), else row % R0; a row with owner(row) != row takes its first hidden state from its owner.
+ *   alias = 1: a replica's prompt slots [0, len) are NEVER written; the decode attention reads them from the owner row (grouped
+ *              form of the fused decode-attention kernels) with cached loads, so that the replicas of a prompt are served from one
+ *              copy in L2 (measured at 128 rows, 4 replicas: L2 misses of the launch x0.37, decode loop -2.6 % at L = 256 and -9.5 % at
+ *              L = 512; DESIGN 4.5, profiles/replica_compare.md).  Slots from
+ *              len on (the replica's own decode keys) live in its own cache row.  pg_debug_read("kcache" / "vcache" / "kscale" /
+ *              "vscale") of a replica's prompt slots returns unspecified bytes.  lanes = 2 is rejected at decode time (PG_ERR_ARG).
+ *   alias = 0: the A/B fallback: the same single prefill, then one copy kernel writes the owner's prompt K/V (FP8 cache: codes and
+ *              both scales) into every replica's own row, and the decode loop runs exactly the kernels it runs after pg_prefill.
+ * Both modes give the same bits (equality-tested on the GPU).  The cache footprint is not reduced: all R rows stay allocated.
+ * replicas = 1 is exactly pg_prefill(h, ids_dev, pad_len_host, R0, L, 0, NULL, PG_F32, s).
+ * PG_ERR_ARG: replicas < 1, R0 < 1, alias not 0 / 1, or a handle without the fused decode attention; PG_ERR_CAPACITY:
+ * R0 * replicas > max_rows.  pg_generate_text_* after it (replicas > 1): PG_ERR_STATE (image-sampling positions). */
+int pg_prefill_replicated(pg_handle h, const int32_t* ids_dev, const int32_t* pad_len_host, int R0, int L,
+                          int replicas, int alias, pg_stream s);
 /* Same, from caller-provided embeddings [R, L, hidden] (dtype PG_F32/PG_BF16): the
  * ``emb is not None`` branch of t2i (plangen_base.py:543-545) and x2t (:513). */
 int pg_prefill_embeds(pg_handle h, const void* embeds_dev, int embeds_dtype,

@@ -43,6 +43,7 @@ class PlanGenConfig:
     text_top_k: int = 0
     text_top_p: float = 1.0
     seed: int = 0
+    share_replicas: int = 0        # parallel_size > 1: 1 = prefill every prompt once, its replicas read its K/V (Engine.prefill_replicated); 0 = replicate the ids (extension, off by default)
     kv_dtype: str = "bf16"         # KV cache of the decode loop: 'bf16' (the compute dtype) or 'fp8' (e4m3 codes + power-of-two scales; extension, off by default)
 
     @property

@@ -38,7 +38,12 @@ __device__ __forceinline__ void sum_slabs(const float* __restrict__ p, long slab
 // K/V chunk of every wave is issued BEFORE the prologue's dependent chain (slab loads -> RoPE -> LDS -> barrier) and consumed right
 // after the barrier, in the loop's own kv[] / vv[] registers (no double buffer, still 4 waves per SIMD); the append is ONE
 // 8-byte-per-lane store instruction per block, issued after the barrier.  Loop 1800 -> 1783 ms at bs=64.
-template <typename T, int UN, int NW, int ABL = 0>      // ABL (timing ablations, WRONG results): 1 no K/V append store, 2 no slab / cos / sin loads, 4 no merge epilogue
+// GRP (grouped form, pg_prefill_replicated with alias = 1): the kernel takes ONE more argument behind the others, group_rows = R0, and a row that
+// does not use the shared uncond prompt reads its prompt slots [0, len[row]) from its owner row (row % group_rows) -- same key -> (wave, group,
+// chunk) map, same arithmetic in the same order as a private row holding those values, only the load address (per lane: key < len ? owner : own)
+// and the cache policy (per chunk, wave-uniform: a chunk that starts below len is loaded cached so the replicas of an owner hit in L2, the rest
+// stays the non-temporal stream) differ.  The GRP = false instantiations have an empty argument pack: their signature and code are unchanged.
+template <typename T, int UN, int NW, int ABL = 0, bool GRP = false, typename... GA>      // ABL (timing ablations, WRONG results): 1 no K/V append store, 2 no slab / cos / sin loads, 4 no merge epilogue
 // Argument order (round 5): gfx950 preloads the first 14 kernarg dwords into SGPRs at wave launch (-amdgpu-kernarg-preload-count); the rest
 // arrive through an s_load that misses every cache (the host wrote the kernarg block for this launch).  The first 56 bytes are therefore
 // exactly what the FIRST K/V chunk's addresses need -- row order, lengths, step counter, cache bases, geometry, shared-prompt alias -- and
@@ -48,7 +53,8 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fused_kernel(const int32_
                                                               int nh, int slots, int shared_len, int shared_row,
                                                               const float* __restrict__ qkv, long slab, T* __restrict__ obuf,
                                                               const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                                                              const int32_t* __restrict__ pos_off_p, int S, int max_pos, float scale) {
+                                                              const int32_t* __restrict__ pos_off_p, int S, int max_pos, float scale, GA... group_args) {
+    static_assert(sizeof...(GA) == (GRP ? 1 : 0), "the grouped form takes exactly one trailing argument (group_rows)");
     constexpr int EPV = ET<T>::EPV, LPK = 128 / EPV, KPI = 64 / LPK, NST = NW * KPI;
     __shared__ float s_o[NST][128];
     __shared__ float s_m[NST], s_l[NST];
@@ -76,23 +82,33 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fused_kernel(const int32_
     const long sbase = ((long)shared_row * nh + head) * (long)slots * 128 + lk * EPV;
     const T* const kpriv = kc + cbase + lk * EPV; const T* const vpriv = vc + cbase + lk * EPV;
     const T* const kshr = kc + sbase; const T* const vshr = vc + sbase;
+    // grouped form: keys below plen live in the owner row, gdelta elements away (both wave-uniform; 0 / 0 for rows on the shared uncond prompt)
+    int plen = 0; long gdelta = 0;
+    if constexpr (GRP) {
+        const int group_rows = (group_args, ...);
+        if (!sh && group_rows > 0) { plen = len_p[row]; gdelta = (long)(row % group_rows - row) * nh * (long)slots * 128; }
+    }
+    auto koff = [&](int key) -> long { return (long)key * 128 + (key < plen ? gdelta : 0L); };   // element offset of a (clamped) key from the row's own base
 
     u32x4 kv[UN], vv[UN];
     auto issue = [&](const T* kb, const T* vb, int base, int k1, auto ntl) {
         constexpr bool NTL = decltype(ntl)::value;
+        const bool cached = GRP && NTL && base < plen;               // grouped form: a chunk of the aliased prefix is loaded cached (wave-uniform)
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
             int key = base + u * KPI + grp;
             key = key < k1 ? key : k1 - 1;
             key = key < 0 ? 0 : key;                                 // k1 == 0 (peeled issue of an empty segment): slot 0 is always mapped
-            kv[u] = NTL ? __builtin_nontemporal_load((const u32x4*)(kb + (long)key * 128)) : *(const u32x4*)(kb + (long)key * 128);
+            if constexpr (GRP) kv[u] = (NTL && !cached) ? __builtin_nontemporal_load((const u32x4*)(kb + koff(key))) : *(const u32x4*)(kb + koff(key));
+            else kv[u] = NTL ? __builtin_nontemporal_load((const u32x4*)(kb + (long)key * 128)) : *(const u32x4*)(kb + (long)key * 128);
         }
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
             int key = base + u * KPI + grp;
             key = key < k1 ? key : k1 - 1;
             key = key < 0 ? 0 : key;
-            vv[u] = NTL ? __builtin_nontemporal_load((const u32x4*)(vb + (long)key * 128)) : *(const u32x4*)(vb + (long)key * 128);
+            if constexpr (GRP) vv[u] = (NTL && !cached) ? __builtin_nontemporal_load((const u32x4*)(vb + koff(key))) : *(const u32x4*)(vb + koff(key));
+            else vv[u] = NTL ? __builtin_nontemporal_load((const u32x4*)(vb + (long)key * 128)) : *(const u32x4*)(vb + (long)key * 128);
         }
     };
     // first chunk of the first segment (shared prefix for uncond rows, private stream otherwise): no dependence on q
@@ -200,19 +216,23 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fused_kernel(const int32_
     // explicitly software-pipelined form of the loop (ABL bit 16, experiment): K(i+1) goes out BEFORE the wait for V(i), so one of the
     // two round trips of an iteration runs under the other's arithmetic; loads unconditional (clamped) so the counted waits stay exact
     auto issueK = [&](const T* kb, int base, int k1) {
+        const bool cached = GRP && base < plen;                      // wave-uniform; never true in the GRP = false forms
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
             int key = base + u * KPI + grp;
             key = key < k1 ? key : k1 - 1;
-            kv[u] = __builtin_nontemporal_load((const u32x4*)(kb + (long)key * 128));
+            if constexpr (GRP) kv[u] = cached ? *(const u32x4*)(kb + koff(key)) : __builtin_nontemporal_load((const u32x4*)(kb + koff(key)));
+            else kv[u] = __builtin_nontemporal_load((const u32x4*)(kb + (long)key * 128));
         }
     };
     auto issueV = [&](const T* vb, int base, int k1) {
+        const bool cached = GRP && base < plen;
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
             int key = base + u * KPI + grp;
             key = key < k1 ? key : k1 - 1;
-            vv[u] = __builtin_nontemporal_load((const u32x4*)(vb + (long)key * 128));
+            if constexpr (GRP) vv[u] = cached ? *(const u32x4*)(vb + koff(key)) : __builtin_nontemporal_load((const u32x4*)(vb + koff(key)));
+            else vv[u] = __builtin_nontemporal_load((const u32x4*)(vb + (long)key * 128));
         }
     };
     auto run_pipe = [&](const T* kb, const T* vb, int kfirst, int k1) {
@@ -258,6 +278,17 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fused_kernel(const int32_
         for (int base = kfirst; base < k1; base += NW * KPW) { issue(kb, vb, base, k1, ntl); consume(base, k1); }
     };
     if (have0) consume(base0, seg_k1);
+    // Grouped form: the same calls as the run() dispatch below, spelled out.  Through run() hipcc (ROCm 7.2) leaves run's operator() of the bf16
+    // 4-wave grouped kernel as a real CALL (s_swappc_b64 to a separate function, 448 bytes of scratch for the captured state, 113 VGPRs); spelled
+    // out, everything inlines: 128 VGPRs, no scratch.  Keep this in step with run(): cached segment = issue + consume, private stream = run_pipe.
+    if constexpr (GRP && (ABL & 16) != 0) {
+        if (sh) {
+            for (int base = base0 + NW * KPW; base < kstart; base += NW * KPW) { issue(kshr, vshr, base, kstart, std::false_type{}); consume(base, kstart); }
+            run_pipe(kpriv, vpriv, kstart + w * KPW, nprev);
+        } else {
+            run_pipe(kpriv, vpriv, base0 + NW * KPW, nprev);
+        }
+    } else
     if (sh) {
         run(kshr, vshr, base0 + NW * KPW, kstart, std::false_type{});
         run(kpriv, vpriv, kstart + w * KPW, nprev, std::true_type{});
@@ -315,13 +346,16 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_fused_kernel(const int32_
 // Structure as attn_decode_fused_kernel's production form (ABL = 16): peeled first chunk issued before the prologue, non-temporal
 // software-pipelined private stream, cached loads of the shared uncond prefix, first-14-dwords kernarg order (the scale pointer is
 // dwords 15-16, still preloaded).  Occupancy is pinned per form (kernels.h: KV8_UN_*): 3 waves per SIMD for the 4-wave block, 2 for the 8-wave block.
-template <int UN, int NW>
+// GRP: the grouped form (see attn_decode_fused_kernel): one trailing argument group_rows; rows off the shared uncond prompt take their prompt slots
+// [0, len[row]) -- codes and scales -- from the owner row (row % group_rows) through the same per-lane select the uncond alias uses.
+template <int UN, int NW, bool GRP = false, typename... GA>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 4 ? 3 : 2, NW == 4 ? 3 : 2))) void attn_decode_kv8_kernel(const int32_t* __restrict__ row_order, const int32_t* __restrict__ len_p,
                                                             const int32_t* __restrict__ n_dec_p, uint8_t* __restrict__ kc, uint8_t* __restrict__ vc,
                                                             int nh, int slots, int shared_len, int shared_row, float* __restrict__ kvs,
                                                             const float* __restrict__ qkv, long slab, bf16* __restrict__ obuf,
                                                             const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                                                            const int32_t* __restrict__ pos_off_p, int S, int max_pos, float scale) {
+                                                            const int32_t* __restrict__ pos_off_p, int S, int max_pos, float scale, GA... group_args) {
+    static_assert(sizeof...(GA) == (GRP ? 1 : 0), "the grouped form takes exactly one trailing argument (group_rows)");
     constexpr int EPV = 16, LPK = 8, KPI = 8, NST = NW * KPI, KPW = KPI * UN;
     __shared__ float s_o[NST][128];
     __shared__ float s_m[NST], s_l[NST];
@@ -340,8 +374,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 4
     const long rbase = ((long)row * nh + head) * slots;              // first slot of this (row, head)
     const long cbase = rbase * 128;
     const bool sh = shared_len > 0 && (row & 1);
-    const int kstart = sh ? (shared_len < nprev ? shared_len : nprev) : 0;
-    const long srow = ((long)shared_row * nh + head) * (long)slots;
+    int kstart = sh ? (shared_len < nprev ? shared_len : nprev) : 0;
+    long srow = ((long)shared_row * nh + head) * (long)slots;
+    if constexpr (GRP) {                                             // the owner row takes the shared row's place: keys below min(len, nprev)
+        const int group_rows = (group_args, ...);
+        if (!sh && group_rows > 0) {
+            const int pl = len_p[row];
+            kstart = pl < nprev ? pl : nprev;
+            srow = ((long)(row % group_rows) * nh + head) * (long)slots;
+        }
+    }
     const uint8_t* const kpriv = kc + cbase + lk * EPV; const uint8_t* const vpriv = vc + cbase + lk * EPV;
     const uint8_t* const kshr = kc + srow * 128 + lk * EPV; const uint8_t* const vshr = vc + srow * 128 + lk * EPV;
     const float* const spriv = kvs + rbase * 2; const float* const sshr = kvs + srow * 2;
@@ -406,7 +448,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 4
         cs = cos_t[(long)pos * 64 + tid]; sn = sin_t[(long)pos * 64 + tid];
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (sh) { issueK(base0, std::false_type{}); issueV(base0, std::false_type{}); }
+    if (sh || (GRP && base0 < kstart)) { issueK(base0, std::false_type{}); issueV(base0, std::false_type{}); }
     else { issueK(base0, std::true_type{}); issueV(base0, std::true_type{}); }
     __builtin_amdgcn_sched_barrier(0);
 

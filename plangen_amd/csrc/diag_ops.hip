@@ -107,6 +107,68 @@ int pg_diag_op_attn_decode_kv8(int form, const float* qkv, int S, long slab, voi
     return launched(s);
 }
 
+// Grouped form of the fused decode attention (SeqState::group_rows > 0: what pg_prefill_replicated with alias = 1 launches): arguments as
+// pg_diag_op_attn_decode (path 0 only) plus group_rows in [1, M]; rows off the shared uncond prompt read their prompt slots [0, len[row]) from
+// row (row % group_rows).  The caches are the caller's: the kernel can be tested without an engine state.
+}  // extern "C"
+namespace {
+// the argument screen of both grouped operators: PG_OK, or the status to return (nothing is launched on a refusal)
+int screen_grouped(int form, const int32_t* len, const int32_t* n_dec, const int32_t* row_order, int shared_len, int shared_row, int group_rows, int M, int nh,
+                   int S, long slab, int slots, int max_pos) {
+    if (group_rows < 1 || group_rows > M) return PG_ERR_ARG;
+    if (form != 0 && form != 4 && form != 8) return PG_ERR_ARG;
+    if (M < 1 || M > kMaxGridYZ || nh < 1 || nh > kMaxGridYZ || S < 1 || slab < (long)M * 3 * nh * 128 || slots < 1 || max_pos < 1) return PG_ERR_ARG;
+    if (shared_len < 0 || shared_len > slots || (shared_len > 0 && (shared_row < 0 || shared_row >= M))) return PG_ERR_ARG;
+    std::vector<int32_t> hl, hn, ho;
+    if (!to_host(hl, len, M) || !to_host(hn, n_dec, 1) || !to_host(ho, row_order, row_order ? M : 0)) return PG_ERR_HIP;
+    for (int r = 0; r < M; ++r) {
+        const long slot = (long)hl[r] + hn[0];
+        if (hl[r] < 0 || hn[0] < 0 || slot >= slots) return PG_ERR_ARG;          // the append slot must exist
+        if (hl[r] != hl[r % group_rows]) return PG_ERR_ARG;                       // a replica carries its owner's prompt length
+    }
+    if (row_order) {                                                            // a permutation of [0, M)
+        std::vector<char> seen(M, 0);
+        for (int i = 0; i < M; ++i) {
+            if (ho[i] < 0 || ho[i] >= M || seen[ho[i]]) return PG_ERR_ARG;
+            seen[ho[i]] = 1;
+        }
+    }
+    return PG_OK;
+}
+}  // namespace
+extern "C" {
+int pg_diag_op_attn_decode_grouped(int is_bf16, int form, const float* qkv, int S, long slab, void* obuf, void* kc, void* vc,
+                                   const float* cos_t, const float* sin_t, const int32_t* len, const int32_t* pos_off, const int32_t* n_dec,
+                                   const int32_t* row_order, int shared_len, int shared_row, int group_rows, int M, int nh, int slots, int max_pos,
+                                   float scale, pg_stream stream) {
+    if (!qkv || !obuf || !kc || !vc || !cos_t || !sin_t || !len || !pos_off || !n_dec) return PG_ERR_ARG;
+    const int rc = screen_grouped(form, len, n_dec, row_order, shared_len, shared_row, group_rows, M, nh, S, slab, slots, max_pos);
+    if (rc != PG_OK) return rc;
+    LocalTune lt;
+    lt.t.attn_waves = form;
+    const hipStream_t s = (hipStream_t)stream;
+    SeqState st{len, pos_off, n_dec, nullptr, nullptr, shared_len, shared_row, row_order, group_rows};
+    if (is_bf16) launch_attn_decode_fused<bf16>(s, qkv, S, slab, (bf16*)obuf, (bf16*)kc, (bf16*)vc, cos_t, sin_t, st, M, nh, slots, max_pos, scale);
+    else launch_attn_decode_fused<float>(s, qkv, S, slab, (float*)obuf, (float*)kc, (float*)vc, cos_t, sin_t, st, M, nh, slots, max_pos, scale);
+    return launched(s);
+}
+
+// FP8 twin: arguments as pg_diag_op_attn_decode_kv8 plus group_rows.
+int pg_diag_op_attn_decode_grouped_kv8(int form, const float* qkv, int S, long slab, void* obuf, void* kc8, void* vc8, float* kvs,
+                                       const float* cos_t, const float* sin_t, const int32_t* len, const int32_t* pos_off, const int32_t* n_dec,
+                                       const int32_t* row_order, int shared_len, int shared_row, int group_rows, int M, int nh, int slots,
+                                       int max_pos, float scale, pg_stream stream) {
+    if (!qkv || !obuf || !kc8 || !vc8 || !kvs || !cos_t || !sin_t || !len || !pos_off || !n_dec) return PG_ERR_ARG;
+    const int rc = screen_grouped(form, len, n_dec, row_order, shared_len, shared_row, group_rows, M, nh, S, slab, slots, max_pos);
+    if (rc != PG_OK) return rc;
+    LocalTune lt;
+    lt.t.attn_waves = form;
+    const hipStream_t s = (hipStream_t)stream;
+    SeqState st{len, pos_off, n_dec, nullptr, nullptr, shared_len, shared_row, row_order, group_rows};
+    launch_attn_decode_kv8(s, qkv, S, slab, (bf16*)obuf, (uint8_t*)kc8, (uint8_t*)vc8, kvs, cos_t, sin_t, st, M, nh, slots, max_pos, scale);
+    return launched(s);
+}
+
 // Prefill attention over the packed tokens: path 2 = attn_prefill_flash2_kernel, 1 = attn_prefill_flash_kernel (both bf16), 0 = attn_kernel mode 1.
 // qbuf / obuf: [Ntok][nh * 128] T; caches [R][nh][slots][128] T; row_off / len: [R] device (row_off -1: the row has no packed token);
 // tok_row / tok_j: [Ntok] device.  The packed tokens of row r must be row_off[r] .. row_off[r] + len[r] - 1 with tok_j = 0 .. len[r] - 1.

@@ -187,7 +187,10 @@ struct pg_engine {
     float* part2 = nullptr; hipStream_t istream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int32_t* d_ndec2 = nullptr;
     int32_t* d_row_order = nullptr; bool lpt_order = true; bool order_valid = false; int order_rows = 0;
-    SeqState seq() const { return SeqState{d_len, d_pos_off, d_ndec, d_tok_row, d_tok_j, shared_len, shared_row, (lpt_order && order_valid && kv_row_off == 0 && R == order_rows) ? d_row_order : nullptr}; }
+    // pg_prefill_replicated: the batch is `replicas_n` copies of R / replicas_n distinct rows (row t * R0 + r = replica t of row r); group_rows = R0 while
+    // the replicas' prompt slots alias their owner rows (alias = 1), 0 otherwise (plain prefill, alias = 0 after the copy, replicas = 1)
+    int group_rows = 0, replicas_n = 1;
+    SeqState seq() const { return SeqState{d_len, d_pos_off, d_ndec, d_tok_row, d_tok_j, shared_len, shared_row, (lpt_order && order_valid && kv_row_off == 0 && R == order_rows) ? d_row_order : nullptr, group_rows}; }
 
     int create();
     void add_slot(const std::string& name, void* dst, SlotKind k, long n, int a = 0, int b = 0, int c = 0);
@@ -203,8 +206,9 @@ struct pg_engine {
     template <typename T> int vision_encode(const void* img, int img_dtype, void* out, int out_dtype, int B, hipStream_t s);
     int load_tensor(const char* name, const void* src, int dtype, const int64_t* shape, int ndim);
     int finalize(int* missing, hipStream_t s);
-    int prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtype, const int32_t* pad_len, int R_, int L_,
-                int pmode, void* hidden_out, int hidden_dtype, hipStream_t s);
+    // pad_len: [R0] rows; replicas > 1 (pg_prefill_replicated): the batch is R0 * replicas virtual rows of which only the R0 distinct ones are packed
+    int prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtype, const int32_t* pad_len, int R0, int L_,
+                int pmode, void* hidden_out, int hidden_dtype, hipStream_t s, int replicas = 1, int alias = 0, bool replicated_api = false);
     template <typename T> void gemm_residual(hipStream_t s, const T* a, const T* W, int M, int N, int K);
     template <typename T> void gemm_llm(hipStream_t s, const T* a, const T* W, int M, int N, int K, bool allow_skinny, const void* Wt = nullptr);
     template <typename T> void run_layers(hipStream_t s, int M, int mode, T* final_out, int32_t* advance = nullptr);

@@ -48,6 +48,11 @@ int pg_prefill(pg_handle h, const int32_t* ids_dev, const int32_t* pad_len_host,
     if (!h || !ids_dev || !pad_len_host) return PG_ERR_ARG;
     return h->prefill(ids_dev, nullptr, 0, pad_len_host, R, L, position_mode, hidden_out_dev, hidden_dtype, (hipStream_t)s);
 }
+int pg_prefill_replicated(pg_handle h, const int32_t* ids_dev, const int32_t* pad_len_host, int R0, int L, int replicas, int alias,
+                          pg_stream s) { TuneGuard _tg(h);
+    if (!h || !ids_dev || !pad_len_host) return PG_ERR_ARG;
+    return h->prefill(ids_dev, nullptr, 0, pad_len_host, R0, L, 0, nullptr, PG_F32, (hipStream_t)s, replicas, alias, /*replicated entry*/ true);
+}
 int pg_prefill_embeds(pg_handle h, const void* embeds_dev, int embeds_dtype, const int32_t* pad_len_host, int R, int L,
                       int position_mode, void* hidden_out_dev, int hidden_dtype, pg_stream s) { TuneGuard _tg(h);
     if (!h || !embeds_dev || !pad_len_host) return PG_ERR_ARG;

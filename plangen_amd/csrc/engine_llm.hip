@@ -119,7 +119,11 @@ void pg_engine::run_layers(hipStream_t s, int M, int mode, T* final_out, int32_t
         }
         if (tc_on && !(mode == 0 && skip_attn)) {
             double keys = shared_len;       // the shared uncond prompt is read from HBM once per launch
-            for (int r = 0; r < R; ++r) keys += (double)(h_len[h_len_off + r] + n_dec_host + 1) - ((shared_len > 0 && (r & 1)) ? shared_len : 0);
+            for (int r = 0; r < R; ++r) {
+                keys += (double)(h_len[h_len_off + r] + n_dec_host + 1) - ((shared_len > 0 && (r & 1)) ? shared_len : 0);
+                // grouped form: a replica's prompt is its owner's -- counted once, with the owner
+                if (group_rows > 0 && r >= group_rows && !(shared_len > 0 && (r & 1))) keys -= (double)h_len[h_len_off + r];
+            }
             toc(s, TC_ATTN, keys * cfg.n_heads * 2 * (kv8 ? 128.0 + 4.0 : 128.0 * (double)esz));      // FP8 cache: 128 codes + one fp32 scale per key, K and V
         }
         tic(s);
@@ -170,17 +174,27 @@ void pg_engine::run_layers(hipStream_t s, int M, int mode, T* final_out, int32_t
     tc_on = false;
 }
 
-int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtype, const int32_t* pad_len, int R_, int L_,
-                       int pmode, void* hidden_out, int hidden_dtype, hipStream_t s) {
+int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtype, const int32_t* pad_len, int R0, int L_,
+                       int pmode, void* hidden_out, int hidden_dtype, hipStream_t s, int replicas, int alias, bool replicated_api) {
     // one-shot: the hint describes the ids of THIS call only -- consumed before anything can fail, so that a rejected call
     // cannot leave it armed for the next batch
     const int hint = uncond_hint; uncond_hint = -1;
     if (!finalized) FAIL(PG_ERR_STATE, "pg_finalize_weights not called");
+    // Replicated batch (pg_prefill_replicated): R_ = R0 * replicas VIRTUAL rows, row t * R0 + r = replica t of row r (the reference's [all pairs] x p,
+    // plangen_base.py:547).  Everything below is decided on the virtual rows exactly as a plain prefill of the replicated ids would decide it; only the
+    // rows that own their prompt (owner(row) == row) are packed and run through the layer stack.
+    if (replicated_api) {          // pg_prefill_replicated's own argument rules (behind the one-shot hint's consumption, like every other rejection)
+        if (replicas < 1 || R0 < 1 || (alias != 0 && alias != 1)) FAIL(PG_ERR_ARG, "pg_prefill_replicated: R0=%d and replicas=%d must be >= 1 and alias=%d 0 or 1", R0, replicas, alias);
+        if ((long)R0 * replicas > cfg.max_rows) FAIL(PG_ERR_CAPACITY, "%d rows x %d replicas > max_rows %d", R0, replicas, cfg.max_rows);
+    }
+    if (replicas > 1 && !fuse_rope) FAIL(PG_ERR_ARG, "pg_prefill_replicated needs the fused decode attention (fuse_rope)");
+    const int R_ = R0 * replicas;
+    auto pad_of = [&](int r) { return pad_len[r % R0]; };
     if (R_ <= 0 || R_ > cfg.max_rows) FAIL(PG_ERR_CAPACITY, "rows %d > max_rows %d", R_, cfg.max_rows);
     if (L_ + cfg.max_new + 1 > max_pos) FAIL(PG_ERR_CAPACITY, "padded length %d too long for the RoPE table (%d)", L_, max_pos);
     if (!ids_dev && !emb_dev) FAIL(PG_ERR_ARG, "ids or embeds required");
     HIPCHK(hipSetDevice(dev));
-    for (int r = 0; r < R_; ++r) {                 // validate every row BEFORE pad_len is used as an offset anywhere
+    for (int r = 0; r < R0; ++r) {                 // validate every row BEFORE pad_len is used as an offset anywhere
         const int pad = pad_len[r];
         if (pad < 0 || pad >= L_) FAIL(PG_ERR_ARG, "row %d: pad_len %d not in [0,%d)", r, pad, L_);
         if (L_ - pad > cfg.max_prompt) FAIL(PG_ERR_CAPACITY, "row %d: %d prompt tokens > max_prompt %d", r, L_ - pad, cfg.max_prompt);
@@ -192,13 +206,14 @@ int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtyp
     // host<->device round trip of pg_prefill: the packed-token count, hence every GEMM shape of
     // the prefill, depends on the answer).  Only on the fused path (no per-position hidden output).
     shared_len = 0;
-    if (share_uncond && fuse_rope && ids_dev && !hidden_out && pmode == 0 && R_ >= 4 && (R_ % 2) == 0) {
+    // (replicated: the odd virtual rows are the odd rows of every replica -- R0 must be even for that -- and the probe compares the distinct ones)
+    if (share_uncond && fuse_rope && ids_dev && !hidden_out && pmode == 0 && R_ >= 4 && (R0 % 2) == 0) {
         bool same = true;
-        for (int r = 3; r < R_ && same; r += 2) same = pad_len[r] == pad_len[1];
+        for (int r = 3; r < R_ && same; r += 2) same = pad_of(r) == pad_len[1];
         if (same && hint == 1) shared_len = L_ - pad_len[1];      // the caller compared the ids on the host (its collate built them): no probe, no sync
         else if (same && hint != 0) {
             HIPCHK(hipMemsetAsync(d_flag, 0, 4, s));
-            launch_rows_differ(s, ids_dev, L_, /*first*/ 3, /*stride*/ 2, /*ref row*/ 1, (R_ - 2) / 2, pad_len[1], d_flag);
+            launch_rows_differ(s, ids_dev, L_, /*first*/ 3, /*stride*/ 2, /*ref row*/ 1, (R0 - 2) / 2, pad_len[1], d_flag);
             HIPCHK(hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             if (*h_flag == 0) shared_len = L_ - pad_len[1];
@@ -215,20 +230,27 @@ int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtyp
     int32_t* s_len = hs; int32_t* s_off = hs + cfg.max_rows; int32_t* s_last = hs + 2 * cfg.max_rows;
     int32_t* s_roff = hs + 3 * cfg.max_rows; int32_t* s_ord = hs + 4 * cfg.max_rows; max_len_host = 0;
     int32_t* s_row = hs + 5 * cfg.max_rows; int32_t* s_j = s_row + max_tok; int32_t* s_src = s_j + max_tok;
+    // owner rule: the shared uncond prompt's row for odd rows when it is shared, else the row's first replica
+    auto owner = [&](int r) { return (shared_len > 0 && (r & 1)) ? 1 : r % R0; };
     for (int r = 0; r < R_; ++r) {
-        const int pad = pad_len[r];
+        const int pad = pad_of(r);
         const int len = L_ - pad;
         h_len[r] = len; s_len[r] = len; s_off[r] = pmode == 0 ? pad : 0;
-        if (shared_len > 0 && (r & 1) && r != 1) { s_last[r] = s_last[1]; s_roff[r] = -1; continue; }   // aliases row 1's prompt
+        if (owner(r) != r) { s_last[r] = s_last[owner(r)]; s_roff[r] = -1; continue; }   // aliases its owner's prompt (owner(r) < r)
         s_roff[r] = ntok; if (len > max_len_host) max_len_host = len;
         for (int j = 0; j < len; ++j) { s_row[ntok] = r; s_j[ntok] = j; s_src[ntok] = r * L_ + pad + j; ++ntok; }
         s_last[r] = ntok - 1;
     }
     R = R_; L = L_; Ntok = ntok; pos_mode = pmode; n_dec_host = 0;
+    replicas_n = replicas; group_rows = (replicas > 1 && alias == 1) ? R0 : 0;
     {   // longest-first row order for the decode attention launch (private keys per row)
         for (int r = 0; r < R_; ++r) s_ord[r] = r;
+        // grouped form: a replica walks its owner's prompt (from L2, one hopes) -- same key as its owner, and ties go by owner, so the replicas of one
+        // owner sit next to each other in the launch (same head -> same XCD, close in time)
+        const int G = group_rows;
         std::stable_sort(s_ord, s_ord + R_, [&](int a, int b) {
             const int ka = h_len[a] - ((shared_len > 0 && (a & 1)) ? shared_len : 0), kb = h_len[b] - ((shared_len > 0 && (b & 1)) ? shared_len : 0);
+            if (G > 0 && ka == kb) return a % G < b % G;
             return ka > kb; });
         order_valid = true; order_rows = R_;
     }
@@ -250,6 +272,11 @@ int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtyp
     if (bf) run_layers<bf16>(s, ntok, 1, (bf16*)xn); else run_layers<float>(s, ntok, 1, (float*)xn);
     // last real token of every row -> hfin (input of gen_head / lm_head for the first sample)
     launch_copy_rows(s, xn, d_last, hfin, nullptr, R, (long)H() * esz);
+    if (replicas > 1 && alias == 0) {     // the equality-tested fallback: every replica gets a private copy of its owner's prompt K/V, decode runs today's kernels
+        const size_t cb = kv8 ? 1 : esz;
+        launch_kv_replicate(s, kv, (long)(kv_layer_elems() * cb), 2 * cfg.n_layers, (long)slots * 128 * (long)cb, (int)(128 * cb), d_len, R0, R, cfg.n_heads, shared_len);
+        if (kv8) launch_kv_replicate(s, kv_scale, (long)(2 * kv_layer_slots() * 4), cfg.n_layers, (long)slots * 8, 8, d_len, R0, R, cfg.n_heads, shared_len);
+    }
     if (hidden_out) {
         const size_t ob = (size_t)R * L * H() * (hidden_dtype == PG_BF16 ? 2 : 4);
         HIPCHK(hipMemsetAsync(hidden_out, 0, ob, s));
@@ -283,6 +310,8 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     if (!prefilled) FAIL(PG_ERR_STATE, "pg_decode_image_tokens before pg_prefill");
     if (kv8 && !fuse_rope) FAIL(PG_ERR_ARG, "the FP8 KV cache needs the fused decode attention (fuse_rope)");
     if (kv8 && lanes_opt == 2) FAIL(PG_ERR_ARG, "the FP8 KV cache does not support lanes = 2");
+    if (group_rows > 0 && lanes_opt == 2) FAIL(PG_ERR_ARG, "replicas that alias their owner's prompt (pg_prefill_replicated, alias = 1) do not support lanes = 2");
+    if (group_rows > 0 && !fuse_rope) FAIL(PG_ERR_ARG, "replicas that alias their owner's prompt need the fused decode attention (fuse_rope)");
     if (R % 2) FAIL(PG_ERR_ARG, "CFG decode needs an even number of rows (got %d)", R);
     if (n_dec_host != 0) FAIL(PG_ERR_STATE, "decode loop needs a fresh prefill");
     if (T < 1 || T - 1 > cfg.max_new) FAIL(PG_ERR_CAPACITY, "T=%d exceeds max_new=%d", T, cfg.max_new);
@@ -379,7 +408,8 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
         // shapes and kernel selection only: seeds, temperatures, T and the caller's buffers reach the kernels through
         // device memory, so a bench / serving loop replays ONE instantiated graph across calls
         std::vector<int64_t> key = {Rtot, (int64_t)bf, (int64_t)logits_out, (int64_t)shared_len, (int64_t)fuse_rope, (int64_t)nl,
-                                    (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch, (int64_t)skip_attn, (int64_t)filtered};
+                                    (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch, (int64_t)skip_attn, (int64_t)filtered,
+                                    (int64_t)group_rows};        // replica geometry: never replay a graph across different aliasing
         if (!gexec || key != gkey) {
             if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
             hipGraph_t g = nullptr;
@@ -411,6 +441,7 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
 int pg_engine::step(const void* emb, int emb_dtype, void* hidden_out, int hidden_dtype, hipStream_t s) {
     if (!prefilled) FAIL(PG_ERR_STATE, "pg_step before pg_prefill");
     if (kv8 && !fuse_rope) FAIL(PG_ERR_ARG, "the FP8 KV cache needs the fused decode attention (fuse_rope)");
+    if (group_rows > 0 && !fuse_rope) FAIL(PG_ERR_ARG, "replicas that alias their owner's prompt need the fused decode attention (fuse_rope)");
     if (n_dec_host + 1 > cfg.max_new) FAIL(PG_ERR_CAPACITY, "decode capacity max_new=%d exhausted", cfg.max_new);
     HIPCHK(hipSetDevice(dev));
     launch_rows_to_f32(s, emb, emb_dtype == PG_BF16, nullptr, x, R, H());
@@ -446,6 +477,7 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
                              float* logits_out, hipStream_t s) {
     if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(PG_ERR_ARG, "top_k=%d must be >= 0 and top_p=%g in (0, 1]", top_k, (double)top_p);
     if (!prefilled) FAIL(PG_ERR_STATE, "text decode before pg_prefill");
+    if (replicas_n > 1) FAIL(PG_ERR_STATE, "text decode after pg_prefill_replicated (position_mode 0, image sampling only)");
     if (kv8 && !fuse_rope) FAIL(PG_ERR_ARG, "the FP8 KV cache needs the fused decode attention (fuse_rope)");
     if (!cfg.with_lm_head) FAIL(PG_ERR_STATE, "engine created without lm_head");
     if (n_dec_host != 0) FAIL(PG_ERR_STATE, "text decode needs a fresh prefill");

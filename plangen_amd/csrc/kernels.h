@@ -145,6 +145,7 @@ struct SeqState {              // device arrays describing the rows of the curre
     int shared_len;            // > 0: odd (uncond CFG) rows share one prompt; its K/V (slots [0, shared_len)) live in row shared_row only
     int shared_row;
     const int32_t* row_order;  // decode attention: blockIdx.y -> row, longest rows first (may be null)
+    int group_rows = 0;        // > 0 (pg_prefill_replicated, alias = 1): rows off the shared uncond prompt read their prompt slots [0, len) from row (row % group_rows)
 };
 // qkv partial fp32 [S, M, 3*nh*128] -> RoPE(q), RoPE(k); q -> qbuf T [M, nh*128];
 // k,v -> caches [R][nh][slots][128].  mode 0: decode (token m = row m, slot = len+n_dec);
@@ -174,6 +175,10 @@ void launch_attn_decode_fused(hipStream_t s, const float* qkv, int S, long slab,
 #define KV8_UN_SMALL 5
 void launch_attn_decode_kv8(hipStream_t s, const float* qkv, int S, long slab, bf16* obuf, uint8_t* kc, uint8_t* vc, float* kvs,
                             const float* cos_t, const float* sin_t, SeqState st, int M, int nh, int slots, int max_pos, float scale);
+// pg_prefill_replicated, alias = 0: for every plane p < planes (a layer's K or V block, or a layer's FP8 scale block; plane_bytes apart) and head, the
+// first len[row] slots (slot_bytes each; a (row, head) holds rowhead_bytes) of row (row % R0) -> row, rows R0 .. R-1; odd rows skipped when shared_len > 0
+void launch_kv_replicate(hipStream_t s, void* base, long plane_bytes, int planes, long rowhead_bytes, int slot_bytes, const int32_t* len,
+                         int R0, int R, int nh, int shared_len);
 // prefill: the packed tokens' K / V rows of a one-layer bf16 scratch (cache layout) -> codes + scales of one layer
 void launch_kv_quantize(hipStream_t s, const bf16* ksrc, const bf16* vsrc, uint8_t* kc, uint8_t* vc, float* kvs, const int32_t* tok_row,
                         const int32_t* tok_j, int ntok, int nh, int slots);

@@ -320,11 +320,19 @@ void launch_attn_decode_fused(hipStream_t s, const float* qkv, int S, long slab,
     // 2x the K/V bytes in flight per CU), 4-wave blocks 6 deep otherwise (7 deep spills in the pipelined form).  Only these two forms are
     // instantiated in libplangen_hip.so; the older non-pipelined kernel and the timing ablations live in libplangen_diag.so (diag_attn.hip),
     // which registers itself in PgTune::diag.
-    if (pg_tune->diag && pg_tune->diag->attn_decode && pg_tune->diag->attn_decode(s, std::is_same<T, bf16>::value, qkv, S, slab, obuf, kc, vc, cos_t, sin_t, st, M, nh, slots, max_pos, scale)) return;
+    // (the measurement forms know nothing of group_rows: a grouped launch never goes through them -- they would read the replicas' never-written prompt slots)
+    if (st.group_rows <= 0 && pg_tune->diag && pg_tune->diag->attn_decode && pg_tune->diag->attn_decode(s, std::is_same<T, bf16>::value, qkv, S, slab, obuf, kc, vc, cos_t, sin_t, st, M, nh, slots, max_pos, scale)) return;
 #define ATT_LAUNCH(U, W, A) hipLaunchKernelGGL((attn_decode_fused_kernel<T, U, W, A>), dim3(nh, M), dim3(64 * W), 0, s, st.row_order, st.len, st.n_dec, kc, vc, nh, slots, st.shared_len, st.shared_row, qkv, slab, obuf, cos_t, sin_t, st.pos_off, S, max_pos, scale)
+    // grouped form (SeqState::group_rows > 0, pg_prefill_replicated alias = 1): the same two block shapes, chosen the same way, with the one extra argument
+#define ATT_LAUNCH_GRP(U, W, A) hipLaunchKernelGGL((attn_decode_fused_kernel<T, U, W, A, true, int>), dim3(nh, M), dim3(64 * W), 0, s, st.row_order, st.len, st.n_dec, kc, vc, nh, slots, st.shared_len, st.shared_row, qkv, slab, obuf, cos_t, sin_t, st.pos_off, S, max_pos, scale, st.group_rows)
     const bool small = (M * nh <= 512 && pg_tune->attn_waves != 4) || pg_tune->attn_waves == 8;
-    if (small) ATT_LAUNCH(5, 8, 16);
+    if (st.group_rows > 0) {
+        if (small) ATT_LAUNCH_GRP(5, 8, 16);
+        else ATT_LAUNCH_GRP(6, 4, 16);
+    }
+    else if (small) ATT_LAUNCH(5, 8, 16);
     else ATT_LAUNCH(6, 4, 16);
+#undef ATT_LAUNCH_GRP
 #undef ATT_LAUNCH
 }
 template void launch_attn_decode_fused<float>(hipStream_t, const float*, int, long, float*, float*, float*, const float*, const float*, SeqState, int, int, int, int, float);
@@ -335,10 +343,42 @@ void launch_attn_decode_kv8(hipStream_t s, const float* qkv, int S, long slab, b
                             const float* cos_t, const float* sin_t, SeqState st, int M, int nh, int slots, int max_pos, float scale) {
     if (M <= 0) return;
 #define ATT8_LAUNCH(U, W) hipLaunchKernelGGL((attn_decode_kv8_kernel<U, W>), dim3(nh, M), dim3(64 * W), 0, s, st.row_order, st.len, st.n_dec, kc, vc, nh, slots, st.shared_len, st.shared_row, kvs, qkv, slab, obuf, cos_t, sin_t, st.pos_off, S, max_pos, scale)
+#define ATT8_LAUNCH_GRP(U, W) hipLaunchKernelGGL((attn_decode_kv8_kernel<U, W, true, int>), dim3(nh, M), dim3(64 * W), 0, s, st.row_order, st.len, st.n_dec, kc, vc, nh, slots, st.shared_len, st.shared_row, kvs, qkv, slab, obuf, cos_t, sin_t, st.pos_off, S, max_pos, scale, st.group_rows)
     const bool small = (M * nh <= 512 && pg_tune->attn_waves != 4) || pg_tune->attn_waves == 8;
-    if (small) ATT8_LAUNCH(KV8_UN_SMALL, 8);
+    if (st.group_rows > 0) {
+        if (small) ATT8_LAUNCH_GRP(KV8_UN_SMALL, 8);
+        else ATT8_LAUNCH_GRP(KV8_UN_BIG, 4);
+    }
+    else if (small) ATT8_LAUNCH(KV8_UN_SMALL, 8);
     else ATT8_LAUNCH(KV8_UN_BIG, 4);
+#undef ATT8_LAUNCH_GRP
 #undef ATT8_LAUNCH
+}
+
+// pg_prefill_replicated with alias = 0: the owner's prompt K/V -> every replica's own row.  One block per (replica row, head, plane); a plane is
+// one layer's K or V block (or one layer's scale block, FP8 cache), rows [R0, R) are the replicas of rows [0, R0): owner = row % R0.  Rows that
+// alias the shared uncond prompt (odd, shared_len > 0) hold no prompt of their own and are skipped.  VB = bytes per load / store (16; 8 for
+// the FP8 scales, whose [slot][2] fp32 pairs are 8 bytes per slot).
+template <int VB>
+__global__ __launch_bounds__(256) void kv_replicate_kernel(char* __restrict__ base, long plane_bytes, long rowhead_bytes, int slot_bytes,
+                                                           const int32_t* __restrict__ len_p, int R0, int nh, int shared_len) {
+    typedef typename std::conditional<VB == 16, u32x4, u32x2>::type V;
+    const int head = blockIdx.x, row = R0 + (int)blockIdx.y;
+    if (shared_len > 0 && (row & 1)) return;
+    const long n = (long)len_p[row] * slot_bytes / VB;
+    char* const plane = base + (long)blockIdx.z * plane_bytes;
+    const V* src = (const V*)(plane + ((long)(row % R0) * nh + head) * rowhead_bytes);
+    V* dst = (V*)(plane + ((long)row * nh + head) * rowhead_bytes);
+    for (long i = threadIdx.x; i < n; i += 256) dst[i] = src[i];
+}
+void launch_kv_replicate(hipStream_t s, void* base, long plane_bytes, int planes, long rowhead_bytes, int slot_bytes, const int32_t* len,
+                         int R0, int R, int nh, int shared_len) {
+    if (R <= R0 || planes <= 0) return;
+    const dim3 grid(nh, R - R0, planes);
+    if (slot_bytes % 16 == 0)
+        hipLaunchKernelGGL(kv_replicate_kernel<16>, grid, dim3(256), 0, s, (char*)base, plane_bytes, rowhead_bytes, slot_bytes, len, R0, nh, shared_len);
+    else
+        hipLaunchKernelGGL(kv_replicate_kernel<8>, grid, dim3(256), 0, s, (char*)base, plane_bytes, rowhead_bytes, slot_bytes, len, R0, nh, shared_len);
 }
 
 // n rows of 128 bf16 -> 128 codes + one scale each (one wave per row)

@@ -31,6 +31,13 @@ def _torch_dt(code: int):
     return torch.bfloat16 if code == PG_BF16 else torch.float32
 
 
+def replica_owner(row: int, R0: int, shared: bool) -> int:
+    """Owner rule of ``pg_prefill_replicated``: the row whose cache holds the prompt K/V that ``row`` of a batch of ``replicas`` copies of ``R0``
+    CFG-interleaved rows (row t * R0 + r = replica t of row r) reads.  ``shared``: the negative prompt is batch-constant and shared, so every odd
+    row reads row 1's; otherwise a row reads its first replica's.  A row aliases another row's prompt iff ``replica_owner(row) != row``."""
+    return 1 if (shared and row % 2 == 1) else row % R0
+
+
 class Engine:
     """MI355X engine for the layout->image path.
 
@@ -347,6 +354,24 @@ class Engine:
         self.R, self.L = R, L
         self._keep = [ids]
         return out
+
+    def prefill_replicated(self, ids: torch.Tensor, pad_len: Sequence[int], replicas: int, alias: bool = True,
+                           uncond_shared: Optional[bool] = None) -> None:
+        """``pg_prefill_replicated``: the state of ``prefill(torch.cat([ids] * replicas), list(pad_len) * replicas)`` with every distinct prompt
+        prefilled once.  ``ids`` [R0, L] / ``pad_len`` [R0] are the un-replicated CFG batch; afterwards the engine holds R0 * replicas rows (row
+        t * R0 + r = replica t of row r).  alias=True: the replicas' prompt slots alias their owner's in the decode attention; False: they are
+        copied (the A/B fallback, same bits).  uncond_shared as in :meth:`prefill` (evaluated on the replicated rows)."""
+        R0, L = ids.shape
+        if uncond_shared is None and not ids.is_cuda and replicas >= 1:
+            pl_all = [int(v) for v in pad_len] * int(replicas)
+            rep = torch.cat([ids] * int(replicas)) if replicas > 1 else ids
+            uncond_shared = self.uncond_rows_shared(rep, pl_all) if R0 % 2 == 0 else False
+        self.set_option("uncond_shared_hint", -1 if uncond_shared is None else int(bool(uncond_shared)))    # always sent: never a stale hint
+        ids = self._dev(ids, torch.int32)
+        pl = (C.c_int32 * R0)(*[int(v) for v in pad_len])
+        self._check(self.lib.pg_prefill_replicated(self.h, self._p(ids), pl, R0, L, int(replicas), int(alias), self.stream), "pg_prefill_replicated")
+        self.R, self.L = R0 * int(replicas), L
+        self._keep = [ids]
 
     def prefill_embeds(self, embeds: torch.Tensor, pad_len: Sequence[int], position_mode: int = 0,
                        return_hidden: bool = False, hidden_dtype=torch.float32) -> Optional[torch.Tensor]:

@@ -56,8 +56,20 @@ class _LlamaModel:
         self.position_mode = position_mode
 
     def __call__(self, inputs_embeds: torch.Tensor = None, attention_mask: Optional[torch.Tensor] = None,
-                 use_cache: bool = True, past_key_values: Optional[PastKeyValues] = None, **kw) -> ModelOutput:
+                 use_cache: bool = True, past_key_values: Optional[PastKeyValues] = None, input_ids: Optional[torch.Tensor] = None,
+                 replicas: int = 1, alias: bool = True, **kw) -> ModelOutput:
         eng = self.eng
+        if past_key_values is None and replicas > 1:
+            # parallel_size replicas of one CFG batch, every prompt prefilled once (pg_prefill_replicated): takes the UN-replicated ids [R0, L] (the
+            # engine embeds them) and the mask of those rows; the cache then holds replicas * R0 rows and later calls take [replicas * R0, 1, H].
+            # last_hidden_state is the LAST position only, [replicas * R0, 1, H] -- all the reference's loop reads (hidden_states[:, -1, :]).
+            if input_ids is None or attention_mask is None:
+                raise PlanGenError("language_model.model(replicas > 1) needs input_ids [R0, L] and their attention_mask")
+            R0, L = input_ids.shape
+            eng.prefill_replicated(input_ids, Engine.pad_len_from_mask(attention_mask[:R0], L), replicas, alias=alias)
+            hid = eng.debug_read("hfin", 0, R0 * replicas * eng.cfg.hidden, eng.tdtype).view(R0 * replicas, 1, eng.cfg.hidden)
+            self.epoch += 1
+            return ModelOutput(hid, PastKeyValues(eng, self.epoch, L))
         if inputs_embeds is None:
             raise PlanGenError("language_model.model: inputs_embeds is required (the reference never passes input_ids)")
         R, q, _ = inputs_embeds.shape

@@ -71,7 +71,8 @@ class System:
     """Inference half of PlanGen's System on one MI355X.
 
     args carries the cfg keys the path reads (cfg/base.py): seed, parallel_size, cfg_weight,
-    temperature, use_teacher_forcing, debug_max_seq_len, janus_hw; optionally top_k / top_p (image sampling filters, off when absent)
+    temperature, use_teacher_forcing, debug_max_seq_len, janus_hw; optionally share_replicas (parallel_size > 1: prefill every prompt once,
+    off when absent), top_k / top_p (image sampling filters, off when absent)
     and text_temperature / text_top_k / text_top_p (sampled layout / caption decode, greedy when absent).
     """
 
@@ -101,15 +102,21 @@ class System:
                      seed: int = 0, edit_region: Optional[torch.Tensor] = None,
                      gt_labels: Optional[torch.Tensor] = None, force_tokens: Optional[torch.Tensor] = None,
                      n_tokens: Optional[int] = None, return_logits: bool = False, top_k: Optional[int] = None,
-                     top_p: Optional[float] = None):
+                     top_p: Optional[float] = None, replicas: int = 1, alias: bool = True):
         """The 576-step CFG loop, fused on device (one pg_prefill + one pg_decode_image_tokens).
         tokens int32 [2B, L] CFG-interleaved ids, mask [2B, L+T].  temperature<=0 -> greedy.
-        top_k / top_p (default: self.args, else off) filter the sampled draws."""
+        top_k / top_p (default: self.args, else off) filter the sampled draws.
+        replicas > 1: ``tokens`` is the UN-replicated batch [2B0, L] and the loop runs on replicas * 2B0 rows (row t * 2B0 + r = replica t of
+        row r) with every prompt prefilled once (Engine.prefill_replicated); mask / edit_region / gt_labels / force_tokens are the replicated ones."""
         top_k = getattr(self.args, "top_k", 0) if top_k is None else top_k
         top_p = getattr(self.args, "top_p", 1.0) if top_p is None else top_p
         L = tokens.shape[1]
-        pad = Engine.pad_len_from_mask(mask, L)
-        self.engine.prefill(tokens, pad, position_mode=0)
+        if replicas > 1:
+            pad = Engine.pad_len_from_mask(mask[:tokens.shape[0]], L)
+            self.engine.prefill_replicated(tokens, pad, replicas, alias=alias)
+        else:
+            pad = Engine.pad_len_from_mask(mask, L)
+            self.engine.prefill(tokens, pad, position_mode=0)
         fm = ft = None
         if edit_region is not None:                        # use_teacher_forcing branch (:593-598)
             ft, fm = gt_labels, (edit_region != 0).to(torch.uint8)
@@ -161,8 +168,13 @@ class System:
             gi = gt_image.to(torch.bfloat16) if self.engine.dtype == "bf16" else gt_image
             gt_labels = self.vl_gpt.gen_vision_model.encode(gi)[-1][-1].reshape(bs, -1).to(torch.int32)
         force_region = edit_region
+        # share_replicas (cfg key, default 0): the ids stay un-replicated and every prompt is prefilled once; the mask, the forced labels and the
+        # all-ones regions of replicas 2..p are built as below either way
+        share = p > 1 and bool(int(getattr(a, "share_replicas", 0)))
+        num_gen = tokens.shape[0] // 2 * p
         if p > 1:
-            tokens = torch.cat([tokens] * p)
+            if not share:
+                tokens = torch.cat([tokens] * p)
             mask = torch.cat([mask] * p)
             if gt_labels is not None:
                 # The reference's forcing loop runs over ``len(batch['edit_region'])`` = the B un-replicated rows (:593-598), so only the
@@ -171,8 +183,8 @@ class System:
                 gt_labels = torch.cat([gt_labels] * p)
                 force_region = torch.cat([edit_region] + [torch.ones_like(edit_region)] * (p - 1))
         toks = self.sample_image(tokens, mask, cfg_weight, temperature, a.seed,
-                                 force_region if gt_labels is not None else None, gt_labels, top_k=top_k, top_p=top_p)
-        num_gen = tokens.shape[0] // 2
+                                 force_region if gt_labels is not None else None, gt_labels, top_k=top_k, top_p=top_p,
+                                 replicas=p if share else 1)
         dec = self.vl_gpt.gen_vision_model.decode_code(toks.to(dtype=torch.int),
                                                        shape=[num_gen, self.cfg.img_dim, self.cfg.grid, self.cfg.grid])
         self.last_generated_tokens = toks

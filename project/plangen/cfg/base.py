@@ -16,6 +16,7 @@ text_temperature = 0.0                 # layout / caption decode (x2t): 0 = gree
 text_top_k = 0                         # top-k filtering of sampled text tokens (0: off)
 text_top_p = 1.0                       # top-p (nucleus) filtering of sampled text tokens (1.0: off)
 kv_dtype = 'bf16'                      # KV cache: 'bf16' = the compute dtype; 'fp8' = e4m3 codes + power-of-two scales (about half the cache bytes; an extension beyond the reference)
+share_replicas = 0                     # parallel_size > 1: 1 = prefill every prompt once and let its replicas read its K/V in the decode loop (same tokens; an extension beyond the reference)
 use_teacher_forcing = False            # base.py:36
 use_neg_box = False                    # base.py:121
 neg_prompt = ""                        # base.py:129: wrapped as wrap_uni_prompt(neg_prompt, '') for every uncond CFG row (:673)
