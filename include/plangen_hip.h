@@ -246,6 +246,39 @@ int pg_vq_encode(pg_handle h, const void* img_dev, int img_dtype, int64_t* idx_o
  * embeddings (modeling_vlm.py:263-266) is data movement done by the caller. */
 int pg_vision_encode(pg_handle h, const void* img_dev, int img_dtype, void* out_dev, int out_dtype, int B, pg_stream s);
 
+/* -- image pre-processing for the understanding path -------------------------------------------- */
+/* VLChatProcessor.image_processor of the mmu path (VLMImageProcessor, three_party/Janus/janus/models/image_processing_vlm.py:41-52,127-192,
+ * reached through hack_image_proc, plangen_base.py:99-101,136-147) on the device.  The resample is Pillow's 8-bit fixed-point bicubic
+ * (torchvision's resize of a PIL image is PIL.Image.resize(BICUBIC); libImaging/Resample.c), so the result equals Pillow +
+ * transformers bit for bit.
+ *   input   B images, each uint8 RGB, HWC, in device memory, with its own pointer, height, width and row stride in BYTES (images_host
+ *           is a host array; sizes differ within a batch; rows need not be contiguous or aligned).
+ *   size    m = max(h, w); oh = max((int)(h / m * S), min_size), ow likewise, in double, in that order (:137-143): 64 x 97 at
+ *           S = 48 is 31 x 48.
+ *   coeffs  precompute_coeffs + normalize_coeffs_8bpc per image and axis: scale = in / out, fs = max(scale, 1), support = 2 fs; for
+ *           output xx: c = (xx + 0.5) scale, xmin = max((int)(c - support + 0.5), 0), n = min((int)(c + support + 0.5), in) - xmin,
+ *           w_x = bicubic((x + xmin - c + 0.5) * (1 / fs)) with a = -0.5, summed in ascending x, each divided by the sum,
+ *           k = (int)(w * 2^22 +- 0.5) (half away from zero).  Computed on the device in fp64 with contraction off by a kernel in
+ *           front of the resample: no host tables, and the doubles are the ones x86 computes.
+ *   passes  horizontal first, then vertical; a pass whose size does not change is skipped.  One value = clamp((2^21 + sum pixel * k)
+ *           >> 22, 0, 255) in int32 with an arithmetic shift; the image between the passes is uint8 (its rounding is part of the result).
+ *   pad     the resized image is pasted at ((S - ow) / 2, 0) or (0, (S - oh) / 2) into an S x S canvas of ``background`` (expand2square).
+ *   values  every uint8 v of channel c becomes lut_host[c * 256 + v] (fp32; the caller fills it with transformers' rescale + normalize
+ *           arithmetic, so any mean / std are exact by construction); PG_BF16 output is the round-to-nearest-even of that fp32 value
+ *           (the .to(torch.bfloat16) of modeling_vlm.py:249).
+ *   output  out_dev [B, 3, S, S] NCHW, PG_F32 or PG_BF16; every element is written, the padding included.
+ * Asynchronous on ``s``, no synchronisation: descriptors and table travel through pinned staging like pg_prefill's pad_len_host; the
+ * library-owned workspace (coefficient tables + uint8 intermediates) is allocated on first use, grows when a batch needs more (growing
+ * frees the old one, which waits for work that still uses it) and is counted by pg_device_bytes.  Calls on one handle must be ordered on
+ * one stream.  Works on any handle (no weights needed).
+ * PG_ERR_ARG, nothing launched: a null pointer (handle, images_host, an image's pix_dev, background, lut_host, out_dev), B < 1, an image
+ * side < 1, min_size < 1, S < min_size, S > 16384, a down-scaling ratio in / out above 64 on an axis (caps the taps per output at 257
+ * and the workspace with it), out_dtype other than PG_F32 / PG_BF16. */
+typedef struct pg_image_u8 { const uint8_t* pix_dev; int32_t height, width; int64_t row_stride; } pg_image_u8;
+int pg_preprocess_images(pg_handle h, const pg_image_u8* images_host, int B, int out_size, int min_size,
+                         const uint8_t background[3], const float* lut_host /* [3][256] */,
+                         void* out_dev, int out_dtype, pg_stream s);
+
 /* -- introspection (tests / bench) -------------------------------------------------------- */
 /* Last-launch timing of the decode loop measured with HIP events on ``s`` inside the
  * library: fills ms for the whole pg_decode_image_tokens call and, when per-kernel

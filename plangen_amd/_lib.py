@@ -31,6 +31,10 @@ class pg_config(C.Structure):
     ]
 
 
+class pg_image_u8(C.Structure):
+    _fields_ = [("pix_dev", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32), ("row_stride", C.c_int64)]
+
+
 class pg_timing(C.Structure):
     _fields_ = [("decode_ms", C.c_float), ("attn_ms_sum", C.c_float), ("attn_launches", C.c_int32),
                 ("attn_bytes_sum", C.c_double), ("prefill_ms", C.c_float), ("vq_ms", C.c_float)]
@@ -58,6 +62,7 @@ SYMBOLS = [
     ("pg_vq_decode", C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     ("pg_vq_encode", C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P]),
     ("pg_vision_encode", C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
+    ("pg_preprocess_images", C.c_int, [_P, C.POINTER(pg_image_u8), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_float), _P, C.c_int, _P]),
     ("pg_get_timing", C.c_int, [_P, C.POINTER(pg_timing)]),
     ("pg_get_class_timing", C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     ("pg_set_option", C.c_int, [_P, C.c_char_p, C.c_int64]),

@@ -125,6 +125,11 @@ struct pg_engine {
     const void* gn_part_of = nullptr; int gn_part_n = 0, gn_part_b = 0;   // gn_ws holds conv-epilogue partials of this tensor
     float* enc_z = nullptr;
     void* stage_dev = nullptr; long stage_bytes = 0;
+    // pg_preprocess_images (imgproc.hip): device workspace (descriptors | coefficient tables | uint8 intermediates), allocated on first use and grown
+    // when a batch needs more, and its own double-buffered pinned staging for the descriptors
+    void* ip_dev = nullptr; long ip_dev_bytes = 0;
+    uint8_t* ip_host[2] = {nullptr, nullptr}; long ip_host_bytes[2] = {0, 0};
+    hipEvent_t ip_ev[2] = {nullptr, nullptr}; bool ip_used[2] = {false, false}; int ip_sel = 0;
     // ---- streams / graph / timing
     hipStream_t istream = nullptr; hipEvent_t ev_in = nullptr, ev_out = nullptr;
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_p0 = nullptr, ev_p1 = nullptr, ev_v0 = nullptr, ev_v1 = nullptr;
@@ -231,6 +236,8 @@ struct pg_engine {
     template <typename T> void attnblock(hipStream_t s, const AttnW& a, int B, int HW);
     template <typename TI> void gn_coefs(hipStream_t s, const NormW& n, const TI* in, int B, int HW);      // statistics (conv epilogue partials or the stats kernel) -> gn_coef
     template <typename T, typename TI = float> void gn(hipStream_t s, const NormW& n, const TI* in, T* out, int B, int HW, int swish);
+    int preprocess_images(const pg_image_u8* images, int B, int S, int min_size, const uint8_t* background, const float* lut_host, void* out_dev,
+                          int out_dtype, hipStream_t s);
     int fetch_timing();
     void destroy();
 };

@@ -128,6 +128,11 @@ int pg_vision_encode(pg_handle h, const void* img_dev, int img_dtype, void* out_
     return h->bf ? h->vision_encode<bf16>(img_dev, img_dtype, out_dev, out_dtype, B, (hipStream_t)s)
                  : h->vision_encode<float>(img_dev, img_dtype, out_dev, out_dtype, B, (hipStream_t)s);
 }
+int pg_preprocess_images(pg_handle h, const pg_image_u8* images_host, int B, int out_size, int min_size, const uint8_t background[3],
+                         const float* lut_host, void* out_dev, int out_dtype, pg_stream s) {
+    if (!h) return PG_ERR_ARG;
+    return h->preprocess_images(images_host, B, out_size, min_size, background, lut_host, out_dev, out_dtype, (hipStream_t)s);
+}
 int pg_get_timing(pg_handle h, pg_timing* out) {
     if (!h || !out) return PG_ERR_ARG;
     const int rc = h->fetch_timing();

@@ -372,6 +372,8 @@ void pg_engine::destroy() {
     drop_graphs();
     for (void* p : allocs) (void)hipFree(p);
     if (stage_dev) (void)hipFree(stage_dev);
+    if (ip_dev) (void)hipFree(ip_dev);
+    for (int i = 0; i < 2; ++i) { if (ip_host[i]) (void)hipHostFree(ip_host[i]); if (ip_ev[i]) (void)hipEventDestroy(ip_ev[i]); }
     for (int i = 0; i < 2; ++i) { if (h_stage2[i]) (void)hipHostFree(h_stage2[i]); if (ev_stage[i]) (void)hipEventDestroy(ev_stage[i]); }
     if (h_flag) (void)hipHostFree(h_flag);
     for (hipEvent_t e : tc_ev) (void)hipEventDestroy(e);

@@ -490,6 +490,41 @@ class Engine:
         self._keep = [images]
         return out
 
+    def preprocess_images(self, images, out_size: int, min_size: int = 14, mean=(0.48145466, 0.4578275, 0.40821073),
+                          std=(0.26862954, 0.26130258, 0.27577711), rescale_factor: float = 1.0 / 255.0, dtype=torch.float32,
+                          background=None, do_normalize: bool = True, lut=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``pg_preprocess_images``: the reference's VLMImageProcessor (image_processing_vlm.py:127-192) on the device.  ``images``: a list of
+        uint8 [H, W, 3] tensors or arrays of any sizes (host ones are copied to the device; device tensors with non-contiguous ROWS are
+        passed by their row stride, not copied) -> [B, 3, out_size, out_size] ``dtype`` (float32 / bfloat16).  ``background`` defaults to
+        the reference's ``int(mean * 255)``; ``lut`` (float32 [3, 256]) replaces the rescale / normalise table and ``out`` the freshly allocated result (tests)."""
+        from .imageproc import background_of, make_lut
+        devs = []
+        for im in images:
+            t = im if isinstance(im, torch.Tensor) else torch.as_tensor(im)
+            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+                raise TypeError(f"preprocess_images needs uint8 [H, W, 3] images (got {t.dtype} {tuple(t.shape)})")
+            t = t.to(self.device)
+            if t.numel() and (t.stride(2) != 1 or t.stride(1) != 3 or t.stride(0) < 0):      # pixels must be packed RGB; only the rows may be strided
+                t = t.contiguous()
+            devs.append(t)
+        B = len(devs)
+        descs = (_lib.pg_image_u8 * max(1, B))()
+        for d, t in zip(descs, devs):
+            d.pix_dev, d.height, d.width, d.row_stride = t.data_ptr(), t.shape[0], t.shape[1], t.stride(0) if t.shape[0] > 1 else t.shape[1] * 3
+        table = make_lut(mean, std, rescale_factor, do_normalize) if lut is None else lut
+        table = torch.as_tensor(table, dtype=torch.float32).cpu().contiguous()
+        if tuple(table.shape) != (3, 256):
+            raise TypeError("lut must be float32 [3, 256]")
+        bg = (C.c_uint8 * 3)(*[int(v) for v in (background_of(mean) if background is None else background)])
+        if out is None:
+            out = torch.empty((B, 3, out_size, out_size), dtype=dtype, device=self.device)
+        elif tuple(out.shape) != (B, 3, out_size, out_size) or not out.is_contiguous() or out.device != self.device:
+            raise TypeError(f"out must be a contiguous [{B}, 3, {out_size}, {out_size}] tensor on {self.device}")
+        self._check(self.lib.pg_preprocess_images(self.h, descs, B, int(out_size), int(min_size), bg, C.cast(table.data_ptr(), C.POINTER(C.c_float)),
+                                                  self._p(out), _dt(out), self.stream), "pg_preprocess_images")
+        self._keep = devs
+        return out
+
     # ------------------------------------------------------------------ test taps
     def debug_read(self, name: str, index: int, numel: int, dtype) -> torch.Tensor:
         """Debug taps (include/plangen_hip.h).  With kv_dtype 'fp8', "kcache" / "vcache" are the uint8 codes (pass dtype=torch.uint8) and

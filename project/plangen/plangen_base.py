@@ -145,7 +145,10 @@ class System(_HotPath):
         With a tokenizer the text goes through the reference's conversation -- ``<|User|>: <image_placeholder>\\n{question}`` /
         empty assistant turn under VLChatProcessor's system prompt -- and the placeholder id is expanded to
         ``<begin_of_image>`` + vit_tokens slots + ``<end_of_image>`` (add_image_token, processing_vlm.py:243-248).
-        Rows with ``question_ids`` (pre-tokenised) keep the bare form [first id] + slots + [rest]."""
+        Rows with ``question_ids`` (pre-tokenised) keep the bare form [first id] + slots + [rest].
+        The image of a row: ``image_pt`` (a saved [3, S, S] tensor, already normalised) is taken as it is; ``image_path`` (a ``.npy`` holding
+        uint8 [H, W, 3], or any file Pillow opens, converted to RGB) goes through the image processor on the device like the reference's PIL
+        images (plangen_base.py:136-147); a row with neither gets seeded noise."""
         from plangen_amd.textproc import wrap_mmu_prompt_ids
         cfg = self.cfg
         P = cfg.vit_tokens
@@ -167,10 +170,33 @@ class System(_HotPath):
             ids[i, L - n:] = torch.tensor(s_ids)
             seq_mask[i, L - n:] = torch.tensor(slot)
             attn[i, L - n:] = 1
-        pix = torch.stack([torch.load(r["image_pt"]) if "image_pt" in r else torch.rand(3, cfg.vit_img, cfg.vit_img, generator=g) * 2 - 1
-                           for r in rows])[:, None]
+        if any("image_path" in r and "image_pt" not in r for r in rows):
+            # the reference's PIL path (vl_chat_processor.image_processor, plangen_base.py:136-147): resize / pad / rescale / normalise on the device
+            from plangen_amd.imageproc import load_image_u8
+            dev = self.engine.device
+            todo = [i for i, r in enumerate(rows) if "image_path" in r and "image_pt" not in r]
+            done = self.image_processor()([load_image_u8(rows[i]["image_path"]) for i in todo]).pixel_values
+            per_row = {i: done[k] for k, i in enumerate(todo)}
+            pix = torch.stack([per_row[i] if i in per_row else
+                               (torch.load(r["image_pt"]) if "image_pt" in r else torch.rand(3, cfg.vit_img, cfg.vit_img, generator=g) * 2 - 1).to(dev)
+                               for i, r in enumerate(rows)])[:, None]
+        else:
+            pix = torch.stack([torch.load(r["image_pt"]) if "image_pt" in r else torch.rand(3, cfg.vit_img, cfg.vit_img, generator=g) * 2 - 1
+                               for r in rows])[:, None]
         return dict(input_ids=ids, pixel_values=pix, images_seq_mask=seq_mask, images_emb_mask=torch.ones((len(rows), 1, P), dtype=torch.bool),
                     attention_mask=attn)
+
+    def image_processor(self):
+        """vl_chat_processor.image_processor with image_size = the vision tower's (plangen_base.py:132): the checkpoint directory's
+        preprocessor_config.json when it has one, else Janus-Pro's shipped values (mean = std = 0.5: pixels in [-1, 1], min_size 14)."""
+        if getattr(self, "_image_processor", None) is None:
+            from plangen_amd.imageproc import VLMImageProcessor
+            d = str(self.cli.janus_path) if self.cli.janus_path else ""
+            if d and os.path.exists(os.path.join(d, "preprocessor_config.json")):
+                self._image_processor = VLMImageProcessor.from_config(d, engine=self.engine, image_size=self.cfg.vit_img)
+            else:
+                self._image_processor = VLMImageProcessor(self.cfg.vit_img, image_mean=(0.5, 0.5, 0.5), image_std=(0.5, 0.5, 0.5), engine=self.engine)
+        return self._image_processor
 
     def setup_data(self, accelerator=None):
         """Prompt sharding (plangen_base.py:994) over WHOLE batches: rank r owns a contiguous run of test batches, so its first
