@@ -1,4 +1,5 @@
-// libplangen_diag.so only: operator entry points of the attention kernels for the operator tests (tests/test_gpu_attention.py).  Each one points
+// libplangen_diag.so only: operator entry points of the attention kernels (tests/test_gpu_attention.py) and of the decode step's deferred-RMSNorm
+// pair and slab-folding elementwise kernels (tests/test_gpu_decode_ops.py) for the operator tests.  Each one points
 // the calling thread's pg_tune at a local PgTune (no diagnostics hooks, one kernel-form selector set), calls the PRODUCTION launcher and restores
 // pg_tune.  Shapes the kernels do not support are refused with PG_ERR_ARG and never launched.  Head dimension: 128 for the LLM kernels (implied
 // by the [.., nh * 128] layouts), 64 for SigLIP (C / NH).  Row lengths, slots and token maps live in device memory; they are copied back and
@@ -7,6 +8,7 @@
 #include <vector>
 #include "kernels.h"
 #include "diag.h"
+#include "gemm_skinny.h"       // SK_BK: the K chunk of the tiled decode copy
 #include "../../include/plangen_hip.h"
 
 namespace {
@@ -213,6 +215,65 @@ int pg_diag_op_attn_vit(int form, const void* qk, const void* vt, void* o, int B
     lt.t.vit_attn = form;
     const hipStream_t s = (hipStream_t)stream;
     launch_attn_vit_flash(s, (const bf16*)qk, (const bf16*)vt, (bf16*)o, B, P, C, NH, scale);
+    return launched(s);
+}
+
+// ------------------------------------------------------------------------------------------------ decode step, 65..128 rows (round 6 pair)
+// Producer of the deferred-1/rms pair (launch_rmsnorm_defer): x [M][2048] fp32 += the S slabs of partial (slab elements apart), xw [M][2048] bf16 =
+// bf16(x . w) WITHOUT the 1/rms, ssq [M][8] fp32 = sums of squares of columns [256 j, 256 j + 256).  The launcher's contract is enforced here.
+int pg_diag_op_rmsnorm_defer(float* x, const float* partial, int S, long slab, const void* w, void* xw, float* ssq, int M, int H, pg_stream stream) {
+    if (!x || !partial || !w || !xw || !ssq) return PG_ERR_ARG;
+    if (((uintptr_t)x | (uintptr_t)partial | (uintptr_t)ssq) & 15 || ((uintptr_t)w | (uintptr_t)xw) & 7) return PG_ERR_ARG;      // f32x4 / 4 x bf16 vectors
+    if (H != 2048 || S < 1 || S > 8 || M < 1 || M > 0x7fffffff / 2 / H) return PG_ERR_ARG;
+    if (slab < (long)M * H || slab > 0x7fffffffL || (slab & 3)) return PG_ERR_ARG;      // 32-bit stride, 16-byte loads
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    launch_rmsnorm_defer(s, x, partial, S, slab, (const bf16*)w, (bf16*)xw, ssq, M, H);
+    return launched(s);
+}
+
+// Consumer of the pair: W [N][K] bf16 row-major is re-tiled exactly like pg_op_gemm kind 4 / pg_finalize_weights do, then
+// launch_gemm_skinny_deferred (swiglu 0: out fp32 [S][M][N]) or launch_gemm_skinny_swiglu_deferred (swiglu 1, S == 1: out bf16 [M][N / 2]; W rows
+// already [8 gate | 8 up] interleaved, as for pg_op_swiglu_gemm).  The shape is NOT screened against deferred_norm_ok here: the launcher itself must
+// refuse (return false -> PG_ERR_ARG, out untouched; the tiled copy built before it never touches out), so the tests pin that BOTH launchers consult the
+// predicate.  Only what keeps the tiled copy's own construction in bounds (N % 16, K % SK_BK, sizes) and the consumer's 16-byte loads of ssq is checked.
+int pg_diag_op_gemm_deferred(const void* xw, const void* W_rowmajor, void* out, int M, int N, int K, int S, const float* ssq, float eps, int swiglu,
+                             pg_stream stream) {
+    if (!xw || !W_rowmajor || !out || !ssq) return PG_ERR_ARG;
+    if (swiglu != 0 && swiglu != 1) return PG_ERR_ARG;
+    if (M < 1 || N < 16 || (N & 15) || K < SK_BK || (K % SK_BK) || S < 1 || (swiglu && S != 1) || (long)N * K > 0x7fffffffL) return PG_ERR_ARG;
+    if (((uintptr_t)ssq | (uintptr_t)xw | (uintptr_t)out | (uintptr_t)W_rowmajor) & 15) return PG_ERR_ARG;     // ssq: two f32x4 per row; xw / W / out: 16-byte vectors
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    bf16* wt = nullptr;
+    if (hipMalloc((void**)&wt, (size_t)N * K * 2) != hipSuccess) return PG_ERR_HIP;
+    launch_tile_weights(s, (const bf16*)W_rowmajor, wt, N, K);
+    const bool ok = swiglu ? launch_gemm_skinny_swiglu_deferred(s, (const bf16*)xw, wt, (bf16*)out, M, N, K, ssq, eps)
+                           : launch_gemm_skinny_deferred(s, (const bf16*)xw, wt, (float*)out, M, N, K, S, ssq, eps);
+    const int rc = launched(s);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(wt);
+    return ok ? rc : PG_ERR_ARG;
+}
+
+// Slab-folding elementwise kernels: kind 0 = launch_silu_mul (partial [S][M][2 N] fp32 with [8 gate | 8 up] interleaved columns -> out [M][N] T,
+// N = I, I % 8 == 0; bias / act unused), kind 1 = launch_bias_act (partial [S][M][N] fp32 (+ bias [N] fp32 or null) -> out [M][N] T; act 0 = none,
+// 1 = erf GELU; is_bf16 0 with act 0 is launch_bias_f32).
+int pg_diag_op_slab_epilogue(int kind, int is_bf16, const float* partial, int S, long slab, const float* bias, void* out, int M, int N, int act,
+                             pg_stream stream) {
+    if (!partial || !out) return PG_ERR_ARG;
+    if ((kind != 0 && kind != 1) || M < 1 || M > kMaxGridYZ || N < 1 || S < 1) return PG_ERR_ARG;
+    if (kind == 0 && ((N & 7) || bias || act)) return PG_ERR_ARG;
+    if (kind == 1 && act != 0 && act != 1) return PG_ERR_ARG;
+    if (slab < (long)M * N * (kind == 0 ? 2 : 1)) return PG_ERR_ARG;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    if (kind == 0) {
+        if (is_bf16) launch_silu_mul<bf16>(s, partial, S, slab, (bf16*)out, M, N);
+        else launch_silu_mul<float>(s, partial, S, slab, (float*)out, M, N);
+    } else if (is_bf16) launch_bias_act<bf16>(s, partial, S, slab, bias, (bf16*)out, M, N, act);
+    else if (act == 0) launch_bias_f32(s, partial, S, slab, bias, (float*)out, M, N);
+    else launch_bias_act<float>(s, partial, S, slab, bias, (float*)out, M, N, act);
     return launched(s);
 }
 

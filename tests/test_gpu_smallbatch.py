@@ -7,11 +7,15 @@ The dispatch depends on the row count M = 2 x images (launch_attn_decode_fused /
     first 160 keys of a segment go through the peeled chunk, the software-pipelined loop (run_pipe) only starts beyond them,
     and the shared-prefix loop only beyond 160 SHARED keys;
   * bs = 32: attn_decode_fused_kernel<bf16,6,4,16> (96 keys per iteration) on 64 rows;
-  * the 16- / 32- / 64-row decode GEMM blocks (gemm_sk4_kernel<1|2|4, NCK, ...>), rmsnorm512_kernel, the M <= 16 sampler.
+  * the 16- / 32- / 64-row decode GEMM blocks (gemm_sk4_kernel<1|2|4, NCK, ...>), rmsnorm512_kernel, the M <= 16 sampler;
+  * 33 / 40 / 48 pairs = 66 / 80 / 96 rows (bf16): the deferred-1/rms pair (rmsnorm_defer_kernel + gemm_skinny3_kernel<4, NCK, 2, true, EPI, 8, TILED>
+    with ssq) BETWEEN the 64-row blocks -- 66 leaves two valid rows in the second block (x and ssq rows clamped to M - 1), 80 sits under the
+    split_mid boundary of skinny_pick_splits (o_proj leaves 8 slabs: ln2 runs rmsnorm_defer_kernel<8>), 96 on it; 128 rows are
+    tests/test_gpu_fullwidth.py's, the operators themselves tests/test_gpu_decode_ops.py's.
 
 Two references:
 
-  1. pairs [:8] / [:16] / [:32] of tests/golden/sample_image_fullwidth.npz (rows are independent, so a slice of the 64-pair
+  1. pairs [:8] / [:16] / [:32] / [:33] / [:40] / [:48] of tests/golden/sample_image_fullwidth.npz (rows are independent, so a slice of the 64-pair
      fixture IS the reference of the smaller batch): 48 steps, cond rows 160-256 + 48 keys, shared 96-token negative prompt;
   2. tests/golden/sample_image_b8_long.npz (oracle/make_golden.py::golden_small_batch): 8 pairs, L = 256, ONE shared
      200-token negative prompt, T = 288 greedy steps -> cond rows reach 448-544 keys (peeled chunk + 2-3 run_pipe iterations),
@@ -73,7 +77,7 @@ def _bf16_stats(logits, toks, g, sl, T, name="sample_image_fullwidth"):
     return stats
 
 
-@pytest.mark.parametrize("pairs", [8, 16, 32])
+@pytest.mark.parametrize("pairs", [8, 16, 32, 40])
 def test_fixture_slices_f32_tokens_bit_exact(pairs):
     """Free-running greedy loop on the first `pairs` CFG pairs of the 64-pair fixture, engine sized for exactly that batch."""
     g = _setup()["g"]
@@ -90,7 +94,7 @@ def test_fixture_slices_f32_tokens_bit_exact(pairs):
     assert np.array_equal(ti[..., 0].cpu().numpy(), g["top_i"][:, :pairs, 0])
 
 
-@pytest.mark.parametrize("pairs", [8, 16, 32])
+@pytest.mark.parametrize("pairs", [8, 16, 32, 33, 40, 48])
 def test_fixture_slices_bf16_teacher_forced(pairs):
     g = _setup()["g"]
     e = _engine("bf16", 2 * pairs)
