@@ -322,7 +322,7 @@ extern "C" int pg_bench_conv_gn_check(int B, int Hi, int Wi, int Cin, int Cout, 
     int rc = 0;
     if (ns > 0) {
         launch_gn_finalize(s, wsB, stB, nullptr, gam, gam, B, ns, (int)HW, Cout, 1e-6f);
-        launch_gn_stats(s, o0, 0, stA, wsA, B, (int)HW, Cout, 1e-6f, nullptr, gam, gam);
+        if (!launch_gn_stats(s, o0, 0, stA, wsA, B, (int)HW, Cout, 1e-6f, nullptr, gam, gam)) return PG_ERR_ARG;
         std::vector<float> a((size_t)B * 64), b((size_t)B * 64);
         hipStreamSynchronize(s);
         hipMemcpy(a.data(), stA, a.size() * 4, hipMemcpyDeviceToHost); hipMemcpy(b.data(), stB, b.size() * 4, hipMemcpyDeviceToHost);

@@ -277,4 +277,201 @@ int pg_diag_op_slab_epilogue(int kind, int is_bf16, const float* partial, int S,
     return launched(s);
 }
 
+// ------------------------------------------------------------------------------------------------ VQ-16 decoder operators (tests/test_gpu_vq_ops.py)
+// Every entry point below synchronises the stream before it returns.  Which kernel ran is part of the result: forms that name ONE kernel call that kernel's
+// own launcher (conv_halo_try, gemm256_try, conv_out_halo_try, conv_out_gn_try) and return PG_ERR_ARG, output untouched, when it declines the shape; form 0
+// (the production dispatch) reports it through *nsplit_out.
+}  // extern "C"
+namespace {
+int finish(hipStream_t s) {
+    const hipError_t a = hipGetLastError(), b = hipStreamSynchronize(s);
+    return a == hipSuccess && b == hipSuccess ? PG_OK : PG_ERR_HIP;
+}
+bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+struct ZeroPage {                   // the convolutions' zero halo source (>= 256 B)
+    void* p = nullptr;
+    bool ok() { return hipMalloc(&p, 1024) == hipSuccess && hipMemset(p, 0, 1024) == hipSuccess; }
+    ~ZeroPage() { if (p) (void)hipFree(p); }
+};
+}  // namespace
+extern "C" {
+
+// 3x3 convolution through the engine's own call (pg_engine::conv3): x NHWC [B][Hi][Wi][Cin] T, w [Cout][9][Cin] T (Engine.op_conv3x3's layout), bias fp32 [Cout],
+// residual [B][Ho][Wo][Cout] fp32 (res_f32) or T, or null; out [B][Ho][Wo][Cout] fp32 (out_f32) or T.  engine_bf16 0: gemm_f32_kernel<ConvLoaderB<float>> (form 0 / 1,
+// fp32 residual and output, no partials).  form: 0 launch_gemm as the engine calls it, 1 the 128 x 128 implicit GEMM (conv_halo = gemm256 = 0), 2 gemm256_try
+// (gn_epilogue256 = want_gn), 3 conv_halo_try with the fast epilogues (conv_halo = 1), 4 conv_halo_try lock-step (conv_halo = 2).  want_gn: GroupNorm partials into
+// ws (ws_floats fp32 available); *nsplit_out = splits per image the kernel wrote (0: none) and, when > 0, launch_gn_finalize -> stats [B][32][2] = (mean, rstd).
+int pg_diag_op_conv3x3(int engine_bf16, int form, const void* x, const void* w, const float* bias, const void* residual, void* out, int out_f32, int res_f32,
+                       int B, int Hi, int Wi, int Cin, int Cout, int up, int stride2, int want_gn, float* ws, long ws_floats, float* stats, float eps,
+                       int* nsplit_out, pg_stream stream) {
+    if (!x || !w || !bias || !out || !nsplit_out) return PG_ERR_ARG;
+    if (form < 0 || form > 4 || (!engine_bf16 && form > 1)) return PG_ERR_ARG;
+    if ((up != 0 && up != 1) || (stride2 != 0 && stride2 != 1) || (up && stride2)) return PG_ERR_ARG;
+    if (B < 1 || Hi < 1 || Wi < 1 || Cin < 1 || Cout < 1 || (stride2 && (Hi < 2 || Wi < 2))) return PG_ERR_ARG;
+    if (Hi > 16384 || Wi > 16384 || (long)B * Hi * Wi * Cin >= (1L << 31)) return PG_ERR_ARG;       // 32-bit element offsets of the slim loader, packed (y, x)
+    const int Ho = stride2 ? Hi / 2 : (Hi << up), Wo = stride2 ? Wi / 2 : (Wi << up);
+    const long M = (long)B * Ho * Wo;
+    if (M * Cout >= (1L << 31)) return PG_ERR_ARG;
+    if (engine_bf16) {
+        if (!pow2(Cin) || Cin < 64 || Cin > 512) return PG_ERR_ARG;                                  // ConvLoader: 64-element K tiles inside one tap, shift / mask
+        if (((uintptr_t)x | (uintptr_t)w) & 15) return PG_ERR_ARG;                                  // 16-byte LDS-DMA
+    } else if (!out_f32 || (residual && !res_f32) || want_gn) return PG_ERR_ARG;
+    if (((uintptr_t)out | (uintptr_t)residual | (uintptr_t)bias) & 15) return PG_ERR_ARG;
+    *nsplit_out = 0;
+    if (want_gn) {
+        if (!ws || !stats || Cout % 32) return PG_ERR_ARG;
+        const long t_halo = (long)(Ho / 8) * (Wo / 32), t_256 = (long)Ho * Wo / 64;
+        if (t_halo > 1024 || t_256 > 1024) return PG_ERR_ARG;                                        // pg_engine::conv3 asks for partials up to 1024 tiles per image
+        if (ws_floats < (long)B * (t_halo > t_256 ? t_halo : t_256) * 64) return PG_ERR_ARG;
+    }
+    ZeroPage z;
+    if (!z.ok()) return PG_ERR_HIP;
+    LocalTune lt;
+    lt.t.conv_halo = form == 0 || form == 3 ? 1 : form == 4 ? 2 : 0;
+    lt.t.gemm256 = form == 1 ? 0 : 1;
+    lt.t.gn_epilogue256 = form == 2 && want_gn ? 1 : 0;
+    const hipStream_t s = (hipStream_t)stream;
+    GemmA a; a.kind = stride2 ? 2 : 1; a.ptr = x; a.Hi = Hi; a.Wi = Wi; a.Cin = Cin; a.up = up; a.zeros = z.p;
+    GemmEpi e; e.out = out; e.out_f32 = out_f32; e.ldc = Cout; e.bias_n = bias; e.residual = residual; e.res_f32 = res_f32;
+    int nsp = 0;
+    if (want_gn) { a.gn_part = ws; a.gn_nsplit = &nsp; }
+    bool taken = true;
+    if (!engine_bf16) launch_gemm<float>(s, a, (const float*)w, 9L * Cin, 0, e, (int)M, Cout, 9 * Cin, 1);
+    else if (form == 2) taken = gemm256_try(s, a, (const bf16*)w, 9L * Cin, 0, e, (int)M, Cout, 9 * Cin, 1, 1, 0);
+    else if (form >= 3) taken = conv_halo_try(s, a, (const bf16*)w, e, (int)M, Cout, 9 * Cin, ws && want_gn ? ws : nullptr, want_gn ? &nsp : nullptr);
+    else launch_gemm<bf16>(s, a, (const bf16*)w, 9L * Cin, 0, e, (int)M, Cout, 9 * Cin, 1);
+    if (taken && nsp > 0) launch_gn_finalize(s, ws, stats, nullptr, nullptr, nullptr, B, nsp, Ho * Wo, Cout, eps);
+    const int rc = finish(s);
+    if (!taken) return PG_ERR_ARG;
+    *nsplit_out = nsp;
+    return rc;
+}
+
+// GroupNorm(32) as pg_engine::gn runs it: launch_gn_stats (x [B][HW][C], fp32 or bf16) -> stats [B][32][2], coef [B][C][2]; launch_gn_apply -> out (fp32 or bf16).
+// (in, out) one of the three instantiated pairs: fp32 -> fp32, fp32 -> bf16, bf16 -> bf16.  ws: the partial sums, ws_floats fp32 available.
+int pg_diag_op_groupnorm(int in_bf16, int out_bf16, const void* x, const float* gamma, const float* beta, void* out, float* stats, float* coef, float* ws,
+                         long ws_floats, int B, int HW, int C, int swish, float eps, pg_stream stream) {
+    if (!x || !gamma || !beta || !out || !stats || !coef || !ws) return PG_ERR_ARG;
+    if (in_bf16 && !out_bf16) return PG_ERR_ARG;                                                     // no bf16 -> fp32 instantiation
+    if (B < 1 || B > kMaxGridYZ || HW < 1 || C < 32 || C % 32 || (long)B * HW * C >= (1L << 40)) return PG_ERR_ARG;
+    const int epv_in = in_bf16 ? 8 : 4, epv_out = out_bf16 ? 8 : 4;
+    if (C % epv_in || C / epv_in > 256 || C % epv_out) return PG_ERR_ARG;                            // gn_stats_kernel: a thread per 16-byte vector of a pixel; gn_apply: whole vectors
+    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)coef) & 15) return PG_ERR_ARG;
+    const long nsplit = HW > 16384 ? 256 : (HW + 63) / 64;
+    if (ws_floats < (long)B * nsplit * 64) return PG_ERR_ARG;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    if (!launch_gn_stats(s, x, in_bf16, stats, ws, B, HW, C, eps, coef, gamma, beta)) return PG_ERR_ARG;
+    if (in_bf16) launch_gn_apply<bf16, bf16>(s, (const bf16*)x, coef, (bf16*)out, B, HW, C, swish);
+    else if (out_bf16) launch_gn_apply<float, bf16>(s, (const float*)x, coef, (bf16*)out, B, HW, C, swish);
+    else launch_gn_apply<float, float>(s, (const float*)x, coef, (float*)out, B, HW, C, swish);
+    return finish(s);
+}
+
+// launch_gn_stats alone on whatever shape the caller names: the LAUNCHER must refuse what its kernel cannot do (false -> PG_ERR_ARG, stats untouched).
+// Buffers must be sized for the shape as if it ran.
+int pg_diag_op_gn_stats_raw(int in_bf16, const void* x, const float* gamma, const float* beta, float* stats, float* coef, float* ws, int B, int HW, int C,
+                            pg_stream stream) {
+    if (!x || !gamma || !beta || !stats || !coef || !ws) return PG_ERR_ARG;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    const bool ok = launch_gn_stats(s, x, in_bf16, stats, ws, B, HW, C, 1e-6f, coef, gamma, beta);
+    const int rc = finish(s);
+    return ok ? rc : PG_ERR_ARG;
+}
+
+// softmax(x * scale) over the rows of x fp32 [rows][n] -> y [rows][n] fp32 or bf16 (launch_softmax_rows).
+int pg_diag_op_softmax_rows(int out_bf16, const float* x, void* y, int rows, int n, float scale, pg_stream stream) {
+    if (!x || !y || rows < 1 || n < 1 || (long)rows * n >= (1L << 40)) return PG_ERR_ARG;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    if (out_bf16) launch_softmax_rows<bf16>(s, x, (bf16*)y, rows, n, scale);
+    else launch_softmax_rows<float>(s, x, (float*)y, rows, n, scale);
+    return finish(s);
+}
+
+// C = A . W^T through launch_gemm (kind 0) with the whole epilogue struct: A [batch][M][K] (lda, strideA; strideA 0 broadcasts), W [batch][N][K] (ldb, strideB),
+// out fp32 (out_f32) or T (ldc, strideC), v = acc scale + bias_n[col] + bias_m[row] + residual (fp32 when res_f32, else T; ldr / strideR, 0: as out), act 0 / 1 (erf GELU).
+// engine_bf16 0: gemm_f32_kernel.  form: 0 launch_gemm as the engine calls it, 1 the 128 x 128 kernel (gemm256 = 0), 2 gemm256_try (gn_epilogue256 = gn_hw > 0).
+// gn_hw > 0: GroupNorm partials of the output (pixels per image) -> ws, *nsplit_out, stats as pg_diag_op_conv3x3.
+int pg_diag_op_gemm_epi(int engine_bf16, int form, const void* A, long lda, long strideA, const void* W, long ldb, long strideB, void* out, int out_f32, long ldc,
+                        long strideC, const float* bias_n, const float* bias_m, const void* residual, int res_f32, long ldr, long strideR, float scale, int act,
+                        int M, int N, int K, int batch, int gn_hw, float* ws, long ws_floats, float* stats, float eps, int* nsplit_out, pg_stream stream) {
+    if (!A || !W || !out || !nsplit_out) return PG_ERR_ARG;
+    if (form < 0 || form > 2 || (!engine_bf16 && form == 2) || (act != 0 && act != 1)) return PG_ERR_ARG;
+    if (M < 1 || N < 1 || K < 1 || batch < 1 || batch > kMaxGridYZ || lda < K || ldb < K || ldc < N || strideA < 0 || strideB < 0 || strideC < 0) return PG_ERR_ARG;
+    if (batch > 1 && strideC < (long)(M - 1) * ldc + N) return PG_ERR_ARG;                           // batches must not overlap in the output
+    if (residual && ((ldr && ldr < N) || strideR < 0)) return PG_ERR_ARG;
+    if (engine_bf16) {
+        // PlainLoaderB / the weight rows: 64-element K tiles fetched as 16-byte LDS-DMA chunks
+        if (K % 64 || ((lda | ldb | strideA | strideB) & 7) || (((uintptr_t)A | (uintptr_t)W) & 15)) return PG_ERR_ARG;
+    } else if (!out_f32 || (residual && !res_f32) || gn_hw) return PG_ERR_ARG;
+    if (((uintptr_t)out | (uintptr_t)residual | (uintptr_t)bias_n) & 15) return PG_ERR_ARG;         // vec_ok() looks at the leading dimensions and offsets only
+    *nsplit_out = 0;
+    if (gn_hw) {
+        if (gn_hw < 1 || !ws || !stats || N % 32 || M % gn_hw || batch != 1) return PG_ERR_ARG;
+        if (ws_floats < (long)(M / gn_hw) * ((gn_hw + 63) / 64) * 64) return PG_ERR_ARG;
+    }
+    LocalTune lt;
+    lt.t.gemm256 = form == 1 ? 0 : 1;
+    lt.t.gn_epilogue256 = form == 2 && gn_hw ? 1 : 0;
+    const hipStream_t s = (hipStream_t)stream;
+    GemmA a; a.ptr = A; a.lda = lda; a.strideA = strideA;
+    GemmEpi e; e.out = out; e.out_f32 = out_f32; e.ldc = ldc; e.strideC = strideC; e.bias_n = bias_n; e.bias_m = bias_m; e.residual = residual; e.res_f32 = res_f32;
+    e.ldr = ldr; e.strideR = strideR; e.scale = scale; e.act = act;
+    int nsp = 0;
+    if (gn_hw) { a.gn_part = ws; a.gn_nsplit = &nsp; a.gn_hw = gn_hw; }
+    bool taken = true;
+    if (!engine_bf16) launch_gemm<float>(s, a, (const float*)W, ldb, strideB, e, M, N, K, batch);
+    else if (form == 2) taken = gemm256_try(s, a, (const bf16*)W, ldb, strideB, e, M, N, K, batch, 1, 0);
+    else launch_gemm<bf16>(s, a, (const bf16*)W, ldb, strideB, e, M, N, K, batch);
+    if (taken && nsp > 0) launch_gn_finalize(s, ws, stats, nullptr, nullptr, nullptr, M / gn_hw, nsp, gn_hw, N, eps);
+    const int rc = finish(s);
+    if (!taken) return PG_ERR_ARG;
+    *nsplit_out = nsp;
+    return rc;
+}
+
+// The decoder's conv_out (Cin -> Cout <= 4), NHWC in -> NCHW out (fp32, or bf16 when out_bf16).  form 1: launch_conv3x3_small<T> (x, w T; engine_bf16 picks T);
+// 2: conv_out_halo_try with conv_halo = 1 (conv3x3_out2_kernel); 3: conv_out_halo_try with conv_halo = 2 (conv3x3_out_halo_kernel); 4: conv_out_gn_try
+// (conv3x3_out_gn_kernel: x is the FP32 skip tensor, coef [B][Cin][2] the GroupNorm coefficients, swish as the decoder's tail).  Forms 2-4: bf16 weights.
+int pg_diag_op_conv_out(int engine_bf16, int form, const void* x, const float* coef, const void* w, const float* bias, void* out, int out_bf16, int B, int H,
+                        int Wd, int Cin, int Cout, int swish, pg_stream stream) {
+    if (!x || !w || !bias || !out || form < 1 || form > 4 || (form > 1 && !engine_bf16) || (form == 4 && !coef)) return PG_ERR_ARG;
+    if (B < 1 || B > kMaxGridYZ || H < 1 || H > kMaxGridYZ || Wd < 1 || Cin < 1 || Cout < 1 || Cout > 4) return PG_ERR_ARG;
+    if ((long)B * H * Wd * Cin >= (1L << 31) || (((uintptr_t)x | (uintptr_t)w | (uintptr_t)coef) & 15)) return PG_ERR_ARG;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    bool taken = true;
+    if (form == 1) {
+        const int epv = engine_bf16 ? 8 : 4, esz = engine_bf16 ? 2 : 4;
+        if (Cin % (4 * epv)) return PG_ERR_ARG;                                                      // four channel quarters of whole 16-byte vectors per pixel
+        if ((size_t)3 * 66 * (Cin * esz + 16) + (size_t)Cout * 9 * Cin * 4 > 160 * 1024) return PG_ERR_ARG;     // the strip and the fp32 weights live in LDS
+        if (engine_bf16) launch_conv3x3_small<bf16>(s, (const bf16*)x, (const bf16*)w, bias, out, out_bf16, B, H, Wd, Cin, Cout);
+        else launch_conv3x3_small<float>(s, (const float*)x, (const float*)w, bias, out, out_bf16, B, H, Wd, Cin, Cout);
+    } else if (form == 4) {
+        lt.t.conv_halo = 1;
+        taken = conv_out_gn_try(s, (const float*)x, coef, (const bf16*)w, bias, out, out_bf16, B, H, Wd, Cin, Cout, swish);
+    } else {
+        ZeroPage z;
+        if (!z.ok()) return PG_ERR_HIP;
+        lt.t.conv_halo = form == 2 ? 1 : 2;
+        taken = conv_out_halo_try(s, (const bf16*)x, (const bf16*)w, bias, (const bf16*)z.p, out, out_bf16, B, H, Wd, Cin, Cout);
+        const int rc = finish(s);                                                                    // before the zero page goes away
+        return taken ? rc : PG_ERR_ARG;
+    }
+    const int rc = finish(s);
+    return taken ? rc : PG_ERR_ARG;
+}
+
+// out [n][C] = table[clamp(codes[p], 0, vocab - 1)] (launch_vq_gather), T = bf16 or fp32.
+int pg_diag_op_vq_gather(int is_bf16, const void* table, const int32_t* codes, void* out, int n, int C, int vocab, pg_stream stream) {
+    if (!table || !codes || !out || n < 1 || C < 1 || vocab < 1) return PG_ERR_ARG;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    if (is_bf16) launch_vq_gather<bf16>(s, (const bf16*)table, codes, (bf16*)out, n, C, vocab);
+    else launch_vq_gather<float>(s, (const float*)table, codes, (float*)out, n, C, vocab);
+    return finish(s);
+}
+
 }  // extern "C"

@@ -122,6 +122,7 @@ struct pg_engine {
     void *cur = nullptr, *t1 = nullptr, *t2 = nullptr, *t3 = nullptr;
     void *aq = nullptr, *ak = nullptr, *avt = nullptr, *ao = nullptr, *ap = nullptr; float* ascore = nullptr;
     float *gn_stats = nullptr, *gn_ws = nullptr, *gn_coef = nullptr;
+    bool gn_refused = false;                                             // launch_gn_stats declined a shape: the entry point that ran it returns PG_ERR_ARG
     const void* gn_part_of = nullptr; int gn_part_n = 0, gn_part_b = 0;   // gn_ws holds conv-epilogue partials of this tensor
     float* enc_z = nullptr;
     void* stage_dev = nullptr; long stage_bytes = 0;
@@ -202,6 +203,7 @@ struct pg_engine {
     void slot_shape(const std::string& name, std::initializer_list<int64_t> shp) { slots_map[name].shape = shp; }
     int alloc_conv(const std::string& name, ConvW& cw, int cout, int cin, int k);
     int alloc_norm(const std::string& name, NormW& nw, int c);
+    int alloc_gnorm(const std::string& name, NormW& nw, int c);
     int alloc_res(const std::string& name, ResBlockW& r, int cin, int cout);
     int alloc_attn(const std::string& name, AttnW& a, int c);
     int build_vq();

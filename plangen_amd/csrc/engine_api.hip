@@ -313,10 +313,12 @@ int pg_op_groupnorm(pg_handle h, const void* x_dev, const float* gamma_dev, cons
                     int HW, int C, int swish, pg_stream s) { TuneGuard _tg(h);
     if (!h || !x_dev || !out_dev) return PG_ERR_ARG;
     if (B > h->cfg.max_images || C > 1024) { h->err = "pg_op_groupnorm: B > max_images or C > 1024"; return PG_ERR_CAPACITY; }
+    if (B < 1 || HW < 1 || C < 32 || C % 32) { h->err = "pg_op_groupnorm: C must be a positive multiple of 32"; return PG_ERR_ARG; }
     (void)hipSetDevice(h->dev);
     NormW n; n.g = (float*)gamma_dev; n.b = (float*)beta_dev; n.c = C;
     if (h->bf) h->gn<bf16>((hipStream_t)s, n, (const float*)x_dev, (bf16*)out_dev, B, HW, swish);
     else h->gn<float>((hipStream_t)s, n, (const float*)x_dev, (float*)out_dev, B, HW, swish);
+    if (h->gn_refused) { h->gn_refused = false; h->err = "pg_op_groupnorm: launch_gn_stats refused the shape"; return PG_ERR_ARG; }
     return hipGetLastError() == hipSuccess ? PG_OK : PG_ERR_HIP;
 }
 

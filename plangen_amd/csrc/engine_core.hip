@@ -23,17 +23,22 @@ int pg_engine::alloc_norm(const std::string& name, NormW& nw, int c) {
     add_slot(name + ".bias", nw.b, K_F32, c);
     return PG_OK;
 }
+// GroupNorm(32) of the VQ model: what launch_gn_stats takes (32 groups, at most 256 16-byte vectors of fp32 per pixel)
+int pg_engine::alloc_gnorm(const std::string& name, NormW& nw, int c) {
+    if (c < 32 || c % 32 || c > 1024) FAIL(PG_ERR_ARG, "%s: GroupNorm(32) over %d channels (multiples of 32 up to 1024)", name.c_str(), c);
+    return alloc_norm(name, nw, c);
+}
 int pg_engine::alloc_res(const std::string& name, ResBlockW& r, int cin, int cout) {
-    TRY(alloc_norm(name + ".norm1", r.n1, cin));
+    TRY(alloc_gnorm(name + ".norm1", r.n1, cin));
     TRY(alloc_conv(name + ".conv1", r.c1, cout, cin, 3));
-    TRY(alloc_norm(name + ".norm2", r.n2, cout));
+    TRY(alloc_gnorm(name + ".norm2", r.n2, cout));
     TRY(alloc_conv(name + ".conv2", r.c2, cout, cout, 3));
     r.has_nin = cin != cout;
     if (r.has_nin) TRY(alloc_conv(name + ".nin_shortcut", r.nin, cout, cin, 1));
     return PG_OK;
 }
 int pg_engine::alloc_attn(const std::string& name, AttnW& a, int c) {
-    TRY(alloc_norm(name + ".norm", a.n, c));
+    TRY(alloc_gnorm(name + ".norm", a.n, c));
     TRY(alloc_conv(name + ".q", a.q, c, c, 1));
     TRY(alloc_conv(name + ".k", a.k, c, c, 1));
     TRY(alloc_conv(name + ".v", a.v, c, c, 1));
@@ -70,7 +75,7 @@ int pg_engine::build_vq() {
                 TRY(alloc_conv(p + ".upsample.conv", lv.resample, block_in, block_in, 3));
             }
         }
-        TRY(alloc_norm(D + "norm_out", dec.norm_out, block_in));
+        TRY(alloc_gnorm(D + "norm_out", dec.norm_out, block_in));
         TRY(alloc_conv(D + "conv_out", dec.conv_out, 3, block_in, 3));
     }
     if (cfg.with_vq_encoder) {
@@ -101,7 +106,7 @@ int pg_engine::build_vq() {
         TRY(alloc_res(E + "mid.0", enc.mid0, b_in, b_in));
         TRY(alloc_attn(E + "mid.1", enc.mid1, b_in));
         TRY(alloc_res(E + "mid.2", enc.mid2, b_in, b_in));
-        TRY(alloc_norm(E + "norm_out", enc.norm_out, b_in));
+        TRY(alloc_gnorm(E + "norm_out", enc.norm_out, b_in));
         TRY(alloc_conv(E + "conv_out", enc.conv_out, cfg.vq_z, b_in, 3));
         TRY(dalloc(&qc_w, (size_t)cfg.img_dim * cfg.vq_z * esz));
         TRY(dalloc(&qc_b, (size_t)cfg.img_dim * 4));

@@ -11,7 +11,7 @@ template <typename TI>
 void pg_engine::gn_coefs(hipStream_t s, const NormW& n, const TI* in, int B, int HW) {
     // statistics already produced by the convolution that wrote ``in`` (conv_halo / gemm256 epilogue)?
     if (gn_part_of == (const void*)in && gn_part_n > 0 && gn_part_b == B) launch_gn_finalize(s, gn_ws, gn_stats, gn_coef, n.g, n.b, B, gn_part_n, HW, n.c, 1e-6f);
-    else launch_gn_stats(s, in, sizeof(TI) == 2, gn_stats, gn_ws, B, HW, n.c, 1e-6f, gn_coef, n.g, n.b);
+    else if (!launch_gn_stats(s, in, sizeof(TI) == 2, gn_stats, gn_ws, B, HW, n.c, 1e-6f, gn_coef, n.g, n.b)) gn_refused = true;
     gn_part_of = nullptr;
 }
 template <typename T, typename TI>
@@ -147,6 +147,7 @@ int pg_engine::vq_decode(const int32_t* codes, void* img_out, int out_dtype, int
     HIPCHK(hipEventRecord(ev_v1, s));
     have_vq_t = true;
     HIPCHK(hipGetLastError());
+    if (gn_refused) { gn_refused = false; FAIL(PG_ERR_ARG, "GroupNorm statistics refused a channel count"); }
     return PG_OK;
 }
 
@@ -186,6 +187,7 @@ int pg_engine::vq_encode(const void* img, int img_dtype, int64_t* idx, int B, hi
     }
     launch_vq_argmin(s, enc_z, codebook_n, idx, B * side * side, cfg.img_dim, cfg.img_vocab);
     HIPCHK(hipGetLastError());
+    if (gn_refused) { gn_refused = false; FAIL(PG_ERR_ARG, "GroupNorm statistics refused a channel count"); }
     return PG_OK;
 }
 

@@ -267,8 +267,8 @@ template <typename T>
 void launch_vq_gather(hipStream_t s, const T* table, const int32_t* codes, T* out, int n, int C, int vocab);
 // GroupNorm(32, eps): statistics -> stats fp32 [B,32,2] = (mean, rstd) and, when coef != null,
 // per-(image, channel) affine coefficients coef fp32 [B,C,2] = (rstd*gamma, beta - mean*rstd*gamma).
-// ws: fp32 scratch >= B*32*2*nsplit
-void launch_gn_stats(hipStream_t s, const void* x, int is_bf16, float* stats, float* ws, int B, int HW, int C, float eps,
+// ws: fp32 scratch >= B*32*2*nsplit.  False (nothing launched) when C is not a multiple of 32 and of the 16-byte vector, or a pixel has more than 256 vectors.
+bool launch_gn_stats(hipStream_t s, const void* x, int is_bf16, float* stats, float* ws, int B, int HW, int C, float eps,
                      float* coef, const float* gamma, const float* beta);
 // y = x*a + sh, optional swish
 template <typename TI, typename TO>

@@ -111,15 +111,19 @@ void launch_gn_finalize(hipStream_t s, const float* ws, float* stats, float* coe
 // Splits per image.  Round 6: one split per 64 pixels (was per 1 024): at 24^2 a split per 1 024 pixels meant ONE block per image -- 64 blocks walking 288 dependent
 // iterations each, 77 us for 75 MB (1.0 TB/s); with 9 splits per image the same pass is 576 blocks of 32 iterations.  gn_finalize_kernel adds the splits in double.
 static int gn_nsplit(int HW) { int n = (HW + 63) / 64; return n < 1 ? 1 : (n > 256 ? 256 : n); }
-void launch_gn_stats(hipStream_t s, const void* x, int is_bf16, float* stats, float* ws, int B, int HW, int C, float eps,
+bool launch_gn_stats(hipStream_t s, const void* x, int is_bf16, float* stats, float* ws, int B, int HW, int C, float eps,
                      float* coef, const float* gamma, const float* beta) {
     const int nsplit = gn_nsplit(HW);
     const int EPV = is_bf16 ? 8 : 4;
+    // the kernel's contract: 32 groups, 16-byte channel vectors, one thread per vector of a pixel.  With C / EPV > 256 the kernel would sum nothing and then
+    // reduce LDS it never wrote: refused here, nothing is launched
+    if (B < 1 || HW < 1 || C < 32 || C % 32 || C % EPV || C / EPV > 256) return false;
     const int VPP = C / EPV, PL = 256 / VPP > 0 ? 256 / VPP : 1;
     const size_t lds = (size_t)2 * PL * C * sizeof(float);
     if (is_bf16) hipLaunchKernelGGL(gn_stats_kernel<bf16>, dim3(nsplit, B), dim3(256), lds, s, (const bf16*)x, ws, HW, C, nsplit);
     else hipLaunchKernelGGL(gn_stats_kernel<float>, dim3(nsplit, B), dim3(256), lds, s, (const float*)x, ws, HW, C, nsplit);
     hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(256), 0, s, ws, stats, coef, gamma, beta, nsplit, (double)HW * (C / 32), eps, C);
+    return true;
 }
 
 // y = swish?(x * a[b][c] + sh[b][c]); grid (chunks, B); input TI (fp32 skip stream or T), output TO.
