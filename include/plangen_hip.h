@@ -228,6 +228,54 @@ int pg_generate_text_sampled(pg_handle h, int max_new, int min_new, int eos_id, 
                              float top_p, uint64_t seed, int64_t* out_dev, int* out_len_host,
                              float* logits_out_dev, pg_stream s);
 
+/* Grammar-constrained text decode: a finite automaton over TOKENS masks the logits of every step,
+ * so a row can only spell a sentence of the automaton's language and is certain to finish inside its
+ * budget (plangen_amd/grammar.py builds the layout language's automaton over a tokenizer).
+ *   token_class_host [vocab]             class of every token id, 0 .. n_classes-1
+ *   next_state_host  [n_states, n_classes]  next state, or -1: a token of this class is not allowed here
+ *   dist_host        [n_states]          fewest further tokens (the EOS included) until the row can
+ *                                        finish; >= 2^30: it cannot finish from here
+ * pg_set_text_dfa validates on the host, before anything is launched (PG_ERR_ARG: n_states outside
+ * 1..4096, n_classes outside 1..1024, start_state or a class id or a next state out of range, a negative
+ * dist, or a state with 0 < dist < 2^30 from which no class that holds a token leads to a state with
+ * dist <= its own - 1: the promise the budget rule rests on), then copies the tables through pinned
+ * staging on s without synchronising the stream.  The device buffers are allocated once, at those
+ * limits, by the first upload (counted by pg_device_bytes; that one call also waits for the buffers'
+ * zero fill on the NULL stream): a captured step graph keeps valid addresses and replays with whatever
+ * automaton was uploaded last.  dfa == NULL forgets the automaton.
+ * The tables do not say which token is EOS, so one property is the builder's to keep: a state with
+ * dist == 0 is entered by eos_id only (grammar.py's automata do).  A hand-made automaton that lets
+ * another token into such a state is accepted, but its rows may reach column max_new - 1 without EOS. */
+typedef struct pg_text_dfa {
+    const int16_t* token_class_host;
+    const int16_t* next_state_host;
+    const int32_t* dist_host;
+    int32_t n_states, n_classes, start_state;
+} pg_text_dfa;
+int pg_set_text_dfa(pg_handle h, const pg_text_dfa* dfa /* NULL: forget it */, pg_stream s);
+/* pg_generate_text_sampled under the automaton.  Every row starts in start_state.  Per row and step,
+ * with remaining = max_new - step (this step counted), token v is ALLOWED in state st iff
+ *   nx = next_state[st][token_class[v]] >= 0   and   dist[nx] <= remaining - 1
+ * (the budget rule: a row only moves to states it can still finish from; dist[start_state] <= max_new is
+ * checked, PG_ERR_ARG otherwise, so every unfinished row emits EOS no later than column max_new - 1,
+ * given the property above).
+ * Disallowed logits become -inf BEFORE temperature, top-k and top-p (where HF applies logits processors
+ * and where the min_new EOS suppression sits); the draw is then exactly pg_generate_text_sampled's: same
+ * noise keyed on (seed, row + "rng_image_offset", step), same filter rule, lowest index on ties;
+ * temperature <= 0 is the masked argmax.  Nothing kept (every allowed logit -inf or NaN): the row emits
+ * eos_id, finishes and keeps its state (not token 0, which could lie outside the language).  An unfinished
+ * row's state becomes next_state[state][token_class[tok]] once its token is chosen; a finished row keeps
+ * its state and emits eos.  There is no min_new: the automaton says where EOS may stand.
+ * state_out_dev int32 [B] or NULL: the final states.  logits_out_dev fp32 [max_new, B, vocab] or NULL:
+ * each step's row after the mask (disallowed entries -inf).  PG_ERR_STATE: no automaton set, and
+ * whatever pg_generate_text_sampled answers so; PG_ERR_ARG: top_k / top_p as there; PG_ERR_CAPACITY:
+ * max_new as there.  The handle stays usable after every error.  pg_generate_text_greedy / _sampled
+ * ignore the automaton: same launches, same bits, and scan kernels whose instruction streams are
+ * unchanged (the automaton is a template parameter that is off for them). */
+int pg_generate_text_constrained(pg_handle h, int max_new, int eos_id, float temperature, int32_t top_k, float top_p,
+                                 uint64_t seed, int64_t* out_dev, int* out_len_host, int32_t* state_out_dev /*[B] or NULL*/,
+                                 float* logits_out_dev, pg_stream s);
+
 /* -- VQ-16 tokenizer ---------------------------------------------------------------------- */
 /* gen_vision_model.decode_code(codes, shape=[B,8,g,g]) (vq_model.py:505-508; call site
  * plangen_base.py:555): codes_dev int32 [B, g*g] -> img_out_dev [B, 3, S, S] (NCHW like the
@@ -378,6 +426,17 @@ int pg_op_sample_filter(pg_handle h, const float* logits_dev /*[B,V]*/, int B, i
 int pg_op_text_sample(pg_handle h, const float* logits_dev /*[B,V]*/, int B, int V, float temperature, int top_k,
                       float top_p, uint64_t seed, int row_offset, int step, uint8_t* keep_dev /*[B,V]*/,
                       int32_t* tok_dev /*[B]*/, pg_stream s);
+
+/* One step of pg_generate_text_constrained on caller-given rows and states (same device code; the uploaded
+ * automaton): logits_dev fp32 [B, V] (16-byte aligned), 1 <= B <= max_rows, 1 <= V <= vocab, state_dev int32 [B]
+ * (a state outside [0, n_states) allows nothing) -> tok_dev int32 [B] = the token for key (seed, row + row_offset,
+ * step), eos_id when nothing was kept; next_state_dev int32 [B] (may be state_dev); keep_dev uint8 [B, V] or NULL
+ * = 1 where the entry is allowed, above -inf and inside the top-k / top-p kept set.  temperature <= 0: masked argmax.
+ * PG_ERR_STATE without an automaton. */
+int pg_op_text_constrain(pg_handle h, const float* logits_dev /*[B,V]*/, int B, int V, const int32_t* state_dev /*[B]*/,
+                         int remaining, int eos_id, float temperature, int top_k, float top_p, uint64_t seed,
+                         int row_offset, int step, uint8_t* keep_dev /*[B,V] or NULL*/, int32_t* tok_dev /*[B]*/,
+                         int32_t* next_state_dev /*[B]*/, pg_stream s);
 
 /* The quantiser of the FP8 KV cache (the device code the decode append and the prefill conversion run; format above):
  * x_dev bf16 [n, 128] -> codes_dev uint8 [n, 128] (e4m3fn), scale_dev fp32 [n] (powers of two).  Works on any handle. */

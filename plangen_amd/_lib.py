@@ -35,6 +35,11 @@ class pg_image_u8(C.Structure):
     _fields_ = [("pix_dev", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32), ("row_stride", C.c_int64)]
 
 
+class pg_text_dfa(C.Structure):
+    _fields_ = [("token_class_host", C.c_void_p), ("next_state_host", C.c_void_p), ("dist_host", C.c_void_p),
+                ("n_states", C.c_int32), ("n_classes", C.c_int32), ("start_state", C.c_int32)]
+
+
 class pg_timing(C.Structure):
     _fields_ = [("decode_ms", C.c_float), ("attn_ms_sum", C.c_float), ("attn_launches", C.c_int32),
                 ("attn_bytes_sum", C.c_double), ("prefill_ms", C.c_float), ("vq_ms", C.c_float)]
@@ -59,6 +64,8 @@ SYMBOLS = [
     ("pg_decode_image_tokens_filtered", C.c_int, [_P, C.c_int, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_uint64, _P, _P, _P, _P, _P]),
     ("pg_generate_text_greedy", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int), _P]),
     ("pg_generate_text_sampled", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int32, C.c_float, C.c_uint64, _P, C.POINTER(C.c_int), _P, _P]),
+    ("pg_set_text_dfa", C.c_int, [_P, C.POINTER(pg_text_dfa), _P]),
+    ("pg_generate_text_constrained", C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_int32, C.c_float, C.c_uint64, _P, C.POINTER(C.c_int), _P, _P, _P]),
     ("pg_vq_decode", C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     ("pg_vq_encode", C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P]),
     ("pg_vision_encode", C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
@@ -74,6 +81,8 @@ SYMBOLS = [
     ("pg_op_uniform", C.c_int, [_P, _P, _P, C.c_int, _P]),
     ("pg_op_sample_filter", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, _P, _P]),
     ("pg_op_text_sample", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, _P, _P, _P]),
+    ("pg_op_text_constrain", C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int,
+                                       _P, _P, _P, _P]),
     ("pg_op_kv_quantize", C.c_int, [_P, _P, _P, _P, C.c_int64, _P]),
     ("pg_op_conv3x3", C.c_int, [_P, _P, _P, _P, _P, _P] + [C.c_int] * 7 + [_P]),
     ("pg_op_groupnorm", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

@@ -42,6 +42,7 @@ class PlanGenConfig:
     text_temperature: float = 0.0  # text / layout decode: 0 = greedy (the reference); > 0 samples, with text_top_k / text_top_p (extension, off by default)
     text_top_k: int = 0
     text_top_p: float = 1.0
+    layout_grammar: bool = False   # stage-1 layout decode constrained to the layout language by a token automaton (grammar.py; extension, off by default)
     seed: int = 0
     share_replicas: int = 0        # parallel_size > 1: 1 = prefill every prompt once, its replicas read its K/V (Engine.prefill_replicated); 0 = replicate the ids (extension, off by default)
     kv_dtype: str = "bf16"         # KV cache of the decode loop: 'bf16' (the compute dtype) or 'fp8' (e4m3 codes + power-of-two scales; extension, off by default)

@@ -106,6 +106,13 @@ struct pg_engine {
     float* txt_mix = nullptr;                                    // top-k / top-p text sampler: reduced logit rows [max_rows, vocab] (first filtered call)
     float* cfg_mix = nullptr;                                    // top-k / top-p sampler: CFG-mixed rows [max_rows/2, img_vocab] (first filtered call)
     SampleParams* d_sparams = nullptr; TextParams* d_tparams = nullptr;   // per-call parameters the graphs read from HBM
+    // grammar-constrained text decode (pg_set_text_dfa): device tables allocated once at the limits (first upload), so a captured step keeps
+    // valid addresses when another automaton is uploaded; pinned staging guarded by an event, like the prefill's row metadata
+    int16_t* d_dfa_class = nullptr; int16_t* d_dfa_next = nullptr; int32_t* d_dfa_dist = nullptr; TextDfaHdr* d_dfa_hdr = nullptr;
+    int32_t* d_dfa_state = nullptr;                               // [max_rows] the rows' states of the running constrained call
+    TextParams* d_op_tparams = nullptr; int32_t* d_op_step = nullptr;     // pg_op_text_constrain's parameters and step
+    unsigned char* h_dfa = nullptr; size_t h_dfa_bytes = 0; hipEvent_t ev_dfa = nullptr; bool dfa_staged = false;
+    bool dfa_set = false; int32_t dfa_dist_start = 0;
     int32_t *d_out_tok = nullptr, *d_force_tok = nullptr; uint8_t* d_force_mask = nullptr; int64_t* d_text_out = nullptr;
     int rng_image_offset = 0;                                    // pg_set_option("rng_image_offset", lo): this rank's first image in the global batch
     PgTune tune;                                                 // per-handle tuning knobs (pg_set_option)
@@ -228,8 +235,12 @@ struct pg_engine {
     int text_greedy(int max_new, int min_new, int eos, int64_t* out, int* out_len, hipStream_t s) {
         return text_generate(max_new, min_new, eos, 0.f, 0, 1.f, 0, out, out_len, nullptr, s);
     }
+    // constrained: every step's logits are masked by the automaton of set_text_dfa (min_new unused); state_out [R] or null: the final states
     int text_generate(int max_new, int min_new, int eos, float temp, int top_k, float top_p, uint64_t seed, int64_t* out, int* out_len,
-                      float* logits_out, hipStream_t s);
+                      float* logits_out, hipStream_t s, bool constrained = false, int32_t* state_out = nullptr);
+    int set_text_dfa(const pg_text_dfa* dfa, hipStream_t s);
+    int text_constrain(const float* logits, int B, int V, const int32_t* state, int remaining, int eos, float temp, int top_k, float top_p,
+                       uint64_t seed, int row_offset, int step, uint8_t* keep, int32_t* tok, int32_t* next_state, hipStream_t s);
     template <typename T> int vq_decode(const int32_t* codes, void* img_out, int out_dtype, int B, hipStream_t s);
     template <typename T> int vq_encode(const void* img, int img_dtype, int64_t* idx, int B, hipStream_t s);
     template <typename T> void conv3(hipStream_t s, const ConvW& cw, const T* in, void* out, int out_f32, const void* residual, int res_f32, int B, int Hi, int Wi, int up, int stride2, int feeds_gn = -1);

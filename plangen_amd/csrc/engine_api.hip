@@ -113,6 +113,16 @@ int pg_generate_text_sampled(pg_handle h, int max_new, int min_new, int eos_id, 
     if (!h || !out_dev) return PG_ERR_ARG;
     return h->text_generate(max_new, min_new, eos_id, temperature, top_k, top_p, seed, out_dev, out_len_host, logits_out_dev, (hipStream_t)s);
 }
+int pg_set_text_dfa(pg_handle h, const pg_text_dfa* dfa, pg_stream s) {
+    if (!h) return PG_ERR_ARG;
+    return h->set_text_dfa(dfa, (hipStream_t)s);
+}
+int pg_generate_text_constrained(pg_handle h, int max_new, int eos_id, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                                 int64_t* out_dev, int* out_len_host, int32_t* state_out_dev, float* logits_out_dev, pg_stream s) { TuneGuard _tg(h);
+    if (!h || !out_dev) return PG_ERR_ARG;
+    return h->text_generate(max_new, 0, eos_id, temperature, top_k, top_p, seed, out_dev, out_len_host, logits_out_dev, (hipStream_t)s,
+                            /*constrained*/ true, state_out_dev);
+}
 int pg_vq_decode(pg_handle h, const int32_t* codes_dev, void* img_out_dev, int out_dtype, int B, pg_stream s) { TuneGuard _tg(h);
     if (!h || !codes_dev || !img_out_dev) return PG_ERR_ARG;
     return h->bf ? h->vq_decode<bf16>(codes_dev, img_out_dev, out_dtype, B, (hipStream_t)s)
@@ -293,6 +303,13 @@ int pg_op_text_sample(pg_handle h, const float* logits_dev, int B, int V, float 
     f.keep = keep_dev; f.tok = tok_dev;
     launch_text_select((hipStream_t)s, f, B);
     return hipGetLastError() == hipSuccess ? PG_OK : PG_ERR_HIP;
+}
+int pg_op_text_constrain(pg_handle h, const float* logits_dev, int B, int V, const int32_t* state_dev, int remaining, int eos_id,
+                         float temperature, int top_k, float top_p, uint64_t seed, int row_offset, int step, uint8_t* keep_dev,
+                         int32_t* tok_dev, int32_t* next_state_dev, pg_stream s) {
+    if (!h || !logits_dev || !state_dev || !tok_dev || !next_state_dev) return PG_ERR_ARG;
+    return h->text_constrain(logits_dev, B, V, state_dev, remaining, eos_id, temperature, top_k, top_p, seed, row_offset, step, keep_dev, tok_dev,
+                             next_state_dev, (hipStream_t)s);
 }
 int pg_op_kv_quantize(pg_handle h, const void* x_dev, uint8_t* codes_dev, float* scale_dev, int64_t n, pg_stream s) {
     if (!h || !x_dev || !codes_dev || !scale_dev || n < 0) return PG_ERR_ARG;

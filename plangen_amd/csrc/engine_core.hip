@@ -381,6 +381,8 @@ void pg_engine::destroy() {
     for (int i = 0; i < 2; ++i) { if (ip_host[i]) (void)hipHostFree(ip_host[i]); if (ip_ev[i]) (void)hipEventDestroy(ip_ev[i]); }
     for (int i = 0; i < 2; ++i) { if (h_stage2[i]) (void)hipHostFree(h_stage2[i]); if (ev_stage[i]) (void)hipEventDestroy(ev_stage[i]); }
     if (h_flag) (void)hipHostFree(h_flag);
+    if (h_dfa) (void)hipHostFree(h_dfa);
+    if (ev_dfa) (void)hipEventDestroy(ev_dfa);
     for (hipEvent_t e : tc_ev) (void)hipEventDestroy(e);
     hipEvent_t evs[] = {ev_in, ev_out, ev_t0, ev_t1, ev_p0, ev_p1, ev_v0, ev_v1, ev_fork, ev_join};
     if (istream2) (void)hipStreamDestroy(istream2);

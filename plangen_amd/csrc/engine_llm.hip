@@ -473,8 +473,93 @@ int pg_engine::gen_head(const void* h_dev, int h_dtype, float* logits, int R_, h
     return PG_OK;
 }
 
+// pg_set_text_dfa: validate on the host, then stage the tables through pinned memory (no stream synchronisation: the staging buffer is
+// guarded by an event, and refilled only after the previous upload's copies have left it).
+int pg_engine::set_text_dfa(const pg_text_dfa* dfa, hipStream_t s) {
+    if (!dfa) { dfa_set = false; return PG_OK; }
+    const int ns = dfa->n_states, nc = dfa->n_classes, V = cfg.vocab;
+    if (!dfa->token_class_host || !dfa->next_state_host || !dfa->dist_host) FAIL(PG_ERR_ARG, "pg_set_text_dfa: null table");
+    if (ns < 1 || ns > TEXT_DFA_MAX_STATES || nc < 1 || nc > TEXT_DFA_MAX_CLASSES)
+        FAIL(PG_ERR_ARG, "pg_set_text_dfa: n_states=%d / n_classes=%d outside 1..%d / 1..%d", ns, nc, TEXT_DFA_MAX_STATES, TEXT_DFA_MAX_CLASSES);
+    if (dfa->start_state < 0 || dfa->start_state >= ns) FAIL(PG_ERR_ARG, "pg_set_text_dfa: start_state=%d outside [0, %d)", dfa->start_state, ns);
+    std::vector<char> used(nc, 0);
+    for (int v = 0; v < V; ++v) {
+        const int c = dfa->token_class_host[v];
+        if (c < 0 || c >= nc) FAIL(PG_ERR_ARG, "pg_set_text_dfa: token %d has class %d outside [0, %d)", v, c, nc);
+        used[c] = 1;
+    }
+    for (int st = 0; st < ns; ++st) {
+        // the builder's promise behind the budget rule: a state that can finish in dist tokens has a token that leads to dist - 1
+        const int32_t dd = dfa->dist_host[st];
+        if (dd < 0) FAIL(PG_ERR_ARG, "pg_set_text_dfa: dist[%d]=%d is negative", st, dd);
+        bool down = dd == 0 || dd >= TEXT_DFA_INF;
+        for (int c = 0; c < nc; ++c) {
+            const int nx = dfa->next_state_host[(size_t)st * nc + c];
+            if (nx < -1 || nx >= ns) FAIL(PG_ERR_ARG, "pg_set_text_dfa: next_state[%d][%d]=%d outside [-1, %d)", st, c, nx, ns);
+            if (nx >= 0 && used[c] && dfa->dist_host[nx] <= dd - 1) down = true;
+        }
+        if (!down) FAIL(PG_ERR_ARG, "pg_set_text_dfa: dist[%d]=%d but no token leads to a state with dist <= %d", st, dd, dd - 1);
+    }
+    HIPCHK(hipSetDevice(dev));
+    if (!ev_dfa) {           // first upload: the event is created last, so a failure part-way is retried from the start by the next call
+        if (!d_dfa_class) TRY(dalloc(&d_dfa_class, (size_t)V * 2 + 16));
+        if (!d_dfa_next) TRY(dalloc(&d_dfa_next, (size_t)TEXT_DFA_MAX_STATES * TEXT_DFA_MAX_CLASSES * 2));
+        if (!d_dfa_dist) TRY(dalloc(&d_dfa_dist, (size_t)TEXT_DFA_MAX_STATES * 4));
+        if (!d_dfa_hdr) TRY(dalloc(&d_dfa_hdr, 64));
+        if (!d_dfa_state) TRY(dalloc(&d_dfa_state, (size_t)cfg.max_rows * 4));
+        if (!d_op_tparams) TRY(dalloc(&d_op_tparams, 64));
+        if (!d_op_step) TRY(dalloc(&d_op_step, 64));
+        HIPCHK(hipStreamSynchronize(nullptr));               // dalloc's zero fills run on the NULL stream (this first call only)
+        HIPCHK(hipEventCreateWithFlags(&ev_dfa, hipEventDisableTiming));
+    }
+    const size_t b_cls = ((size_t)V * 2 + 15) & ~(size_t)15, b_next = (((size_t)ns * nc * 2) + 15) & ~(size_t)15, b_dist = (size_t)ns * 4;
+    const size_t need = b_cls + b_next + b_dist + sizeof(TextDfaHdr);
+    if (dfa_staged) HIPCHK(hipEventSynchronize(ev_dfa));
+    if (need > h_dfa_bytes) {
+        if (h_dfa) { (void)hipHostFree(h_dfa); h_dfa = nullptr; h_dfa_bytes = 0; }
+        HIPCHK(hipHostMalloc((void**)&h_dfa, need));
+        h_dfa_bytes = need;
+    }
+    TextDfaHdr hd{ns, nc, dfa->start_state, 0};
+    memcpy(h_dfa, dfa->token_class_host, (size_t)V * 2);
+    memcpy(h_dfa + b_cls, dfa->next_state_host, (size_t)ns * nc * 2);
+    memcpy(h_dfa + b_cls + b_next, dfa->dist_host, b_dist);
+    memcpy(h_dfa + b_cls + b_next + b_dist, &hd, sizeof hd);
+    HIPCHK(hipMemcpyAsync(d_dfa_class, h_dfa, (size_t)V * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_dfa_next, h_dfa + b_cls, (size_t)ns * nc * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_dfa_dist, h_dfa + b_cls + b_next, b_dist, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_dfa_hdr, h_dfa + b_cls + b_next + b_dist, sizeof hd, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(ev_dfa, s));
+    dfa_staged = true; dfa_set = true; dfa_dist_start = dfa->dist_host[dfa->start_state];
+    return PG_OK;
+}
+
+// pg_op_text_constrain: the scan + pick pair of the constrained loop on caller-given rows and states
+int pg_engine::text_constrain(const float* logits, int B, int V, const int32_t* state, int remaining, int eos, float temp, int top_k, float top_p,
+                              uint64_t seed, int row_offset, int step, uint8_t* keep, int32_t* tok, int32_t* next_state, hipStream_t s) {
+    if (!dfa_set) FAIL(PG_ERR_STATE, "pg_op_text_constrain: no automaton (pg_set_text_dfa)");
+    if (B < 1 || B > cfg.max_rows || V < 1 || V > cfg.vocab) FAIL(PG_ERR_ARG, "pg_op_text_constrain: needs 1 <= B <= max_rows and 1 <= V <= vocab");
+    if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f) || remaining < 0 || step < 0)
+        FAIL(PG_ERR_ARG, "pg_op_text_constrain: needs top_k >= 0, top_p in (0, 1], remaining >= 0, step >= 0");
+    if (((uintptr_t)logits & 15) || ((uintptr_t)keep & 3)) FAIL(PG_ERR_ARG, "pg_op_text_constrain: logits_dev must be 16-byte and keep_dev 4-byte aligned");
+    HIPCHK(hipSetDevice(dev));
+    const int mode = !(temp > 0.f) ? 0 : ((top_k > 0 || top_p < 1.f) ? 2 : 1);
+    if (mode == 2 && !txt_mix) { TRY(dalloc(&txt_mix, (size_t)cfg.max_rows * cfg.vocab * 4, false)); }
+    TextParams tp{}; tp.eos = eos; tp.min_new = 0; tp.max_new = remaining + step;
+    tp.temperature = temp; tp.top_k = top_k; tp.top_p = top_p; tp.seed = seed; tp.row_off = row_offset;
+    launch_set_text_op_params(s, d_op_tparams, tp, d_op_step, step);
+    TextArgs ta{};
+    ta.logits_partial = logits; ta.S = 1; ta.slab = V; ta.V = V; ta.p = d_op_tparams; ta.n_dec = d_op_step;
+    TextDfaArgs da{};
+    da.token_class = d_dfa_class; da.next_state = d_dfa_next; da.dist = d_dfa_dist; da.hdr = d_dfa_hdr;
+    da.state = state; da.state_out = next_state; da.keep = keep; da.tok = tok;
+    launch_text_constrained(s, ta, da, B, mode, cfg_pv, cfg_pi, txt_mix);
+    HIPCHK(hipGetLastError());
+    return PG_OK;
+}
+
 int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int top_k, float top_p, uint64_t seed, int64_t* out, int* out_len,
-                             float* logits_out, hipStream_t s) {
+                             float* logits_out, hipStream_t s, bool constrained, int32_t* state_out) {
     if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(PG_ERR_ARG, "top_k=%d must be >= 0 and top_p=%g in (0, 1]", top_k, (double)top_p);
     if (!prefilled) FAIL(PG_ERR_STATE, "text decode before pg_prefill");
     if (replicas_n > 1) FAIL(PG_ERR_STATE, "text decode after pg_prefill_replicated (position_mode 0, image sampling only)");
@@ -482,6 +567,10 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
     if (!cfg.with_lm_head) FAIL(PG_ERR_STATE, "engine created without lm_head");
     if (n_dec_host != 0) FAIL(PG_ERR_STATE, "text decode needs a fresh prefill");
     if (max_new < 1 || max_new > cfg.max_new || max_new > 1000) FAIL(PG_ERR_CAPACITY, "max_new=%d exceeds capacity %d", max_new, cfg.max_new);
+    if (constrained) {
+        if (!dfa_set) FAIL(PG_ERR_STATE, "constrained text decode without an automaton (pg_set_text_dfa)");
+        if (dfa_dist_start > max_new) FAIL(PG_ERR_ARG, "max_new=%d is below dist[start_state]=%d: no row could finish", max_new, dfa_dist_start);
+    }
     HIPCHK(hipSetDevice(dev));
     const int B = R;
     // launch structure: greedy argmax (temperature <= 0 ignores the filters, as HF's warpers do) / Gumbel-max folded into the scan /
@@ -511,11 +600,18 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
         tp.temperature = temp; tp.top_k = top_k; tp.top_p = top_p; tp.seed = seed; tp.row_off = rng_image_offset;
         launch_set_text_params(ws, d_tparams, tp);
     }
+    TextDfaArgs da{};
+    if (constrained) {
+        da.token_class = d_dfa_class; da.next_state = d_dfa_next; da.dist = d_dfa_dist; da.hdr = d_dfa_hdr;
+        da.state = d_dfa_state; da.state_out = d_dfa_state;
+        launch_text_dfa_reset(ws, d_dfa_state, d_dfa_hdr, B);
+    }
     auto iteration = [&](bool with_forward) {
         if (bf) gemm_llm<bf16>(ws, (const bf16*)hfin, (const bf16*)lm_head, B, cfg.vocab, H(), true, lm_head_t);
         else gemm_llm<float>(ws, (const float*)hfin, (const float*)lm_head, B, cfg.vocab, H(), true);
         ta.logits_partial = part; ta.S = S_last; ta.slab = slab_last;
-        if (mode == 2) launch_text_sample_filtered(ws, ta, B, cfg_pv, cfg_pi, txt_mix);
+        if (constrained) launch_text_constrained(ws, ta, da, B, mode, cfg_pv, cfg_pi, txt_mix);
+        else if (mode == 2) launch_text_sample_filtered(ws, ta, B, cfg_pv, cfg_pi, txt_mix);
         else if (mode == 1) launch_text_sample(ws, ta, B, cfg_pv, cfg_pi);
         else launch_text_argmax(ws, ta, B, cfg_pv, cfg_pi);
         if (with_forward) forward_decode(ws);
@@ -525,7 +621,7 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
         if (use_graph && !last && step_i > 0) {
             // shapes and kernel selection only: temperature, top_k, top_p, seed and the row offset reach the kernels through TextParams
             std::vector<int64_t> key = {R, (int64_t)bf, (int64_t)fuse_rope, (int64_t)shared_len, (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch,
-                                        (int64_t)mode, (int64_t)logits_out};
+                                        (int64_t)mode, (int64_t)logits_out, (int64_t)constrained};
             if (!gexec_txt || key != gkey_txt) {
                 if (gexec_txt) { (void)hipGraphExecDestroy(gexec_txt); gexec_txt = nullptr; }
                 hipGraph_t g = nullptr;
@@ -552,6 +648,7 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
     if (done_len < 0) done_len = max_new;
     // only the columns this call produced; the caller's buffer keeps its own fill beyond them
     HIPCHK(hipMemcpy2DAsync(out, (size_t)max_new * 8, d_text_out, (size_t)max_new * 8, (size_t)done_len * 8, B, hipMemcpyDeviceToDevice, ws));
+    if (constrained && state_out) HIPCHK(hipMemcpyAsync(state_out, d_dfa_state, (size_t)B * 4, hipMemcpyDeviceToDevice, ws));
     if (ws != s) {
         HIPCHK(hipEventRecord(ev_out, ws));
         HIPCHK(hipStreamWaitEvent(s, ev_out, 0));

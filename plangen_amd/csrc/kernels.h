@@ -257,6 +257,28 @@ struct TextSelectArgs {
 };
 void launch_text_sample_filtered(hipStream_t s, const TextArgs& a, int B, float* scratch_v, int* scratch_i, float* mix);
 void launch_text_select(hipStream_t s, const TextSelectArgs& f, int B);
+// grammar-constrained text decode (pg_set_text_dfa): a token v is allowed in state st iff nx = next_state[st][token_class[v]] >= 0 and
+// dist[nx] <= remaining - 1 (remaining = p->max_new - step).  The scan reads the row's state, folds both clauses into one bit per class
+// in LDS and turns every disallowed logit into -inf where the EOS ban is applied; the pick emits eos when nothing was kept and moves the
+// state.  The tables live in buffers allocated once at the limits: a captured step keeps valid addresses across uploads.
+#define TEXT_DFA_MAX_STATES 4096
+#define TEXT_DFA_MAX_CLASSES 1024
+#define TEXT_DFA_INF (1 << 30)
+struct TextDfaHdr { int32_t n_states, n_classes, start_state, pad; };
+struct TextDfaArgs {
+    const int16_t* token_class;                                   // [vocab]
+    const int16_t* next_state;                                    // [n_states, n_classes]
+    const int32_t* dist;                                          // [n_states]
+    const TextDfaHdr* hdr;
+    const int32_t* state;                                         // [B] the rows' states at this step
+    int32_t* state_out;                                           // [B] loop: == state; operator: the caller's next_state_dev
+    uint8_t* keep;                                                // operator: [B, V] kept mask or null
+    int32_t* tok;                                                 // operator: [B] the token (non-null selects the operator form of the pick)
+};
+void launch_text_dfa_reset(hipStream_t s, int32_t* state, const TextDfaHdr* hdr, int B);
+void launch_set_text_op_params(hipStream_t s, TextParams* dst, TextParams v, int32_t* step_dst, int step);
+// mode: 0 greedy, 1 Gumbel-max in the scan, 2 scan -> mix -> text_select_kernel (as pg_engine::text_generate picks them)
+void launch_text_constrained(hipStream_t s, const TextArgs& a, const TextDfaArgs& d, int B, int mode, float* scratch_v, int* scratch_i, float* mix);
 void launch_advance(hipStream_t s, int32_t* n_dec);
 void launch_rows_differ(hipStream_t s, const int32_t* ids, int L, int first, int stride, int ref, int n, int from, int32_t* flag);
 void launch_uniform_from_bits(hipStream_t s, const uint64_t* z, float* out, int n);

@@ -806,87 +806,26 @@ void launch_sample_filter(hipStream_t s, const float* rows, int B, int V, float 
 // MODE: TEXT_GREEDY (the argmax, as before), TEXT_SAMPLE (every logit perturbed by gumbel_perturb with p->temperature / seed / row_off: no extra
 // pass), TEXT_STORE (filtered sampler: the reduced row, EOS suppression applied, goes to mix [B, V]; the winners are the chunk MAXIMA of the
 // unperturbed row, which text_select_kernel reads as the softmax shift).  TAP: also write the row to logits_out [max_new, B, V].
+// DFA (pg_generate_text_constrained; rule: kernels.h TextDfaArgs): the block first folds its row's state into one "allowed" bit per token
+// class -- 1024 bits = 32 LDS dwords, one per bank, so the lookups of a wave never conflict whatever classes its tokens have (a byte or
+// int16 per class spreads 1024 classes over 8-16 dwords per bank) -- and each 16-byte logit load gets one 8-byte load of the four tokens'
+// classes issued beside it (token_class: 200 KiB shared by every row, L2 resident).  A disallowed entry becomes -inf where the EOS ban is
+// applied, so the tap, the TEXT_STORE row and text_select_kernel carry it without a change.
 enum { TEXT_GREEDY = 0, TEXT_SAMPLE = 1, TEXT_STORE = 2 };
+// One body, two kernels (text_scan_body.h is included in each): text_scan_kernel is the kernel it was, text_scan_dfa_kernel takes the
+// automaton as well.  A shared __device__ function would do, but it changes the unconstrained kernels' register allocation; this way
+// their instruction streams are unchanged (compared with llvm-objdump against the build before the DFA parameter existed).
 template <int MODE, bool TAP>
 __global__ __launch_bounds__(256) void text_scan_kernel(TextArgs a, float* __restrict__ pv, int* __restrict__ pi, float* __restrict__ mix) {
-    __shared__ float sv[4]; __shared__ int si[4];
-    const int ch = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, step = *a.n_dec;
-    const int ban = step < a.p->min_new ? a.p->eos : -1;
-    const int chunk = ((a.V + CFG_CHUNKS * 4 - 1) / (CFG_CHUNKS * 4)) * 4;
-    const int v0 = ch * chunk, v1 = v0 + chunk < a.V ? v0 + chunk : a.V;
-    const float* lp = a.logits_partial + (long)b * a.V;
-    float best = -INFINITY; int bi = 0x7fffffff;
-    float invT = 1.f; uint64_t seed = 0, stream = 0;
-    if (MODE == TEXT_SAMPLE) {
-        invT = 1.f / a.p->temperature; seed = a.p->seed;
-        stream = (uint64_t)(b + a.p->row_off) * 1000003ull + step;
-    }
-    float* tap = TAP ? a.logits_out + ((long)step * gridDim.y + b) * a.V : nullptr;
-    float* mrow = MODE == TEXT_STORE ? mix + (long)b * a.V : nullptr;
-    if (((a.V | (int)(a.slab & 3)) & 3) == 0) {
-        // eight independent 16-byte loads per slab in flight per thread (addresses clamped into the chunk, validity applied to the
-        // compare): a plain `for v` / `for s` nest is one dependent round trip per vector and slab
-        constexpr int IT = 8;
-        for (int vb = v0 + tid * 4; vb < v1; vb += IT * 1024) {
-            f32x4 c[IT];
-#pragma unroll
-            for (int it = 0; it < IT; ++it) {
-                const int v = vb + it * 1024;
-                c[it] = *(const f32x4*)(lp + (v < v1 ? v : v1 - 4));
-            }
-            for (int s = 1; s < a.S; ++s) {
-                f32x4 t[IT];
-#pragma unroll
-                for (int it = 0; it < IT; ++it) {
-                    const int v = vb + it * 1024;
-                    t[it] = *(const f32x4*)(lp + (long)s * a.slab + (v < v1 ? v : v1 - 4));
-                }
-#pragma unroll
-                for (int it = 0; it < IT; ++it) c[it] += t[it];
-            }
-#pragma unroll
-            for (int it = 0; it < IT; ++it) {
-                const int v = vb + it * 1024;
-                if (MODE == TEXT_STORE || TAP) {
-                    if (v < v1) {                                  // V % 4 == 0: a vector is wholly inside the chunk or wholly outside
-                        f32x4 w = c[it];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) if (v + j == ban) w[j] = -INFINITY;
-                        if (TAP) *(f32x4*)(tap + v) = w;
-                        if (MODE == TEXT_STORE) *(f32x4*)(mrow + v) = w;
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float cj = (v + j == ban || v >= v1) ? -INFINITY : c[it][j];
-                    if (MODE == TEXT_SAMPLE && v < v1) cj = gumbel_perturb(cj, invT, seed, stream, v + j);
-                    if (cj > best) { best = cj; bi = v + j; }
-                }
-            }
-        }
-    } else {
-        for (int v = v0 + tid; v < v1; v += 256) {
-            float c = 0.f;
-            for (int s = 0; s < a.S; ++s) c += lp[(long)s * a.slab + v];
-            if (v == ban) c = -INFINITY;
-            if (TAP) tap[v] = c;
-            if (MODE == TEXT_STORE) mrow[v] = c;
-            if (MODE == TEXT_SAMPLE) c = gumbel_perturb(c, invT, seed, stream, v);
-            if (c > best) { best = c; bi = v; }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-        argmax_combine(best, bi, ov, oi);
-    }
-    if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-        float v = sv[0]; int i = si[0];
-        for (int k = 1; k < 4; ++k) argmax_combine(v, i, sv[k], si[k]);
-        pv[b * CFG_CHUNKS + ch] = v; pi[b * CFG_CHUNKS + ch] = i;
-    }
+    constexpr bool DFA = MODE < 0;                      // always false; dependent, so `if constexpr (DFA)` discards its branch
+    [[maybe_unused]] const TextDfaArgs* d = nullptr;
+#include "text_scan_body.h"
+}
+template <int MODE, bool TAP>
+__global__ __launch_bounds__(256) void text_scan_dfa_kernel(TextArgs a, float* __restrict__ pv, int* __restrict__ pi, float* __restrict__ mix, TextDfaArgs dfa) {
+    constexpr bool DFA = MODE >= 0;                     // always true
+    const TextDfaArgs* d = &dfa;
+#include "text_scan_body.h"
 }
 __global__ __launch_bounds__(256) void text_argmax_kernel(TextArgs a, const float* __restrict__ pv, const int* __restrict__ pi) {
     __shared__ int s_tok;
@@ -909,10 +848,61 @@ __global__ __launch_bounds__(256) void text_argmax_kernel(TextArgs a, const floa
     float* x0 = a.x + (long)b * a.H;
     for (int i = tid * 4; i < a.H; i += 1024) *(f32x4*)(x0 + i) = *(const f32x4*)(src + i);
 }
+// The constrained pick: text_argmax_kernel with two differences.  Nothing kept (every allowed logit -inf / NaN) emits eos and finishes the
+// row -- token 0 could lie outside the language -- and an unfinished row's state moves along its token (it stays where it is when nothing
+// was kept, and for finished rows).  d.tok != null is the operator form: token and next state out, no loop bookkeeping, no embedding.
+__global__ __launch_bounds__(256) void text_pick_dfa_kernel(TextArgs a, TextDfaArgs d, const float* __restrict__ pv, const int* __restrict__ pi) {
+    __shared__ int s_tok;
+    const int b = blockIdx.x, tid = threadIdx.x, step = *a.n_dec;
+    if (tid == 0) {
+        const int eos = a.p->eos, max_new = a.p->max_new;
+        float v = pv[b * CFG_CHUNKS]; int i = pi[b * CFG_CHUNKS];
+        for (int k = 1; k < CFG_CHUNKS; ++k) argmax_combine(v, i, pv[b * CFG_CHUNKS + k], pi[b * CFG_CHUNKS + k]);
+        const bool none = i == 0x7fffffff || i < 0 || i >= a.V;
+        const int unf = d.tok ? 1 : a.unfinished[b];
+        const int tok = (unf && !none) ? i : eos;
+        const int st = d.state[b], ncl = d.hdr->n_classes;
+        int ns = st;
+        if (unf && !none && st >= 0 && st < d.hdr->n_states) {
+            const int nx = d.next_state[(long)st * ncl + ((uint16_t)d.token_class[i] & (TEXT_DFA_MAX_CLASSES - 1))];
+            if (nx >= 0) ns = nx;
+        }
+        d.state_out[b] = ns;
+        if (d.tok) { d.tok[b] = tok; s_tok = -1; }
+        else {
+            if (step < max_new) a.out[(long)b * max_new + step] = tok;
+            const int still = unf && (tok != eos);
+            a.unfinished[b] = still;
+            if (still) atomicOr(a.any_unfinished + ((step + 1) & 1023), 1);
+            s_tok = tok < 0 ? 0 : (tok >= a.V ? a.V - 1 : tok);
+        }
+    }
+    __syncthreads();
+    if (s_tok < 0) return;
+    const float* src = a.embed_table + (long)s_tok * a.H;
+    float* x0 = a.x + (long)b * a.H;
+    for (int i = tid * 4; i < a.H; i += 1024) *(f32x4*)(x0 + i) = *(const f32x4*)(src + i);
+}
+__global__ void text_dfa_reset_kernel(int32_t* __restrict__ state, const TextDfaHdr* __restrict__ hdr, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) state[b] = hdr->start_state;
+}
+void launch_text_dfa_reset(hipStream_t s, int32_t* state, const TextDfaHdr* hdr, int B) {
+    hipLaunchKernelGGL(text_dfa_reset_kernel, dim3((B + 255) / 256), dim3(256), 0, s, state, hdr, B);
+}
+__global__ void set_text_op_params_kernel(TextParams* dst, TextParams v, int32_t* step_dst, int step) { *dst = v; *step_dst = step; }
+void launch_set_text_op_params(hipStream_t s, TextParams* dst, TextParams v, int32_t* step_dst, int step) {
+    hipLaunchKernelGGL(set_text_op_params_kernel, dim3(1), dim3(1), 0, s, dst, v, step_dst, step);
+}
 template <int MODE>
 static void launch_text_scan(hipStream_t s, const TextArgs& a, int B, float* scratch_v, int* scratch_i, float* mix) {
     if (a.logits_out) hipLaunchKernelGGL((text_scan_kernel<MODE, true>), dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i, mix);
     else hipLaunchKernelGGL((text_scan_kernel<MODE, false>), dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i, mix);
+}
+template <int MODE>
+static void launch_text_scan_dfa(hipStream_t s, const TextArgs& a, const TextDfaArgs& d, int B, float* scratch_v, int* scratch_i, float* mix) {
+    if (a.logits_out) hipLaunchKernelGGL((text_scan_dfa_kernel<MODE, true>), dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i, mix, d);
+    else hipLaunchKernelGGL((text_scan_dfa_kernel<MODE, false>), dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i, mix, d);
 }
 void launch_text_argmax(hipStream_t s, const TextArgs& a, int B, float* scratch_v, int* scratch_i) {
     launch_text_scan<TEXT_GREEDY>(s, a, B, scratch_v, scratch_i, nullptr);
@@ -1209,6 +1199,16 @@ void launch_text_sample_filtered(hipStream_t s, const TextArgs& a, int B, float*
     f.rows = mix; f.V = a.V; f.chunk_max = scratch_v; f.p = a.p; f.n_dec = a.n_dec; f.pv = scratch_v; f.pi = scratch_i;
     launch_text_select(s, f, B);
     hipLaunchKernelGGL(text_argmax_kernel, dim3(B), dim3(256), 0, s, a, scratch_v, scratch_i);
+}
+void launch_text_constrained(hipStream_t s, const TextArgs& a, const TextDfaArgs& d, int B, int mode, float* scratch_v, int* scratch_i, float* mix) {
+    if (mode == 2) {
+        launch_text_scan_dfa<TEXT_STORE>(s, a, d, B, scratch_v, scratch_i, mix);
+        TextSelectArgs f{};
+        f.rows = mix; f.V = a.V; f.chunk_max = scratch_v; f.p = a.p; f.n_dec = a.n_dec; f.pv = scratch_v; f.pi = scratch_i; f.keep = d.keep;
+        launch_text_select(s, f, B);
+    } else if (mode == 1) launch_text_scan_dfa<TEXT_SAMPLE>(s, a, d, B, scratch_v, scratch_i, mix);
+    else launch_text_scan_dfa<TEXT_GREEDY>(s, a, d, B, scratch_v, scratch_i, mix);
+    hipLaunchKernelGGL(text_pick_dfa_kernel, dim3(B), dim3(256), 0, s, a, d, scratch_v, scratch_i);
 }
 
 // test tap: the sampler's uniform / Gumbel transform of raw 64-bit RNG outputs: out[i] = u, out[n+i] = -log(-log(u))

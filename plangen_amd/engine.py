@@ -455,6 +455,43 @@ class Engine:
         self._keep = [out, lg]
         return (out[:, :n.value], lg[:n.value]) if return_logits else out[:, :n.value]
 
+    def set_text_dfa(self, dfa) -> None:
+        """pg_set_text_dfa: upload a token automaton (``grammar.TokenDFA`` or anything with ``token_class`` [vocab], ``next_state``
+        [n_states, n_classes], ``dist`` [n_states], ``start_state``) for ``generate_text_constrained`` / ``text_constrain``; None forgets it.
+        The tables are validated and copied inside the call.  ``uploaded_dfa`` remembers the object, so that callers which pass the same
+        cached automaton again (``language_model.generate(dfa=)``) can skip the upload."""
+        self.uploaded_dfa = None
+        if dfa is None:
+            self._check(self.lib.pg_set_text_dfa(self.h, None, self.stream), "pg_set_text_dfa")
+            return
+        import numpy as np
+        cls = np.ascontiguousarray(dfa.token_class, dtype=np.int16).reshape(-1)
+        nxt = np.ascontiguousarray(dfa.next_state, dtype=np.int16)
+        dist = np.ascontiguousarray(dfa.dist, dtype=np.int32).reshape(-1)
+        if cls.shape[0] != self.cfg.vocab or nxt.ndim != 2 or dist.shape[0] != nxt.shape[0]:
+            raise PlanGenError(f"set_text_dfa: token_class {cls.shape} must be [vocab={self.cfg.vocab}], next_state {nxt.shape} "
+                               f"[n_states, n_classes], dist {dist.shape} [n_states]")
+        d = _lib.pg_text_dfa(cls.ctypes.data, nxt.ctypes.data, dist.ctypes.data, nxt.shape[0], nxt.shape[1], int(dfa.start_state))
+        self._check(self.lib.pg_set_text_dfa(self.h, C.byref(d), self.stream), "pg_set_text_dfa")
+        self.uploaded_dfa = dfa
+
+    def generate_text_constrained(self, max_new_tokens: int, eos_id: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
+                                  seed: int = 0, return_logits: bool = False, return_state: bool = False):
+        """``generate_text`` under the automaton of ``set_text_dfa``: disallowed tokens are -inf before temperature / top-k / top-p, a row
+        only moves to states it can still finish from, so every row ends with eos inside ``max_new_tokens`` (needs dist[start] <=
+        max_new_tokens).  return_logits: also the masked rows fp32 [n, R, vocab]; return_state: also the final states int32 [R].
+        Semantics: include/plangen_hip.h."""
+        out = torch.full((self.R, max_new_tokens), eos_id, dtype=torch.int64, device=self.device)
+        lg = torch.zeros((max_new_tokens, self.R, self.cfg.vocab), dtype=torch.float32, device=self.device) if return_logits else None
+        st = torch.full((self.R,), -1, dtype=torch.int32, device=self.device) if return_state else None
+        n = C.c_int(0)
+        self._check(self.lib.pg_generate_text_constrained(self.h, max_new_tokens, eos_id, float(temperature), int(top_k), float(top_p),
+                                                          int(seed), self._p(out), C.byref(n), self._p(st), self._p(lg), self.stream),
+                    "pg_generate_text_constrained")
+        self._keep = [out, lg, st]
+        res = (out[:, :n.value],) + ((lg[:n.value],) if return_logits else ()) + ((st,) if return_state else ())
+        return res if len(res) > 1 else res[0]
+
     def generate_text_greedy(self, max_new_tokens: int, eos_id: int, min_new_tokens: int = 0) -> torch.Tensor:
         out = torch.full((self.R, max_new_tokens), eos_id, dtype=torch.int64, device=self.device)
         n = C.c_int(0)
@@ -621,6 +658,22 @@ class Engine:
                                                int(row_offset), int(step), self._p(keep), self._p(tok), self.stream), "pg_op_text_sample")
         self._keep = [x, keep, tok]
         return keep.bool(), tok
+
+    def text_constrain(self, logits: torch.Tensor, state, remaining: int, eos_id: int, temperature: float = 0.0, top_k: int = 0,
+                       top_p: float = 1.0, seed: int = 0, row_offset: int = 0, step: int = 0):
+        """pg_op_text_constrain: one constrained step over fp32 rows ``logits`` [B, V], V <= vocab, in the states ``state`` [B] ->
+        (kept mask bool [B, V], token int32 [B], next state int32 [B])."""
+        x = self._dev(logits, torch.float32).reshape(-1, logits.shape[-1]).contiguous()
+        B, V = x.shape
+        st = self._dev(torch.as_tensor(state), torch.int32).reshape(-1).contiguous()
+        keep = torch.zeros((B, V), dtype=torch.uint8, device=self.device)
+        tok = torch.full((B,), -1, dtype=torch.int32, device=self.device)
+        nxt = torch.full((B,), -1, dtype=torch.int32, device=self.device)
+        self._check(self.lib.pg_op_text_constrain(self.h, self._p(x), B, V, self._p(st), int(remaining), int(eos_id), float(temperature),
+                                                  int(top_k), float(top_p), int(seed), int(row_offset), int(step), self._p(keep),
+                                                  self._p(tok), self._p(nxt), self.stream), "pg_op_text_constrain")
+        self._keep = [x, st, keep, tok, nxt]
+        return keep.bool(), tok, nxt
 
     def op_conv3x3(self, x_nhwc: torch.Tensor, w_oihw: torch.Tensor, bias: torch.Tensor, residual=None, up: int = 0,
                    stride2: int = 0) -> torch.Tensor:

@@ -258,7 +258,15 @@ class System:
                 ids1 = batch["uni_stage1_inputs_ids"].to(dev)
                 attention_mask = batch["uni_stage1_attention_mask"]
                 emb = self.vl_gpt.language_model.get_input_embeddings()(ids1)
-            outputs = self.x2t(emb, attention_mask.to(dev), max_new_tokens=max_new_tokens, min_new_tokens=min_new_tokens)
+            dfa = None
+            if not is_mmu and getattr(self.args, "layout_grammar", False):
+                # the layout string only: mmu captions stay free text
+                if self.codec is None:
+                    raise PlanGenError("layout_grammar needs a tokenizer (System(codec=...)): the automaton is built over its vocabulary")
+                from .grammar import layout_token_dfa
+                dfa = layout_token_dfa(self.codec, self.cfg.vocab)
+            outputs = self.x2t(emb, attention_mask.to(dev), max_new_tokens=max_new_tokens, min_new_tokens=min_new_tokens,
+                               **({} if dfa is None else {"dfa": dfa}))
             out["pr_text_ids" if is_mmu else "pr_layout_ids"] = outputs
             rows = outputs.cpu().tolist()
             if self.codec is not None:
@@ -314,11 +322,12 @@ class System:
     @torch.no_grad()
     def x2t(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
             max_new_tokens: int = 512, min_new_tokens: int = 0, temperature: Optional[float] = None,
-            top_k: Optional[int] = None, top_p: Optional[float] = None) -> torch.Tensor:
+            top_k: Optional[int] = None, top_p: Optional[float] = None, dfa=None) -> torch.Tensor:
         """System.x2t (:513-523): text / layout-token decode.  Greedy like the reference unless ``text_temperature`` > 0 (argument,
         else self.args, else 0): then every row is sampled with ``text_top_k`` / ``text_top_p`` (HF order temperature -> top-k -> top-p)
         from seed = args.seed, the seed t2i uses.  The draw is keyed on the row's index in the batch, so two rows that carry the same
-        prompt get different layouts: repeat a caption N times in one batch for N layouts of it."""
+        prompt get different layouts: repeat a caption N times in one batch for N layouts of it.
+        ``dfa`` (grammar.TokenDFA): the decode is constrained to the automaton's language, greedy or sampled (``layout_grammar``)."""
         a = self.args
         temperature = float(getattr(a, "text_temperature", 0.0)) if temperature is None else float(temperature)
         top_k = int(getattr(a, "text_top_k", 0)) if top_k is None else int(top_k)
@@ -326,6 +335,8 @@ class System:
         kw = dict(do_sample=False)
         if temperature > 0:
             kw = dict(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, seed=int(getattr(a, "seed", 0)))
+        if dfa is not None:
+            kw["dfa"] = dfa
         return self.vl_gpt.language_model.generate(inputs_embeds=inputs_embeds, attention_mask=attention_mask,
                                                    pad_token_id=self.cfg.eos_id, bos_token_id=None,
                                                    eos_token_id=self.cfg.eos_id, max_new_tokens=max_new_tokens,

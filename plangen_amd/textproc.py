@@ -159,6 +159,17 @@ class HFCodec:
     def decode(self, ids: Sequence[int]) -> str:
         return self.tok.decode(list(ids), skip_special_tokens=False)     # plangen_base.py:294
 
+    def token_strings(self, vocab: int) -> List[Optional[str]]:
+        """The string every id decodes to on its own (grammar.compile_token_dfa); None for the model's ids past the tokenizer's and
+        for byte-level pieces that are not valid UTF-8 alone (they decode to U+FFFD: what they spell depends on their neighbours, so
+        the automaton allows them nowhere)."""
+        n = len(self.tok)
+        out: List[Optional[str]] = []
+        for i in range(vocab):
+            s = self.tok.decode([i], skip_special_tokens=False) if i < n else None
+            out.append(None if s is not None and "\ufffd" in s else s)
+        return out
+
 
 class TagWordCodec:
     """Reversible offline vocabulary: special tags, ``<...>`` tags, digits, punctuation, newline runs and words
@@ -197,3 +208,10 @@ class TagWordCodec:
 
     def decode(self, ids: Sequence[int]) -> str:
         return "".join(self._i2t.get(int(i), "") for i in ids)
+
+    def token_strings(self, vocab: int) -> List[Optional[str]]:
+        """The table as it stands (grammar.compile_token_dfa); None for ids not yet assigned."""
+        return [self._i2t.get(i) for i in range(vocab)]
+
+    def token_table_version(self) -> int:
+        return len(self._i2t)                             # words are added on first sight: a cached automaton is stale after that

@@ -15,6 +15,7 @@ top_p = 1.0                            # top-p (nucleus) filtering of sampled im
 text_temperature = 0.0                 # layout / caption decode (x2t): 0 = greedy like the reference; > 0 samples (an extension beyond the reference)
 text_top_k = 0                         # top-k filtering of sampled text tokens (0: off)
 text_top_p = 1.0                       # top-p (nucleus) filtering of sampled text tokens (1.0: off)
+layout_grammar = False                 # True: the stage-1 layout decode (uni_2stage, plan) can only emit a well-formed layout string that ends inside max_new_tokens (an extension beyond the reference)
 kv_dtype = 'bf16'                      # KV cache: 'bf16' = the compute dtype; 'fp8' = e4m3 codes + power-of-two scales (about half the cache bytes; an extension beyond the reference)
 share_replicas = 0                     # parallel_size > 1: 1 = prefill every prompt once and let its replicas read its K/V in the decode loop (same tokens; an extension beyond the reference)
 use_teacher_forcing = False            # base.py:36

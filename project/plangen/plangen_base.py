@@ -55,6 +55,7 @@ class System(_HotPath):
         cfg.top_k, cfg.top_p = int(getattr(args, "top_k", 0)), float(getattr(args, "top_p", 1.0))
         cfg.text_temperature = float(getattr(args, "text_temperature", 0.0))
         cfg.text_top_k, cfg.text_top_p = int(getattr(args, "text_top_k", 0)), float(getattr(args, "text_top_p", 1.0))
+        cfg.layout_grammar = bool(getattr(args, "layout_grammar", False))
         cfg.kv_dtype = str(getattr(args, "kv_dtype", "bf16"))
         cfg.share_replicas = int(getattr(args, "share_replicas", 0))
         bs = int(args.test_batch_size)
@@ -78,6 +79,7 @@ class System(_HotPath):
         super().__init__(cfg, eng, SimpleNamespace(seed=args.seed, parallel_size=args.parallel_size, cfg_weight=args.cfg_weight,
                                                    temperature=args.temperature, top_k=cfg.top_k, top_p=cfg.top_p,
                                                    text_temperature=cfg.text_temperature, text_top_k=cfg.text_top_k, text_top_p=cfg.text_top_p,
+                                                   layout_grammar=cfg.layout_grammar,
                                                    use_teacher_forcing=args.use_teacher_forcing, share_replicas=cfg.share_replicas,
                                                    debug_max_seq_len=args.debug_max_seq_len, janus_hw=args.janus_hw,
                                                    neg_prompt=getattr(args, "neg_prompt", ""),
