@@ -1,9 +1,11 @@
-// libplangen_diag.so only: operator entry points of the attention kernels (tests/test_gpu_attention.py) and of the decode step's deferred-RMSNorm
-// pair and slab-folding elementwise kernels (tests/test_gpu_decode_ops.py) for the operator tests.  Each one points
-// the calling thread's pg_tune at a local PgTune (no diagnostics hooks, one kernel-form selector set), calls the PRODUCTION launcher and restores
+// libplangen_diag.so only: operator entry points of the attention kernels (tests/test_gpu_attention.py), of the decode step's deferred-RMSNorm
+// pair and slab-folding elementwise kernels (tests/test_gpu_decode_ops.py), of the VQ-16 decoder kernels (tests/test_gpu_vq_ops.py) and of the prefill
+// GEMM epilogues -- RoPE + KV write (act 3), SwiGLU (act 2), rope_kv_kernel alone and the two weight interleavers (tests/test_gpu_prefill_ops.py) -- for
+// the operator tests.  Each one points the calling thread's pg_tune at a local PgTune (no diagnostics hooks, one kernel-form selector set), calls the PRODUCTION launcher and restores
 // pg_tune.  Shapes the kernels do not support are refused with PG_ERR_ARG and never launched.  Head dimension: 128 for the LLM kernels (implied
 // by the [.., nh * 128] layouts), 64 for SigLIP (C / NH).  Row lengths, slots and token maps live in device memory; they are copied back and
 // checked on the host before anything is launched (these are test entry points: the synchronisation does not matter).
+#include <initializer_list>
 #include <type_traits>
 #include <vector>
 #include "kernels.h"
@@ -471,6 +473,159 @@ int pg_diag_op_vq_gather(int is_bf16, const void* table, const int32_t* codes, v
     const hipStream_t s = (hipStream_t)stream;
     if (is_bf16) launch_vq_gather<bf16>(s, (const bf16*)table, codes, (bf16*)out, n, C, vocab);
     else launch_vq_gather<float>(s, (const float*)table, codes, (float*)out, n, C, vocab);
+    return finish(s);
+}
+
+// ------------------------------------------------------------------------------------------------ prefill GEMM epilogues (tests/test_gpu_prefill_ops.py)
+// Every entry point below synchronises the stream before it returns.
+}  // extern "C"
+namespace {
+bool opt256_ok(int o) { return o == 1 || o == 4 || o == 5 || o == 6 || o == 12 || o == 13 || o == 14; }      // gemm256.hip pick_tile_height: auto, 256 / 224 / 192 rows, + 8 = four phases
+bool aligned16(std::initializer_list<const void*> ps) {
+    uintptr_t a = 0;
+    for (const void* p : ps) a |= (uintptr_t)p;
+    return (a & 15) == 0;
+}
+// Token map of a RoPE + KV write: token m -> (row[m], slot[m]).  rows inside [0, R), slots >= 0, pos_off inside [0, max_pos), no cache slot with two owners
+// (the kernels' stores would race).  slot >= slots is what the kernels' capacity guard is for and is ALLOWED -- but only below 2 * slots and in a row that is
+// not the last one, so that even a kernel without the guard writes inside the caches [R][nh][slots][128], where the callers' sentinel screen sees it.
+int screen_token_map(const std::vector<int32_t>& row, const std::vector<int32_t>& slot, const std::vector<int32_t>& pos, int M, int R, int slots, int max_pos) {
+    for (int r = 0; r < R; ++r)
+        if (pos[r] < 0 || pos[r] >= max_pos) return PG_ERR_ARG;
+    std::vector<char> owned((size_t)R * slots, 0);
+    for (int m = 0; m < M; ++m) {
+        if (row[m] < 0 || row[m] >= R || slot[m] < 0) return PG_ERR_ARG;
+        if (slot[m] >= slots) {
+            if (row[m] == R - 1 || slot[m] >= 2L * slots) return PG_ERR_ARG;
+            continue;
+        }
+        char& o = owned[(size_t)row[m] * slots + slot[m]];
+        if (o) return PG_ERR_ARG;
+        o = 1;
+    }
+    return PG_OK;
+}
+struct Scratch {
+    void* p = nullptr;
+    bool get(size_t bytes) { return hipMalloc(&p, bytes) == hipSuccess; }
+    ~Scratch() { if (p) (void)hipFree(p); }
+};
+}  // namespace
+extern "C" {
+
+// Prefill QKV projection + RoPE + KV write.  xn bf16 [M][K], Wqkv bf16 [3 * nh * 128][K] row-major and UN-interleaved; qbuf bf16 [M][nh * 128], kc / vc bf16
+// [R][nh][slots][128], cos_t / sin_t fp32 [max_pos][64], tok_row / tok_j [M] and pos_off [R] device.  form 0: launch_interleave_qk into scratch, then gemm256_try
+// with act = 3 as run_layers calls it, pg_tune->gemm256 = gemm256_opt (1, 4, 5, 6, 12, 13, 14 and nothing else); PG_ERR_ARG when gemm256_try declines the shape.
+// form 1: the engine's unfused path, launch_gemm<bf16> -> fp32 [M][3 * nh * 128] on the un-interleaved weights (gemm256_opt as above, or 0 = the 128 x 128
+// kernel), then launch_rope_kv<bf16> mode 1 with S = 1.
+int pg_diag_op_qkv_rope(int form, int gemm256_opt, const void* xn, const void* Wqkv, void* qbuf, void* kc, void* vc, const float* cos_t, const float* sin_t,
+                        const int32_t* tok_row, const int32_t* tok_j, const int32_t* pos_off, int M, int nh, int K, int R, int slots, int max_pos,
+                        pg_stream stream) {
+    if (!xn || !Wqkv || !qbuf || !kc || !vc || !cos_t || !sin_t || !tok_row || !tok_j || !pos_off) return PG_ERR_ARG;
+    if ((form != 0 && form != 1) || !(opt256_ok(gemm256_opt) || (form == 1 && gemm256_opt == 0))) return PG_ERR_ARG;
+    if (M < 1 || nh < 1 || nh > 1024 || K < 128 || K % 64 || R < 1 || slots < 1 || max_pos < 1) return PG_ERR_ARG;
+    const long N = 3L * nh * 128;
+    if ((long)M * N >= (1L << 31) || N * K >= (1L << 31) || (long)R * slots > (1L << 28) || (long)R * nh * slots * 128 >= (1L << 40)) return PG_ERR_ARG;
+    if (!aligned16({xn, Wqkv, qbuf, kc, vc, cos_t, sin_t, tok_row, tok_j, pos_off})) return PG_ERR_ARG;
+    std::vector<int32_t> hrow, hj, hpos;
+    if (!to_host(hrow, tok_row, M) || !to_host(hj, tok_j, M) || !to_host(hpos, pos_off, R)) return PG_ERR_HIP;
+    const int sc = screen_token_map(hrow, hj, hpos, M, R, slots, max_pos);
+    if (sc != PG_OK) return sc;
+    LocalTune lt;
+    lt.t.gemm256 = gemm256_opt;
+    const hipStream_t s = (hipStream_t)stream;
+    Scratch tmp;
+    GemmA ga; ga.ptr = xn; ga.lda = K;
+    if (form == 0) {
+        if (!tmp.get((size_t)N * K * 2)) return PG_ERR_HIP;
+        launch_interleave_qk(s, (const bf16*)Wqkv, (bf16*)tmp.p, nh, K);
+        GemmEpi ge; ge.act = 3; ge.out = qbuf; ge.out_f32 = 0; ge.ldc = N;
+        ge.rope.qbuf = qbuf; ge.rope.kc = kc; ge.rope.vc = vc; ge.rope.cos_t = cos_t; ge.rope.sin_t = sin_t;
+        ge.rope.tok_row = tok_row; ge.rope.tok_j = tok_j; ge.rope.pos_off = pos_off;
+        ge.rope.nh = nh; ge.rope.slots = slots; ge.rope.max_pos = max_pos;
+        const bool taken = gemm256_try(s, ga, (const bf16*)tmp.p, K, 0, ge, M, (int)N, K, 1, 1, 0);
+        const int rc = finish(s);                                                                    // before the interleaved copy goes away
+        return taken ? rc : PG_ERR_ARG;
+    }
+    if (!tmp.get((size_t)M * N * 4)) return PG_ERR_HIP;
+    GemmEpi e; e.out = tmp.p; e.out_f32 = 1; e.ldc = N;
+    launch_gemm<bf16>(s, ga, (const bf16*)Wqkv, K, 0, e, M, (int)N, K, 1);
+    SeqState st{nullptr, pos_off, nullptr, tok_row, tok_j, 0, 0, nullptr};
+    launch_rope_kv<bf16>(s, (const float*)tmp.p, 1, (long)M * N, (bf16*)qbuf, (bf16*)kc, (bf16*)vc, cos_t, sin_t, st, 1, M, nh, slots, max_pos);
+    return finish(s);
+}
+
+// launch_rope_kv<T> alone.  qkv fp32 [S][M][3 * nh * 128] (slab elements apart); buffers as pg_diag_op_qkv_rope in T (bf16 or fp32).  mode 0 (decode): token m is
+// row m (R >= M), slot len[m] + n_dec[0]; mode 1 (prefill): tok_row / tok_j.  The token map goes through the same screen in both modes.
+int pg_diag_op_rope_kv(int is_bf16, int mode, const float* qkv, int S, long slab, void* qbuf, void* kc, void* vc, const float* cos_t, const float* sin_t,
+                       const int32_t* len, const int32_t* n_dec, const int32_t* tok_row, const int32_t* tok_j, const int32_t* pos_off, int M, int nh, int R,
+                       int slots, int max_pos, pg_stream stream) {
+    if (!qkv || !qbuf || !kc || !vc || !cos_t || !sin_t || !pos_off) return PG_ERR_ARG;
+    if ((mode != 0 && mode != 1) || (mode == 0 && (!len || !n_dec)) || (mode == 1 && (!tok_row || !tok_j))) return PG_ERR_ARG;
+    if (M < 1 || nh < 1 || nh > 1024 || R < 1 || (mode == 0 && R < M) || slots < 1 || max_pos < 1 || S < 1 || S > 64) return PG_ERR_ARG;
+    if (slab < (long)M * 3 * nh * 128 || (long)R * slots > (1L << 28) || (long)R * nh * slots * 128 >= (1L << 40)) return PG_ERR_ARG;
+    if (!aligned16({qkv, qbuf, kc, vc, cos_t, sin_t, len, n_dec, tok_row, tok_j, pos_off})) return PG_ERR_ARG;
+    std::vector<int32_t> hrow, hj, hpos, hn;
+    if (!to_host(hpos, pos_off, R)) return PG_ERR_HIP;
+    if (mode == 0) {
+        if (!to_host(hj, len, M) || !to_host(hn, n_dec, 1)) return PG_ERR_HIP;
+        if (hn[0] < 0 || hn[0] > (1 << 28)) return PG_ERR_ARG;
+        hrow.resize(M);
+        for (int m = 0; m < M; ++m) {
+            if (hj[m] < 0 || hj[m] > (1 << 28)) return PG_ERR_ARG;
+            hrow[m] = m; hj[m] += hn[0];
+        }
+    } else if (!to_host(hrow, tok_row, M) || !to_host(hj, tok_j, M)) return PG_ERR_HIP;
+    const int sc = screen_token_map(hrow, hj, hpos, M, R, slots, max_pos);
+    if (sc != PG_OK) return sc;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    SeqState st{len, pos_off, n_dec, tok_row, tok_j, 0, 0, nullptr};
+    if (is_bf16) launch_rope_kv<bf16>(s, qkv, S, slab, (bf16*)qbuf, (bf16*)kc, (bf16*)vc, cos_t, sin_t, st, mode, M, nh, slots, max_pos);
+    else launch_rope_kv<float>(s, qkv, S, slab, (float*)qbuf, (float*)kc, (float*)vc, cos_t, sin_t, st, mode, M, nh, slots, max_pos);
+    return finish(s);
+}
+
+// Prefill gate|up projection + SwiGLU.  xn bf16 [M][K], Wgu bf16 [2 I][K] with rows ALREADY [8 gate | 8 up] interleaved, h bf16 [M][I].  form 0: gemm256_try with
+// act = 2 as run_layers calls it (gemm256_opt as pg_diag_op_qkv_rope; I % 8 refused: the interleave is in blocks of 8); PG_ERR_ARG when it declines.  form 1:
+// launch_gemm<bf16> -> fp32 [M][2 I] (gemm256_opt, or 0 = the 128 x 128 kernel), then launch_silu_mul<bf16> with S = 1.
+int pg_diag_op_gemm_swiglu256(int form, int gemm256_opt, const void* xn, const void* Wgu, void* h, int M, int I, int K, pg_stream stream) {
+    if (!xn || !Wgu || !h) return PG_ERR_ARG;
+    if ((form != 0 && form != 1) || !(opt256_ok(gemm256_opt) || (form == 1 && gemm256_opt == 0))) return PG_ERR_ARG;
+    if (M < 1 || M > kMaxGridYZ || I < 8 || (I & 7) || K < 128 || K % 64) return PG_ERR_ARG;                  // silu_mul_kernel: a grid row per token
+    if ((long)M * 2 * I >= (1L << 31) || 2L * I * K >= (1L << 31)) return PG_ERR_ARG;
+    if (!aligned16({xn, Wgu, h})) return PG_ERR_ARG;
+    LocalTune lt;
+    lt.t.gemm256 = gemm256_opt;
+    const hipStream_t s = (hipStream_t)stream;
+    GemmA ga; ga.ptr = xn; ga.lda = K;
+    if (form == 0) {
+        GemmEpi ge; ge.out = h; ge.out_f32 = 0; ge.ldc = I; ge.act = 2;
+        const bool taken = gemm256_try(s, ga, (const bf16*)Wgu, K, 0, ge, M, 2 * I, K, 1, 1, 0);
+        const int rc = finish(s);
+        return taken ? rc : PG_ERR_ARG;
+    }
+    Scratch tmp;
+    if (!tmp.get((size_t)M * 2 * I * 4)) return PG_ERR_HIP;
+    GemmEpi e; e.out = tmp.p; e.out_f32 = 1; e.ldc = 2 * I;
+    launch_gemm<bf16>(s, ga, (const bf16*)Wgu, K, 0, e, M, 2 * I, K, 1);
+    launch_silu_mul<bf16>(s, (const float*)tmp.p, 1, (long)M * 2 * I, (bf16*)h, M, I);
+    return finish(s);
+}
+
+// The two weight interleavers (bf16).  kind 0: launch_interleave_qk, src0 [3 * a * 128][b] -> dst (a = nh, b = K; src1 unused).  kind 1:
+// launch_convert_interleave16<bf16> with which = 0 on src0 (gate [a][b]) and which = 1 on src1 (up [a][b]) into the one dst [2 a][b] (a = I, b = H).
+int pg_diag_op_interleave(int kind, const void* src0, const void* src1, void* dst, int a, int b, pg_stream stream) {
+    if (!src0 || !dst || (kind != 0 && kind != 1) || (kind == 1 && !src1)) return PG_ERR_ARG;
+    if (a < 1 || b < 8 || (b & 7) || (kind == 0 && a > 1024) || (kind == 1 && (a & 7)) || (kind == 0 ? 384L : 2L) * a * b >= (1L << 31)) return PG_ERR_ARG;
+    if (!aligned16({src0, src1, dst})) return PG_ERR_ARG;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    if (kind == 0) launch_interleave_qk(s, (const bf16*)src0, (bf16*)dst, a, b);
+    else {
+        launch_convert_interleave16<bf16>(s, src0, 1, (bf16*)dst, a, b, 0);
+        launch_convert_interleave16<bf16>(s, src1, 1, (bf16*)dst, a, b, 1);
+    }
     return finish(s);
 }
 
