@@ -1,10 +1,12 @@
 // libplangen_diag.so only: operator entry points of the attention kernels (tests/test_gpu_attention.py), of the decode step's deferred-RMSNorm
 // pair and slab-folding elementwise kernels (tests/test_gpu_decode_ops.py), of the VQ-16 decoder kernels (tests/test_gpu_vq_ops.py) and of the prefill
-// GEMM epilogues -- RoPE + KV write (act 3), SwiGLU (act 2), rope_kv_kernel alone and the two weight interleavers (tests/test_gpu_prefill_ops.py) -- for
-// the operator tests.  Each one points the calling thread's pg_tune at a local PgTune (no diagnostics hooks, one kernel-form selector set), calls the PRODUCTION launcher and restores
+// GEMM epilogues -- RoPE + KV write (act 3), SwiGLU (act 2), rope_kv_kernel alone and the two weight interleavers (tests/test_gpu_prefill_ops.py) -- and of
+// the understanding path's input-side kernels (SigLIP LayerNorm / patchify / add_pos, the VQ encoder's conv_in and nearest-code search, l2norm_rows, the
+// two-level batched GEMM of SigLIP's scores and P . V: tests/test_gpu_vision_ops.py) for the operator tests.  Each one points the calling thread's pg_tune at a local PgTune (no diagnostics hooks, one kernel-form selector set), calls the PRODUCTION launcher and restores
 // pg_tune.  Shapes the kernels do not support are refused with PG_ERR_ARG and never launched.  Head dimension: 128 for the LLM kernels (implied
 // by the [.., nh * 128] layouts), 64 for SigLIP (C / NH).  Row lengths, slots and token maps live in device memory; they are copied back and
 // checked on the host before anything is launched (these are test entry points: the synchronisation does not matter).
+#include <algorithm>
 #include <initializer_list>
 #include <type_traits>
 #include <vector>
@@ -396,17 +398,45 @@ int pg_diag_op_softmax_rows(int out_bf16, const float* x, void* y, int rows, int
 // out fp32 (out_f32) or T (ldc, strideC), v = acc scale + bias_n[col] + bias_m[row] + residual (fp32 when res_f32, else T; ldr / strideR, 0: as out), act 0 / 1 (erf GELU).
 // engine_bf16 0: gemm_f32_kernel.  form: 0 launch_gemm as the engine calls it, 1 the 128 x 128 kernel (gemm256 = 0), 2 gemm256_try (gn_epilogue256 = gn_hw > 0).
 // gn_hw > 0: GroupNorm partials of the output (pixels per image) -> ws, *nsplit_out, stats as pg_diag_op_conv3x3.
-int pg_diag_op_gemm_epi(int engine_bf16, int form, const void* A, long lda, long strideA, const void* W, long ldb, long strideB, void* out, int out_f32, long ldc,
-                        long strideC, const float* bias_n, const float* bias_m, const void* residual, int res_f32, long ldr, long strideR, float scale, int act,
-                        int M, int N, int K, int batch, int gn_hw, float* ws, long ws_floats, float* stats, float eps, int* nsplit_out, pg_stream stream) {
+}  // extern "C"
+namespace {
+// Output blocks of a two-level batched GEMM: block (b, b2) starts at b strideC + b2 strideC2 and covers M rows of N elements, ldc apart.  Seen on the grid of
+// ldc-wide rows a block is the rectangle rows [q, q + M) x columns [p, p + N) with start = q ldc + p; a block that wraps the row pitch (p + N > ldc) is refused,
+// and no two rectangles may intersect -- that covers the dense layouts and the column-offset one (strideC2 < ldc: the heads side by side inside a row).
+bool blocks_disjoint(int M, int N, long ldc, int batch, int batch2, long strideC, long strideC2) {
+    struct Rect { long q, p; };
+    std::vector<Rect> r;
+    r.reserve((size_t)batch * batch2);
+    for (int b = 0; b < batch; ++b)
+        for (int b2 = 0; b2 < batch2; ++b2) {
+            const long o = (long)b * strideC + (long)b2 * strideC2;
+            if (o % ldc + N > ldc) return false;
+            r.push_back({o / ldc, o % ldc});
+        }
+    std::sort(r.begin(), r.end(), [](const Rect& a, const Rect& b) { return a.q < b.q || (a.q == b.q && a.p < b.p); });
+    for (size_t i = 0; i < r.size(); ++i)
+        for (size_t j = i + 1; j < r.size() && r[j].q < r[i].q + M; ++j)
+            if (r[j].p < r[i].p + N && r[i].p < r[j].p + N) return false;
+    return true;
+}
+int gemm_epi_impl(int engine_bf16, int form, const void* A, long lda, long strideA, const void* W, long ldb, long strideB, void* out, int out_f32, long ldc,
+                  long strideC, const float* bias_n, const float* bias_m, const void* residual, int res_f32, long ldr, long strideR, float scale, int act,
+                  int M, int N, int K, int batch, int batch2, long strideA2, long strideB2, long strideC2, int gn_hw, float* ws, long ws_floats, float* stats,
+                  float eps, int* nsplit_out, pg_stream stream) {
     if (!A || !W || !out || !nsplit_out) return PG_ERR_ARG;
     if (form < 0 || form > 2 || (!engine_bf16 && form == 2) || (act != 0 && act != 1)) return PG_ERR_ARG;
     if (M < 1 || N < 1 || K < 1 || batch < 1 || batch > kMaxGridYZ || lda < K || ldb < K || ldc < N || strideA < 0 || strideB < 0 || strideC < 0) return PG_ERR_ARG;
-    if (batch > 1 && strideC < (long)(M - 1) * ldc + N) return PG_ERR_ARG;                           // batches must not overlap in the output
+    if (batch2 < 1 || (long)batch * batch2 > kMaxGridYZ || strideA2 < 0 || strideB2 < 0 || strideC2 < 0) return PG_ERR_ARG;      // gemm_f32_kernel: grid z = batch x batch2
+    if (batch2 == 1) {
+        if (batch > 1 && strideC < (long)(M - 1) * ldc + N) return PG_ERR_ARG;                       // batches must not overlap in the output
+    } else {
+        if (residual || gn_hw) return PG_ERR_ARG;                                                    // the kernels have no second-level residual stride; partials need batch 1
+        if (!blocks_disjoint(M, N, ldc, batch, batch2, strideC, strideC2)) return PG_ERR_ARG;
+    }
     if (residual && ((ldr && ldr < N) || strideR < 0)) return PG_ERR_ARG;
     if (engine_bf16) {
         // PlainLoaderB / the weight rows: 64-element K tiles fetched as 16-byte LDS-DMA chunks
-        if (K % 64 || ((lda | ldb | strideA | strideB) & 7) || (((uintptr_t)A | (uintptr_t)W) & 15)) return PG_ERR_ARG;
+        if (K % 64 || ((lda | ldb | strideA | strideB | strideA2 | strideB2) & 7) || (((uintptr_t)A | (uintptr_t)W) & 15)) return PG_ERR_ARG;
     } else if (!out_f32 || (residual && !res_f32) || gn_hw) return PG_ERR_ARG;
     if (((uintptr_t)out | (uintptr_t)residual | (uintptr_t)bias_n) & 15) return PG_ERR_ARG;         // vec_ok() looks at the leading dimensions and offsets only
     *nsplit_out = 0;
@@ -418,20 +448,28 @@ int pg_diag_op_gemm_epi(int engine_bf16, int form, const void* A, long lda, long
     lt.t.gemm256 = form == 1 ? 0 : 1;
     lt.t.gn_epilogue256 = form == 2 && gn_hw ? 1 : 0;
     const hipStream_t s = (hipStream_t)stream;
-    GemmA a; a.ptr = A; a.lda = lda; a.strideA = strideA;
-    GemmEpi e; e.out = out; e.out_f32 = out_f32; e.ldc = ldc; e.strideC = strideC; e.bias_n = bias_n; e.bias_m = bias_m; e.residual = residual; e.res_f32 = res_f32;
-    e.ldr = ldr; e.strideR = strideR; e.scale = scale; e.act = act;
+    GemmA a; a.ptr = A; a.lda = lda; a.strideA = strideA; a.strideA2 = strideA2;
+    GemmEpi e; e.out = out; e.out_f32 = out_f32; e.ldc = ldc; e.strideC = strideC; e.strideC2 = strideC2; e.bias_n = bias_n; e.bias_m = bias_m; e.residual = residual;
+    e.res_f32 = res_f32; e.ldr = ldr; e.strideR = strideR; e.scale = scale; e.act = act;
     int nsp = 0;
     if (gn_hw) { a.gn_part = ws; a.gn_nsplit = &nsp; a.gn_hw = gn_hw; }
     bool taken = true;
-    if (!engine_bf16) launch_gemm<float>(s, a, (const float*)W, ldb, strideB, e, M, N, K, batch);
-    else if (form == 2) taken = gemm256_try(s, a, (const bf16*)W, ldb, strideB, e, M, N, K, batch, 1, 0);
-    else launch_gemm<bf16>(s, a, (const bf16*)W, ldb, strideB, e, M, N, K, batch);
+    if (!engine_bf16) launch_gemm<float>(s, a, (const float*)W, ldb, strideB, e, M, N, K, batch, batch2, strideB2);
+    else if (form == 2) taken = gemm256_try(s, a, (const bf16*)W, ldb, strideB, e, M, N, K, batch, batch2, strideB2);
+    else launch_gemm<bf16>(s, a, (const bf16*)W, ldb, strideB, e, M, N, K, batch, batch2, strideB2);
     if (taken && nsp > 0) launch_gn_finalize(s, ws, stats, nullptr, nullptr, nullptr, M / gn_hw, nsp, gn_hw, N, eps);
     const int rc = finish(s);
     if (!taken) return PG_ERR_ARG;
     *nsplit_out = nsp;
     return rc;
+}
+}  // namespace
+extern "C" {
+int pg_diag_op_gemm_epi(int engine_bf16, int form, const void* A, long lda, long strideA, const void* W, long ldb, long strideB, void* out, int out_f32, long ldc,
+                        long strideC, const float* bias_n, const float* bias_m, const void* residual, int res_f32, long ldr, long strideR, float scale, int act,
+                        int M, int N, int K, int batch, int gn_hw, float* ws, long ws_floats, float* stats, float eps, int* nsplit_out, pg_stream stream) {
+    return gemm_epi_impl(engine_bf16, form, A, lda, strideA, W, ldb, strideB, out, out_f32, ldc, strideC, bias_n, bias_m, residual, res_f32, ldr, strideR, scale, act,
+                         M, N, K, batch, 1, 0, 0, 0, gn_hw, ws, ws_floats, stats, eps, nsplit_out, stream);
 }
 
 // The decoder's conv_out (Cin -> Cout <= 4), NHWC in -> NCHW out (fp32, or bf16 when out_bf16).  form 1: launch_conv3x3_small<T> (x, w T; engine_bf16 picks T);
@@ -627,6 +665,95 @@ int pg_diag_op_interleave(int kind, const void* src0, const void* src1, void* ds
         launch_convert_interleave16<bf16>(s, src1, 1, (bf16*)dst, a, b, 1);
     }
     return finish(s);
+}
+
+// ------------------------------------------------------------------------------------------------ understanding path, input side (tests/test_gpu_vision_ops.py)
+// Every entry point below synchronises the stream before it returns.
+
+// LayerNorm over the last dimension: x fp32 [M][C], gamma / beta fp32 [C] -> y [M][C] fp32 or bf16 (launch_layernorm<T>).  form 0: ln_wave = 0, layernorm_kernel
+// (a block per row, any C).  form 1: ln_wave = 1, layernorm_wave_kernel<T, 4> -- the launcher takes it at C == 1024 only, so every other C is REFUSED here (a
+// caller then knows which kernel ran); its 16-byte row, gamma and beta loads and 8- / 16-byte stores need 16-byte aligned pointers.
+int pg_diag_op_layernorm(int out_bf16, int form, const float* x, const float* gamma, const float* beta, void* y, int M, int C, float eps, pg_stream stream) {
+    if (!x || !gamma || !beta || !y || (form != 0 && form != 1)) return PG_ERR_ARG;
+    if (M < 1 || C < 1 || (long)M * C >= (1L << 40) || !(eps >= 0.f)) return PG_ERR_ARG;
+    if (form == 1 && (C != 1024 || !aligned16({x, gamma, beta, y}))) return PG_ERR_ARG;
+    LocalTune lt;
+    lt.t.ln_wave = form;
+    const hipStream_t s = (hipStream_t)stream;
+    if (out_bf16) launch_layernorm<bf16>(s, x, gamma, beta, (bf16*)y, M, C, eps);
+    else launch_layernorm<float>(s, x, gamma, beta, (float*)y, M, C, eps);
+    return finish(s);
+}
+
+// PatchEmbed's gather: img NCHW [B][3][S][S] fp32 or bf16 -> out [B (S / ps)^2][3 ps^2] fp32 or bf16, k = (c, py, px) (launch_patchify<T>).  S % ps != 0 is refused:
+// the kernel's grid g = S / ps would drop the last partial patch silently.
+int pg_diag_op_patchify(int img_bf16, int out_bf16, const void* img, void* out, int B, int S, int ps, pg_stream stream) {
+    if (!img || !out || B < 1 || ps < 1 || S < ps || S > 16384 || S % ps) return PG_ERR_ARG;
+    if ((long)B * (S / ps) * (S / ps) > 0x7fffffffL) return PG_ERR_ARG;                               // a block per patch
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    if (out_bf16) launch_patchify<bf16>(s, img, img_bf16, (bf16*)out, B, S, ps);
+    else launch_patchify<float>(s, img, img_bf16, (float*)out, B, S, ps);
+    return finish(s);
+}
+
+// x fp32 [B][P][C] += pos fp32 [P][C] (launch_add_pos).
+int pg_diag_op_add_pos(float* x, const float* pos, int B, int P, int C, pg_stream stream) {
+    if (!x || !pos || B < 1 || P < 1 || C < 1 || (long)B * P > 0x7fffffffL) return PG_ERR_ARG;      // a block per row
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    launch_add_pos(s, x, pos, B, P, C);
+    return finish(s);
+}
+
+// The VQ encoder's conv_in (launch_conv3x3_in<T>, Cin = 3): x NCHW [B][3][H][W] fp32 or bf16, w fp32 [Cout][3][3][3], bias fp32 [Cout] -> out NHWC [B][H][W][Cout]
+// fp32 or bf16.  The grid is (ceil(W / 64), H, B).
+int pg_diag_op_conv_in(int x_bf16, int out_bf16, const void* x, const float* w, const float* bias, void* out, int B, int H, int W, int Cout, pg_stream stream) {
+    if (!x || !w || !bias || !out) return PG_ERR_ARG;
+    if (B < 1 || B > kMaxGridYZ || H < 1 || H > kMaxGridYZ || W < 1 || Cout < 1 || (long)B * H * W * (Cout > 3 ? Cout : 3) >= (1L << 40)) return PG_ERR_ARG;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    if (out_bf16) launch_conv3x3_in<bf16>(s, x, x_bf16, w, bias, (bf16*)out, B, H, W, 3, Cout);
+    else launch_conv3x3_in<float>(s, x, x_bf16, w, bias, (float*)out, B, H, W, 3, Cout);
+    return finish(s);
+}
+
+// Nearest code: z fp32 [n][D], cb fp32 [V][D] (already L2-normalised by the caller) -> idx int64 [n].  form 0: vq_argmin_kernel (vq_argmin_multi = 0); form 1:
+// vq_argmin_multi_kernel<8> (vq_argmin_multi = 1), refused unless D == 8 && n >= 64 -- the launcher's own condition, so the form names the kernel; form 2:
+// launch_vq_argmin under the default tune, as the engine calls it.  D outside [1, 8] is refused: both kernels keep the vector in zn[8], and in the product only
+// pg_create's img_dim check stands between a larger D and an overflow of that array.  The eight-vector kernel reads a code as two 16-byte vectors: cb aligned.
+int pg_diag_op_vq_argmin(int form, const float* z, const float* cb, int64_t* idx, int n, int D, int V, pg_stream stream) {
+    if (!z || !cb || !idx || form < 0 || form > 2) return PG_ERR_ARG;
+    if (n < 1 || D < 1 || D > 8 || V < 1 || (long)V * D > 0x7fffffffL) return PG_ERR_ARG;
+    const bool multi = D == 8 && n >= 64;
+    if (form == 1 && !multi) return PG_ERR_ARG;
+    if (form != 0 && multi && ((uintptr_t)cb & 15)) return PG_ERR_ARG;
+    LocalTune lt;
+    if (form != 2) lt.t.vq_argmin_multi = form;
+    const hipStream_t s = (hipStream_t)stream;
+    launch_vq_argmin(s, z, cb, idx, n, D, V);
+    return finish(s);
+}
+
+// dst fp32 [n][D] = src[r] / max(|src[r]|, 1e-12) (launch_l2norm_rows: the codebook's F.normalize).
+int pg_diag_op_l2norm_rows(const float* src, float* dst, int n, int D, pg_stream stream) {
+    if (!src || !dst || n < 1 || D < 1 || (long)n * D >= (1L << 40)) return PG_ERR_ARG;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    launch_l2norm_rows(s, src, dst, n, D);
+    return finish(s);
+}
+
+// pg_diag_op_gemm_epi with the second batch level (SigLIP's heads): block (b, b2) reads A + b strideA + b2 strideA2 and W + b strideB + b2 strideB2 and writes at
+// out + b strideC + b2 strideC2 (launch_gemm<T>(.., batch, batch2, strideB2); form 0 / 1 / 2 as pg_diag_op_gemm_epi).  With batch2 > 1 no residual and no GroupNorm
+// partials (the kernels have no second-level stride for either), and no two output blocks may overlap (blocks_disjoint: strideC2 < ldc, the heads side by
+// side inside a row, included).
+int pg_diag_op_gemm_heads(int engine_bf16, int form, const void* A, long lda, long strideA, const void* W, long ldb, long strideB, void* out, int out_f32, long ldc,
+                          long strideC, const float* bias_n, const float* bias_m, const void* residual, int res_f32, long ldr, long strideR, float scale, int act,
+                          int M, int N, int K, int batch, int batch2, long strideA2, long strideB2, long strideC2, int gn_hw, float* ws, long ws_floats,
+                          float* stats, float eps, int* nsplit_out, pg_stream stream) {
+    return gemm_epi_impl(engine_bf16, form, A, lda, strideA, W, ldb, strideB, out, out_f32, ldc, strideC, bias_n, bias_m, residual, res_f32, ldr, strideR, scale, act,
+                         M, N, K, batch, batch2, strideA2, strideB2, strideC2, gn_hw, ws, ws_floats, stats, eps, nsplit_out, stream);
 }
 
 }  // extern "C"

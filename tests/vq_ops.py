@@ -160,9 +160,10 @@ def run_softmax(x, scale, out_kind, dev="cuda"):
 
 
 def run_gemm_epi(A, W, out_kind, M, N, K, batch, lda, strideA, ldb, strideB, ldc, strideC, bias_n=None, bias_m=None, residual=None, res_kind="f32", ldr=0,
-                 strideR=0, scale=1.0, act=0, gn_hw=0, form=1, engine="bf16", dev="cuda", expect=PG_OK):
+                 strideR=0, scale=1.0, act=0, gn_hw=0, form=1, engine="bf16", dev="cuda", expect=PG_OK, inplace=False):
     """A, W: flat or shaped tensors holding the operands in the layout the strides describe.  Returns dict(rc, out [batch, M, N] CPU (rows ldc apart are
-    compacted), nsplit, stats, guards, gaps: the elements between rows / batches (ldc > N) still NaN)."""
+    compacted), nsplit, stats, guards, gaps: the elements between rows / batches (ldc > N) still NaN).  inplace: the fp32 residual [batch, M, N] is laid into the
+    output buffer itself and the kernel is handed ONE pointer as out and residual (pg_engine::lin's x += proj(o)); fp32 output, ldr / strideR as the output's."""
     T = tdt(engine)
     Ad, Wd = A.to(dev, T).contiguous(), W.to(dev, T).contiguous()
     bn = None if bias_n is None else bias_n.to(dev, torch.float32)
@@ -170,6 +171,10 @@ def run_gemm_epi(A, W, out_kind, M, N, K, batch, lda, strideA, ldb, strideB, ldc
     rd = None if residual is None else residual.to(dev, torch.float32 if res_kind == "f32" else T).contiguous()
     numel = (batch - 1) * strideC + (M - 1) * ldc + N
     out = Banded(numel, torch.float32 if out_kind == "f32" else T, dev)
+    if inplace:
+        assert residual is not None and out_kind == "f32" and res_kind == "f32" and ldr in (0, ldc) and strideR == strideC
+        torch.as_strided(out.t, (batch, M, N), (strideC, ldc, 1)).copy_(residual.reshape(batch, M, N).to(dev, torch.float32))
+        rd = out.t
     need = (M // gn_hw) * ((gn_hw + 63) // 64) * 64 if gn_hw else 64
     ws = Workspace(need, dev)
     nb = M // gn_hw if gn_hw else 1
