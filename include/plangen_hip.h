@@ -276,6 +276,33 @@ int pg_generate_text_constrained(pg_handle h, int max_new, int eos_id, float tem
                                  uint64_t seed, int64_t* out_dev, int* out_len_host, int32_t* state_out_dev /*[B] or NULL*/,
                                  float* logits_out_dev, pg_stream s);
 
+/* Token log-probabilities: how likely the model found every token a decode loop emitted (HF's output_scores /
+ * compute_transition_scores), reduced on the device next to the sampler: one float per row and step instead of the logits_out tap.
+ * A row is an image of the CFG loop or a sequence of the text loop.  Per row and step, with tok the EMITTED token and y the fp32 row
+ * the draw is made from, before top-k and top-p:
+ *   image loop  y = u + w (c - u), bit for bit what logits_out_dev receives;
+ *   text loop   y = the reduced lm_head row after the min_new EOS suppression and after the automaton's mask (disallowed entries
+ *               -inf), bit for bit what logits_out_dev receives;
+ *   x = y * (1 / temperature) when temperature > 0 (the fp32 product the draw uses), else x = y; NaN counts as -inf;
+ *   logprob = (x[tok] - m) - logf(sum_v expf(x_v - m)),  m = max_v x_v,  all fp32 with the accurate expf / logf.
+ * top-k and top-p do NOT renormalise it (scores of runs with different filters stay comparable); the automaton's mask and the EOS
+ * ban do, because they change which tokens exist.  x[tok] = -inf gives -inf (a forced token on a masked entry; the "nothing kept"
+ * emission of token 0 / eos_id), and so does a row without a finite entry; when m = +inf the mass lies evenly on the +inf entries.
+ * Forcing: tok is what out_tok_dev receives.  With force_mask_dev it is force_tok where mask == 0 -- force_mask = zeros is the SCORING
+ * MODE: the log-likelihood of a given image under the model; with force_tok_dev alone the emitted token is the model's own, and so
+ * is the score.  Text: a row that was finished BEFORE a step gets 0.0 there, so that a row's sum is its sequence log-probability; the
+ * step that emits its EOS is scored like any other.
+ * pg_request_token_logprobs is ONE-SHOT: the request is consumed by the next pg_decode_image_tokens[_filtered] /
+ * pg_generate_text_{greedy,sampled,constrained} on this handle, whether that call succeeds or not, and that call also writes
+ * out_dev fp32 [B, T] (image loop) or [B, max_new] (text loop; columns >= *out_len_host are left untouched).  out_dev must stay valid
+ * until that call's work on the stream is done.  Inside the loop the scores go to a library-owned buffer (allocated by the first
+ * request, counted by pg_device_bytes) and are copied to out_dev at the end, as the tokens are; a captured step graph is re-captured
+ * when a call's request differs from the capture's.  A call without a request launches exactly what it launched before this
+ * entry point existed.  out_dev == NULL cancels a pending request.
+ * PG_ERR_ARG: capacity_floats < 1 here; at the consuming call, nothing launched and the handle still usable: capacity_floats below
+ * B * T / B * max_new, or the "lanes" = 2 decode. */
+int pg_request_token_logprobs(pg_handle h, float* out_dev, int64_t capacity_floats);
+
 /* -- VQ-16 tokenizer ---------------------------------------------------------------------- */
 /* gen_vision_model.decode_code(codes, shape=[B,8,g,g]) (vq_model.py:505-508; call site
  * plangen_base.py:555): codes_dev int32 [B, g*g] -> img_out_dev [B, 3, S, S] (NCHW like the
@@ -437,6 +464,12 @@ int pg_op_text_constrain(pg_handle h, const float* logits_dev /*[B,V]*/, int B, 
                          int remaining, int eos_id, float temperature, int top_k, float top_p, uint64_t seed,
                          int row_offset, int step, uint8_t* keep_dev /*[B,V] or NULL*/, int32_t* tok_dev /*[B]*/,
                          int32_t* next_state_dev /*[B]*/, pg_stream s);
+
+/* The scoring kernel of pg_request_token_logprobs on caller-given rows (same device code): x_dev fp32 [B, V] (the row y above; any
+ * B >= 1, V >= 1), tok_dev int32 [B], temperature as above -> logprob_dev fp32 [B].  A token outside [0, V) gives -inf.  Works on
+ * any handle.  PG_ERR_ARG: a null pointer, B < 1, V < 1. */
+int pg_op_token_logprob(pg_handle h, const float* x_dev, int B, int V, const int32_t* tok_dev, float temperature,
+                        float* logprob_dev, pg_stream s);
 
 /* The quantiser of the FP8 KV cache (the device code the decode append and the prefill conversion run; format above):
  * x_dev bf16 [n, 128] -> codes_dev uint8 [n, 128] (e4m3fn), scale_dev fp32 [n] (powers of two).  Works on any handle. */

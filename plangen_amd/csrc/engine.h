@@ -114,6 +114,9 @@ struct pg_engine {
     unsigned char* h_dfa = nullptr; size_t h_dfa_bytes = 0; hipEvent_t ev_dfa = nullptr; bool dfa_staged = false;
     bool dfa_set = false; int32_t dfa_dist_start = 0;
     int32_t *d_out_tok = nullptr, *d_force_tok = nullptr; uint8_t* d_force_mask = nullptr; int64_t* d_text_out = nullptr;
+    // pg_request_token_logprobs: the caller's destination for the NEXT decode / generate call (one-shot, like uncond_hint) and the library-owned
+    // [B, T] / [B, max_new] buffer the loop's kernels write (allocated by the first request, so a captured step keeps a valid address)
+    float* lp_req = nullptr; int64_t lp_req_cap = 0; float* d_logprob = nullptr;
     int rng_image_offset = 0;                                    // pg_set_option("rng_image_offset", lo): this rank's first image in the global batch
     PgTune tune;                                                 // per-handle tuning knobs (pg_set_option)
     int tune_epoch = 0;                                          // bumped by every option that changes what a captured graph contains
@@ -239,6 +242,7 @@ struct pg_engine {
     int text_generate(int max_new, int min_new, int eos, float temp, int top_k, float top_p, uint64_t seed, int64_t* out, int* out_len,
                       float* logits_out, hipStream_t s, bool constrained = false, int32_t* state_out = nullptr);
     int set_text_dfa(const pg_text_dfa* dfa, hipStream_t s);
+    int token_logprob(const float* x, int B, int V, const int32_t* tok, float temp, float* out, hipStream_t s);
     int text_constrain(const float* logits, int B, int V, const int32_t* state, int remaining, int eos, float temp, int top_k, float top_p,
                        uint64_t seed, int row_offset, int step, uint8_t* keep, int32_t* tok, int32_t* next_state, hipStream_t s);
     template <typename T> int vq_decode(const int32_t* codes, void* img_out, int out_dtype, int B, hipStream_t s);

@@ -123,6 +123,12 @@ int pg_generate_text_constrained(pg_handle h, int max_new, int eos_id, float tem
     return h->text_generate(max_new, 0, eos_id, temperature, top_k, top_p, seed, out_dev, out_len_host, logits_out_dev, (hipStream_t)s,
                             /*constrained*/ true, state_out_dev);
 }
+int pg_request_token_logprobs(pg_handle h, float* out_dev, int64_t capacity_floats) {
+    if (!h) return PG_ERR_ARG;
+    if (out_dev && capacity_floats < 1) { h->err = "pg_request_token_logprobs: capacity_floats must be >= 1"; return PG_ERR_ARG; }
+    h->lp_req = out_dev; h->lp_req_cap = out_dev ? capacity_floats : 0;
+    return PG_OK;
+}
 int pg_vq_decode(pg_handle h, const int32_t* codes_dev, void* img_out_dev, int out_dtype, int B, pg_stream s) { TuneGuard _tg(h);
     if (!h || !codes_dev || !img_out_dev) return PG_ERR_ARG;
     return h->bf ? h->vq_decode<bf16>(codes_dev, img_out_dev, out_dtype, B, (hipStream_t)s)
@@ -310,6 +316,10 @@ int pg_op_text_constrain(pg_handle h, const float* logits_dev, int B, int V, con
     if (!h || !logits_dev || !state_dev || !tok_dev || !next_state_dev) return PG_ERR_ARG;
     return h->text_constrain(logits_dev, B, V, state_dev, remaining, eos_id, temperature, top_k, top_p, seed, row_offset, step, keep_dev, tok_dev,
                              next_state_dev, (hipStream_t)s);
+}
+int pg_op_token_logprob(pg_handle h, const float* x_dev, int B, int V, const int32_t* tok_dev, float temperature, float* logprob_dev, pg_stream s) {
+    if (!h || !x_dev || !tok_dev || !logprob_dev) return PG_ERR_ARG;
+    return h->token_logprob(x_dev, B, V, tok_dev, temperature, logprob_dev, (hipStream_t)s);
 }
 int pg_op_kv_quantize(pg_handle h, const void* x_dev, uint8_t* codes_dev, float* scale_dev, int64_t n, pg_stream s) {
     if (!h || !x_dev || !codes_dev || !scale_dev || n < 0) return PG_ERR_ARG;

@@ -306,6 +306,8 @@ void pg_engine::forward_decode(hipStream_t s) {
 
 int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_p, uint64_t seed, const int32_t* force_tok,
                             const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s) {
+    float* const lp_out = lp_req; const int64_t lp_cap = lp_req_cap;      // the one-shot log-prob request: consumed whatever this call answers
+    lp_req = nullptr; lp_req_cap = 0;
     if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(PG_ERR_ARG, "top_k=%d must be >= 0 and top_p=%g in (0, 1]", top_k, (double)top_p);
     if (!prefilled) FAIL(PG_ERR_STATE, "pg_decode_image_tokens before pg_prefill");
     if (kv8 && !fuse_rope) FAIL(PG_ERR_ARG, "the FP8 KV cache needs the fused decode attention (fuse_rope)");
@@ -315,8 +317,12 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     if (R % 2) FAIL(PG_ERR_ARG, "CFG decode needs an even number of rows (got %d)", R);
     if (n_dec_host != 0) FAIL(PG_ERR_STATE, "decode loop needs a fresh prefill");
     if (T < 1 || T - 1 > cfg.max_new) FAIL(PG_ERR_CAPACITY, "T=%d exceeds max_new=%d", T, cfg.max_new);
+    if (lp_out && lp_cap < (int64_t)(R / 2) * T) FAIL(PG_ERR_ARG, "token log-probs: capacity %lld floats is below B * T = %lld", (long long)lp_cap, (long long)(R / 2) * T);
+    if (lp_out && lanes_opt == 2) FAIL(PG_ERR_ARG, "token log-probs do not support lanes = 2");
     HIPCHK(hipSetDevice(dev));
     const int Rtot = R, B = R / 2;
+    const bool score = lp_out != nullptr;
+    if (score && !d_logprob) TRY(dalloc(&d_logprob, (size_t)cfg.max_rows * (cfg.max_new + 1) * 4, false));
     // Lanes: at large batch the rows are split into two independent chains on two streams so one
     // half's latency-bound GEMM / norm kernels overlap the other half's bandwidth-bound attention.
     // CFG pairs never straddle lanes; results are lane-independent (global image index in the RNG).
@@ -329,8 +335,8 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     const bool filtered = temp > 0.f && (top_k > 0 || top_p < 1.f);
     if (filtered) {
         if (cfg.img_vocab > SEL_MAXV) FAIL(PG_ERR_CAPACITY, "top-k / top-p sampler supports img_vocab <= %d (got %d)", SEL_MAXV, cfg.img_vocab);
-        if (!cfg_mix) TRY(dalloc(&cfg_mix, (size_t)(cfg.max_rows / 2) * cfg.img_vocab * 4, false));
     }
+    if ((filtered || score) && !cfg_mix) TRY(dalloc(&cfg_mix, (size_t)(cfg.max_rows / 2) * cfg.img_vocab * 4, false));
     struct LaneDef { int r0, nrows; float* part; int32_t* ndec; };
     LaneDef ld[2];
     ld[0] = {0, nl == 2 ? Rtot / 2 : Rtot, part, d_ndec};
@@ -365,7 +371,11 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
         sa.logits_partial = part; sa.S = S_last; sa.slab = slab_last; sa.x = x; sa.n_dec = d_ndec; sa.b_off = L.r0 / 2;
         tic(st);
         if (filtered) launch_cfg_sample_filtered(st, sa, R / 2, cfg_pv, cfg_pi, cfg_mix);
-        else launch_cfg_sample(st, sa, R / 2, cfg_pv, cfg_pi);
+        else {
+            if (score) launch_cfg_store(st, sa, R / 2, cfg_mix);     // the filtered route already leaves the mixed rows in cfg_mix
+            launch_cfg_sample(st, sa, R / 2, cfg_pv, cfg_pi);
+        }
+        if (score) launch_token_logprob_image(st, sa, R / 2, cfg_mix, d_logprob);
         toc(st, TC_SAMPLE, (double)S_last * R * cfg.img_vocab * 4.0);
         tc_on = false;
     };
@@ -409,7 +419,8 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
         // device memory, so a bench / serving loop replays ONE instantiated graph across calls
         std::vector<int64_t> key = {Rtot, (int64_t)bf, (int64_t)logits_out, (int64_t)shared_len, (int64_t)fuse_rope, (int64_t)nl,
                                     (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch, (int64_t)skip_attn, (int64_t)filtered,
-                                    (int64_t)group_rows};        // replica geometry: never replay a graph across different aliasing
+                                    (int64_t)group_rows,         // replica geometry: never replay a graph across different aliasing
+                                    (int64_t)score};             // the scored step holds two more launches
         if (!gexec || key != gkey) {
             if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
             hipGraph_t g = nullptr;
@@ -428,6 +439,7 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     }
     if (T > 1) TRY(iteration(false));
     HIPCHK(hipMemcpyAsync(out_tok, d_out_tok, (size_t)B * T * 4, hipMemcpyDeviceToDevice, ws));
+    if (score) HIPCHK(hipMemcpyAsync(lp_out, d_logprob, (size_t)B * T * 4, hipMemcpyDeviceToDevice, ws));
     HIPCHK(hipEventRecord(ev_t1, ws));
     if (ws != s) {
         HIPCHK(hipEventRecord(ev_out, ws));
@@ -558,8 +570,20 @@ int pg_engine::text_constrain(const float* logits, int B, int V, const int32_t* 
     return PG_OK;
 }
 
+// pg_op_token_logprob: the loops' scoring kernel on caller-given rows and tokens
+int pg_engine::token_logprob(const float* x, int B, int V, const int32_t* tok, float temp, float* out, hipStream_t s) {
+    if (B < 1 || V < 1) FAIL(PG_ERR_ARG, "pg_op_token_logprob: needs B >= 1 and V >= 1 (got %d, %d)", B, V);
+    if (((uintptr_t)x & 3) || ((uintptr_t)tok & 3) || ((uintptr_t)out & 3)) FAIL(PG_ERR_ARG, "pg_op_token_logprob: pointers must be 4-byte aligned");
+    HIPCHK(hipSetDevice(dev));
+    launch_token_logprob_op(s, x, B, V, tok, temp, out);
+    HIPCHK(hipGetLastError());
+    return PG_OK;
+}
+
 int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int top_k, float top_p, uint64_t seed, int64_t* out, int* out_len,
                              float* logits_out, hipStream_t s, bool constrained, int32_t* state_out) {
+    float* const lp_out = lp_req; const int64_t lp_cap = lp_req_cap;      // the one-shot log-prob request: consumed whatever this call answers
+    lp_req = nullptr; lp_req_cap = 0;
     if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(PG_ERR_ARG, "top_k=%d must be >= 0 and top_p=%g in (0, 1]", top_k, (double)top_p);
     if (!prefilled) FAIL(PG_ERR_STATE, "text decode before pg_prefill");
     if (replicas_n > 1) FAIL(PG_ERR_STATE, "text decode after pg_prefill_replicated (position_mode 0, image sampling only)");
@@ -571,12 +595,15 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
         if (!dfa_set) FAIL(PG_ERR_STATE, "constrained text decode without an automaton (pg_set_text_dfa)");
         if (dfa_dist_start > max_new) FAIL(PG_ERR_ARG, "max_new=%d is below dist[start_state]=%d: no row could finish", max_new, dfa_dist_start);
     }
+    if (lp_out && lp_cap < (int64_t)R * max_new) FAIL(PG_ERR_ARG, "token log-probs: capacity %lld floats is below B * max_new = %lld", (long long)lp_cap, (long long)R * max_new);
     HIPCHK(hipSetDevice(dev));
     const int B = R;
+    const bool score = lp_out != nullptr;
+    if (score && !d_logprob) TRY(dalloc(&d_logprob, (size_t)cfg.max_rows * (cfg.max_new + 1) * 4, false));
     // launch structure: greedy argmax (temperature <= 0 ignores the filters, as HF's warpers do) / Gumbel-max folded into the scan /
     // scan -> workspace -> select.  Everything else about sampling is a value in TextParams.
     const int mode = !(temp > 0.f) ? 0 : ((top_k > 0 || top_p < 1.f) ? 2 : 1);
-    if (mode == 2 && !txt_mix) TRY(dalloc(&txt_mix, (size_t)cfg.max_rows * cfg.vocab * 4, false));
+    if ((mode == 2 || score) && !txt_mix) TRY(dalloc(&txt_mix, (size_t)cfg.max_rows * cfg.vocab * 4, false));
     std::vector<int32_t> ones(B, 1);
     HIPCHK(hipMemcpyAsync(d_unf, ones.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(d_anyunf, 0, 1024 * 4, s));
@@ -610,10 +637,13 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
         if (bf) gemm_llm<bf16>(ws, (const bf16*)hfin, (const bf16*)lm_head, B, cfg.vocab, H(), true, lm_head_t);
         else gemm_llm<float>(ws, (const float*)hfin, (const float*)lm_head, B, cfg.vocab, H(), true);
         ta.logits_partial = part; ta.S = S_last; ta.slab = slab_last;
+        // scored greedy / Gumbel-in-the-scan steps: the row goes to txt_mix first (mode 2 leaves it there anyway); the step's own scan follows
+        if (score && mode != 2) launch_text_store(ws, ta, constrained ? &da : nullptr, B, cfg_pv, cfg_pi, txt_mix);
         if (constrained) launch_text_constrained(ws, ta, da, B, mode, cfg_pv, cfg_pi, txt_mix);
         else if (mode == 2) launch_text_sample_filtered(ws, ta, B, cfg_pv, cfg_pi, txt_mix);
         else if (mode == 1) launch_text_sample(ws, ta, B, cfg_pv, cfg_pi);
         else launch_text_argmax(ws, ta, B, cfg_pv, cfg_pi);
+        if (score) launch_token_logprob_text(ws, ta, B, txt_mix, d_logprob);
         if (with_forward) forward_decode(ws);
     };
     for (int step_i = 0; step_i < max_new; ++step_i) {
@@ -621,7 +651,7 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
         if (use_graph && !last && step_i > 0) {
             // shapes and kernel selection only: temperature, top_k, top_p, seed and the row offset reach the kernels through TextParams
             std::vector<int64_t> key = {R, (int64_t)bf, (int64_t)fuse_rope, (int64_t)shared_len, (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch,
-                                        (int64_t)mode, (int64_t)logits_out, (int64_t)constrained};
+                                        (int64_t)mode, (int64_t)logits_out, (int64_t)constrained, (int64_t)score};
             if (!gexec_txt || key != gkey_txt) {
                 if (gexec_txt) { (void)hipGraphExecDestroy(gexec_txt); gexec_txt = nullptr; }
                 hipGraph_t g = nullptr;
@@ -648,6 +678,7 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
     if (done_len < 0) done_len = max_new;
     // only the columns this call produced; the caller's buffer keeps its own fill beyond them
     HIPCHK(hipMemcpy2DAsync(out, (size_t)max_new * 8, d_text_out, (size_t)max_new * 8, (size_t)done_len * 8, B, hipMemcpyDeviceToDevice, ws));
+    if (score) HIPCHK(hipMemcpy2DAsync(lp_out, (size_t)max_new * 4, d_logprob, (size_t)max_new * 4, (size_t)done_len * 4, B, hipMemcpyDeviceToDevice, ws));
     if (constrained && state_out) HIPCHK(hipMemcpyAsync(state_out, d_dfa_state, (size_t)B * 4, hipMemcpyDeviceToDevice, ws));
     if (ws != s) {
         HIPCHK(hipEventRecord(ev_out, ws));

@@ -279,6 +279,29 @@ void launch_text_dfa_reset(hipStream_t s, int32_t* state, const TextDfaHdr* hdr,
 void launch_set_text_op_params(hipStream_t s, TextParams* dst, TextParams v, int32_t* step_dst, int step);
 // mode: 0 greedy, 1 Gumbel-max in the scan, 2 scan -> mix -> text_select_kernel (as pg_engine::text_generate picks them)
 void launch_text_constrained(hipStream_t s, const TextArgs& a, const TextDfaArgs& d, int B, int mode, float* scratch_v, int* scratch_i, float* mix);
+// Token log-probabilities (pg_request_token_logprobs / pg_op_token_logprob; definition: include/plangen_hip.h).  The stored-row route: when a
+// call asks for scores, the loop also leaves the row y the draw is made from in the samplers' row workspace (cfg_scan_kernel<true> -> cfg_mix,
+// TEXT_STORE -> txt_mix: the instantiations the top-k / top-p samplers already use) and, after the pick, one 1024-thread block per row reads
+// that row and the emitted token and writes one float: x = y * (1 / temperature) (temperature > 0, else y), NaN as -inf, a max pass and a
+// sum-of-expf pass over the L2-resident row with 16-byte loads, fixed-shape reductions (the result does not depend on scheduling).
+struct LogprobArgs {
+    const float* rows; int V;                                     // [gridDim, V] fp32
+    const SampleParams* sp;                                       // image loop: temperature and T from device memory
+    const TextParams* tp;                                         // text loop: temperature, max_new and eos from device memory
+    float temperature;                                            // operator: from the host
+    const int32_t* tok32;                                         // operator: [gridDim]; image loop: out_tok [B, T]
+    const int64_t* tok64;                                         // text loop: out [B, max_new]
+    const int32_t* n_dec; int b_off;                              // loops: device step counter, first image of this launch
+    float* out;                                                   // operator: [gridDim]; loops: [B, T] / [B, max_new] library-owned
+};
+void launch_token_logprob_op(hipStream_t s, const float* rows, int B, int V, const int32_t* tok, float temperature, float* out);
+// the CFG-mixed rows of this step -> mix [B, V] (cfg_scan_kernel<true>; nothing else is written except the logits_out tap's own values)
+void launch_cfg_store(hipStream_t s, const SampleArgs& a, int B, float* mix);
+void launch_token_logprob_image(hipStream_t s, const SampleArgs& a, int B, const float* mix, float* out);
+// the reduced text rows of this step (EOS ban and, with d != null, the automaton's mask applied) -> mix [B, V] (the TEXT_STORE scan).  It
+// also leaves chunk maxima in scratch_v / scratch_i: launch it BEFORE the step's own scan, which overwrites them with its winners.
+void launch_text_store(hipStream_t s, const TextArgs& a, const TextDfaArgs* d, int B, float* scratch_v, int* scratch_i, float* mix);
+void launch_token_logprob_text(hipStream_t s, const TextArgs& a, int B, const float* mix, float* out);
 void launch_advance(hipStream_t s, int32_t* n_dec);
 void launch_rows_differ(hipStream_t s, const int32_t* ids, int L, int first, int stride, int ref, int n, int from, int32_t* flag);
 void launch_uniform_from_bits(hipStream_t s, const uint64_t* z, float* out, int n);

@@ -1211,6 +1211,121 @@ void launch_text_constrained(hipStream_t s, const TextArgs& a, const TextDfaArgs
     hipLaunchKernelGGL(text_pick_dfa_kernel, dim3(B), dim3(256), 0, s, a, d, scratch_v, scratch_i);
 }
 
+// ------------------------------------------------------------------------------- token log-probabilities
+// logprob = x[tok] - logsumexp(x) of one stored row per block (kernels.h LogprobArgs; the definition is in include/plangen_hip.h).
+// Two passes over the row, which the scan of this step has just written (L2 resident; 400 KiB at vocab 102 400): the maximum, then
+// sum expf(x - max) -- one accurate expf per entry, nothing rescaled.  Eight 16-byte loads in flight per thread as in text_scan_body.h;
+// the row may start at any 4-byte boundary and have any length (scalar head and tail around the aligned vectors).  A thread adds at
+// most V / 1024 terms in index order, then a butterfly over the wave and a serial sum of the 16 wave sums: a fixed shape, so the
+// bits do not depend on how the block was scheduled.  x == max contributes exactly 1 (this is expf(0), and it keeps a row whose
+// maximum is +inf meaningful: the mass sits evenly on the +inf entries).
+#define LP_THREADS 1024
+enum { LP_OP = 0, LP_IMAGE = 1, LP_TEXT = 2 };
+template <int FORM>
+__global__ __launch_bounds__(LP_THREADS) void token_logprob_kernel(LogprobArgs a) {
+    __shared__ float red[LP_THREADS / 64];
+    __shared__ float s_m;
+    const int b = blockIdx.x, tid = threadIdx.x, V = a.V;
+    int tok; float temperature; float* dst;
+    if (FORM == LP_OP) { tok = a.tok32[b]; temperature = a.temperature; dst = a.out + b; }
+    else if (FORM == LP_IMAGE) {
+        const int step = *a.n_dec, T = a.sp->T;
+        if (step >= T) return;
+        const long at = (long)(b + a.b_off) * T + step;
+        tok = a.tok32[at]; temperature = a.sp->temperature; dst = a.out + at;
+    } else {
+        const int step = *a.n_dec, max_new = a.tp->max_new;
+        if (step >= max_new) return;
+        const int64_t* o = a.tok64 + (long)b * max_new;
+        dst = a.out + (long)b * max_new + step;
+        // a finished row emits eos and a row finishes by emitting eos: the row was finished BEFORE this step iff its previous token is eos
+        if (step > 0 && o[step - 1] == (int64_t)a.tp->eos) { if (tid == 0) *dst = 0.f; return; }
+        tok = (int)o[step]; temperature = a.tp->temperature;
+    }
+    const float invT = temperature > 0.f ? 1.f / temperature : 1.f;
+    const float* row = a.rows + (long)b * V;
+    auto xval = [&](float y) -> float { const float x = temperature > 0.f ? __fmul_rn(y, invT) : y; return x != x ? -INFINITY : x; };   // the rounded product, never fused into x - m
+    int head = (int)(((16u - (uint32_t)((uintptr_t)row & 15u)) & 15u) >> 2);
+    if (head > V) head = V;
+    const int nv = (V - head) >> 2, tail0 = head + nv * 4;
+    const f32x4* rv = (const f32x4*)(row + head);
+    constexpr int IT = 8;
+    auto block_reduce = [&](float v, bool is_max) -> float {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const float ov = __shfl_xor(v, o, 64); v = is_max ? fmaxf(v, ov) : v + ov; }
+        __syncthreads();                                   // red / s_m of the previous reduction have been read
+        if ((tid & 63) == 0) red[tid >> 6] = v;
+        __syncthreads();
+        if (tid == 0) {
+            float r = red[0];
+            for (int k = 1; k < LP_THREADS / 64; ++k) r = is_max ? fmaxf(r, red[k]) : r + red[k];
+            s_m = r;
+        }
+        __syncthreads();
+        return s_m;
+    };
+    float m = -INFINITY;
+    for (int i0 = tid; i0 < nv; i0 += IT * LP_THREADS) {
+        f32x4 c[IT];
+#pragma unroll
+        for (int it = 0; it < IT; ++it) { const int i = i0 + it * LP_THREADS; c[it] = rv[i < nv ? i : nv - 1]; }   // clamped: a repeat does not move a maximum
+#pragma unroll
+        for (int it = 0; it < IT; ++it)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) m = fmaxf(m, xval(c[it][j]));
+    }
+    for (int v = tid; v < head; v += LP_THREADS) m = fmaxf(m, xval(row[v]));
+    for (int v = tail0 + tid; v < V; v += LP_THREADS) m = fmaxf(m, xval(row[v]));
+    m = block_reduce(m, true);
+    auto term = [&](float y) -> float { const float x = xval(y); return x == m ? 1.f : expf(x - m); };
+    float sum = 0.f;
+    for (int i0 = tid; i0 < nv; i0 += IT * LP_THREADS) {
+        f32x4 c[IT];
+#pragma unroll
+        for (int it = 0; it < IT; ++it) { const int i = i0 + it * LP_THREADS; c[it] = rv[i < nv ? i : nv - 1]; }
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+            if (i0 + it * LP_THREADS < nv) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) sum += term(c[it][j]);
+            }
+        }
+    }
+    for (int v = tid; v < head; v += LP_THREADS) sum += term(row[v]);
+    for (int v = tail0 + tid; v < V; v += LP_THREADS) sum += term(row[v]);
+    sum = block_reduce(sum, false);
+    if (tid == 0) {
+        const float xt = (tok >= 0 && tok < V) ? xval(row[tok]) : -INFINITY;
+        float lp = -INFINITY;                              // no finite entry, or the token's own entry is -inf
+        if (m > -INFINITY && xt > -INFINITY) lp = (xt == m ? 0.f : xt - m) - logf(sum);
+        *dst = lp;
+    }
+}
+void launch_token_logprob_op(hipStream_t s, const float* rows, int B, int V, const int32_t* tok, float temperature, float* out) {
+    LogprobArgs l{};
+    l.rows = rows; l.V = V; l.temperature = temperature; l.tok32 = tok; l.out = out;
+    hipLaunchKernelGGL(token_logprob_kernel<LP_OP>, dim3(B), dim3(LP_THREADS), 0, s, l);
+}
+void launch_cfg_store(hipStream_t s, const SampleArgs& a, int B, float* mix) {
+    hipLaunchKernelGGL(cfg_scan_kernel<true>, dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, (float*)nullptr, (int*)nullptr, mix);
+}
+void launch_token_logprob_image(hipStream_t s, const SampleArgs& a, int B, const float* mix, float* out) {
+    LogprobArgs l{};
+    l.rows = mix; l.V = a.V; l.sp = a.p; l.tok32 = a.out_tok; l.n_dec = a.n_dec; l.b_off = a.b_off; l.out = out;
+    hipLaunchKernelGGL(token_logprob_kernel<LP_IMAGE>, dim3(B), dim3(LP_THREADS), 0, s, l);
+}
+void launch_text_store(hipStream_t s, const TextArgs& a, const TextDfaArgs* d, int B, float* scratch_v, int* scratch_i, float* mix) {
+    if (d) {
+        TextDfaArgs dd = *d; dd.keep = nullptr;
+        launch_text_scan_dfa<TEXT_STORE>(s, a, dd, B, scratch_v, scratch_i, mix);
+    } else launch_text_scan<TEXT_STORE>(s, a, B, scratch_v, scratch_i, mix);
+}
+void launch_token_logprob_text(hipStream_t s, const TextArgs& a, int B, const float* mix, float* out) {
+    LogprobArgs l{};
+    l.rows = mix; l.V = a.V; l.tp = a.p; l.tok64 = a.out; l.n_dec = a.n_dec; l.out = out;
+    hipLaunchKernelGGL(token_logprob_kernel<LP_TEXT>, dim3(B), dim3(LP_THREADS), 0, s, l);
+}
+
 // test tap: the sampler's uniform / Gumbel transform of raw 64-bit RNG outputs: out[i] = u, out[n+i] = -log(-log(u))
 __global__ void uniform_from_bits_kernel(const uint64_t* __restrict__ z, float* __restrict__ out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -419,12 +419,15 @@ class Engine:
     def decode_image_tokens(self, T: Optional[int] = None, cfg_weight: float = 5.0, temperature: float = 0.0,
                             seed: int = 0, force_tokens: Optional[torch.Tensor] = None,
                             force_mask: Optional[torch.Tensor] = None, return_logits: bool = False,
-                            top_k: int = 0, top_p: float = 1.0):
+                            top_k: int = 0, top_p: float = 1.0, return_logprobs: bool = False):
         """The fused CFG decode loop.  top_k / top_p filter the sampled draws (temperature > 0; HF order temperature ->
-        top-k -> top-p); (0, 1.0) is the unfiltered sampler.  Semantics: include/plangen_hip.h."""
+        top-k -> top-p); (0, 1.0) is the unfiltered sampler.  return_logprobs: also fp32 [B, T], the log-probability of every emitted
+        token under softmax(mixed / temperature) before the filters (``pg_request_token_logprobs``); with ``force_mask = zeros`` it is the
+        log-likelihood of ``force_tokens``.  Semantics: include/plangen_hip.h."""
         T = self.cfg.img_tokens if T is None else T
         B = self.R // 2
         out = torch.zeros((B, T), dtype=torch.int32, device=self.device)
+        lp = self._request_logprobs((B, T)) if return_logprobs else None
         ft = self._dev(force_tokens, torch.int32) if force_tokens is not None else None
         fm = self._dev(force_mask, torch.uint8) if force_mask is not None else None
         lg = torch.zeros((T, B, self.cfg.img_vocab), dtype=torch.float32, device=self.device) if return_logits else None
@@ -436,24 +439,49 @@ class Engine:
             self._check(self.lib.pg_decode_image_tokens_filtered(self.h, T, float(cfg_weight), float(temperature), int(top_k),
                                                                  float(top_p), int(seed), self._p(ft), self._p(fm), self._p(out),
                                                                  self._p(lg), self.stream), "pg_decode_image_tokens_filtered")
-        self._keep = [ft, fm, out, lg]
-        return (out, lg) if return_logits else out
+        self._keep = [ft, fm, out, lg, lp]
+        res = (out,) + ((lg,) if return_logits else ()) + ((lp,) if return_logprobs else ())
+        return res if len(res) > 1 else res[0]
+
+    def _request_logprobs(self, shape) -> torch.Tensor:
+        """``pg_request_token_logprobs`` for the next decode / generate call: the fp32 tensor that call fills (NaN where it writes nothing)."""
+        lp = torch.full(shape, float("nan"), dtype=torch.float32, device=self.device)
+        self._check(self.lib.pg_request_token_logprobs(self.h, self._p(lp), lp.numel()), "pg_request_token_logprobs")
+        return lp
+
+    def token_logprob(self, x: torch.Tensor, tok: torch.Tensor, temperature: float = 0.0) -> torch.Tensor:
+        """``pg_op_token_logprob``: the loops' scoring kernel over fp32 rows ``x`` [B, V] and tokens ``tok`` [B] -> fp32 [B],
+        log softmax(x / temperature)[tok] (temperature <= 0: of x itself); a token outside [0, V) gives -inf."""
+        x = self._dev(x, torch.float32).reshape(-1, x.shape[-1]).contiguous()
+        B, V = x.shape
+        t = self._dev(torch.as_tensor(tok), torch.int32).reshape(-1).contiguous()
+        if t.numel() != B:
+            raise PlanGenError(f"token_logprob: {t.numel()} tokens for {B} rows")
+        out = torch.full((B,), float("nan"), dtype=torch.float32, device=self.device)
+        self._check(self.lib.pg_op_token_logprob(self.h, self._p(x), B, V, self._p(t), float(temperature), self._p(out), self.stream),
+                    "pg_op_token_logprob")
+        self._keep = [x, t, out]
+        return out
 
     def generate_text(self, max_new_tokens: int, eos_id: int, min_new_tokens: int = 0, temperature: float = 0.0, top_k: int = 0,
-                      top_p: float = 1.0, seed: int = 0, return_logits: bool = False):
+                      top_p: float = 1.0, seed: int = 0, return_logits: bool = False, return_logprobs: bool = False):
         """The text decode loop after a ``prefill*(position_mode=1)``: new tokens only, int64 [R, n <= max_new_tokens], finished rows
         padded with eos.  temperature <= 0: greedy (``generate_text_greedy``, bit for bit).  temperature > 0: sampled in HF's order
         (min_new EOS suppression -> temperature -> top-k -> top-p -> draw), keyed on (seed, row + the ``rng_image_offset`` option, step):
         a row's tokens do not depend on the other rows, and two rows that carry the same prompt draw different texts.
-        return_logits: also fp32 [n, R, vocab], the logits every emitted token was drawn from.  Semantics: include/plangen_hip.h."""
+        return_logits: also fp32 [n, R, vocab], the logits every emitted token was drawn from.  return_logprobs: also fp32 [R, n], every
+        emitted token's log-probability (0.0 once a row has finished, so a row's sum is its sequence log-probability).  Semantics:
+        include/plangen_hip.h."""
         out = torch.full((self.R, max_new_tokens), eos_id, dtype=torch.int64, device=self.device)
         lg = torch.zeros((max_new_tokens, self.R, self.cfg.vocab), dtype=torch.float32, device=self.device) if return_logits else None
+        lp = self._request_logprobs((self.R, max_new_tokens)) if return_logprobs else None
         n = C.c_int(0)
         self._check(self.lib.pg_generate_text_sampled(self.h, max_new_tokens, min_new_tokens, eos_id, float(temperature), int(top_k),
                                                       float(top_p), int(seed), self._p(out), C.byref(n), self._p(lg), self.stream),
                     "pg_generate_text_sampled")
-        self._keep = [out, lg]
-        return (out[:, :n.value], lg[:n.value]) if return_logits else out[:, :n.value]
+        self._keep = [out, lg, lp]
+        res = (out[:, :n.value],) + ((lg[:n.value],) if return_logits else ()) + ((lp[:, :n.value],) if return_logprobs else ())
+        return res if len(res) > 1 else res[0]
 
     def set_text_dfa(self, dfa) -> None:
         """pg_set_text_dfa: upload a token automaton (``grammar.TokenDFA`` or anything with ``token_class`` [vocab], ``next_state``
@@ -476,20 +504,23 @@ class Engine:
         self.uploaded_dfa = dfa
 
     def generate_text_constrained(self, max_new_tokens: int, eos_id: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
-                                  seed: int = 0, return_logits: bool = False, return_state: bool = False):
+                                  seed: int = 0, return_logits: bool = False, return_state: bool = False, return_logprobs: bool = False):
         """``generate_text`` under the automaton of ``set_text_dfa``: disallowed tokens are -inf before temperature / top-k / top-p, a row
         only moves to states it can still finish from, so every row ends with eos inside ``max_new_tokens`` (needs dist[start] <=
-        max_new_tokens).  return_logits: also the masked rows fp32 [n, R, vocab]; return_state: also the final states int32 [R].
-        Semantics: include/plangen_hip.h."""
+        max_new_tokens).  return_logits: also the masked rows fp32 [n, R, vocab]; return_state: also the final states int32 [R];
+        return_logprobs: also (last) fp32 [R, n], every emitted token's log-probability over the ALLOWED tokens (0.0 once a row has
+        finished).  Semantics: include/plangen_hip.h."""
         out = torch.full((self.R, max_new_tokens), eos_id, dtype=torch.int64, device=self.device)
         lg = torch.zeros((max_new_tokens, self.R, self.cfg.vocab), dtype=torch.float32, device=self.device) if return_logits else None
         st = torch.full((self.R,), -1, dtype=torch.int32, device=self.device) if return_state else None
+        lp = self._request_logprobs((self.R, max_new_tokens)) if return_logprobs else None
         n = C.c_int(0)
         self._check(self.lib.pg_generate_text_constrained(self.h, max_new_tokens, eos_id, float(temperature), int(top_k), float(top_p),
                                                           int(seed), self._p(out), C.byref(n), self._p(st), self._p(lg), self.stream),
                     "pg_generate_text_constrained")
-        self._keep = [out, lg, st]
-        res = (out[:, :n.value],) + ((lg[:n.value],) if return_logits else ()) + ((st,) if return_state else ())
+        self._keep = [out, lg, st, lp]
+        res = (out[:, :n.value],) + ((lg[:n.value],) if return_logits else ()) + ((st,) if return_state else ()) \
+            + ((lp[:, :n.value],) if return_logprobs else ())
         return res if len(res) > 1 else res[0]
 
     def generate_text_greedy(self, max_new_tokens: int, eos_id: int, min_new_tokens: int = 0) -> torch.Tensor:

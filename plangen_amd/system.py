@@ -73,7 +73,9 @@ class System:
     args carries the cfg keys the path reads (cfg/base.py): seed, parallel_size, cfg_weight,
     temperature, use_teacher_forcing, debug_max_seq_len, janus_hw; optionally share_replicas (parallel_size > 1: prefill every prompt once,
     off when absent), top_k / top_p (image sampling filters, off when absent)
-    and text_temperature / text_top_k / text_top_p (sampled layout / caption decode, greedy when absent).
+    and text_temperature / text_top_k / text_top_p (sampled layout / caption decode, greedy when absent); select_best (parallel_size > 1:
+    keep each prompt's most probable replica, off when absent) and layout_best_of (stage 1: draw N layouts per row and keep the most
+    probable, 1 when absent).
     """
 
     def __init__(self, cfg: PlanGenConfig, engine: Engine, args: Optional[SimpleNamespace] = None, codec=None):
@@ -81,6 +83,7 @@ class System:
         self.engine = engine
         self.codec = codec                # tokenizer (plangen_amd.textproc.HFCodec / TagWordCodec); None: ids only
         self.last_generated_tokens = None
+        self.last_selection = None        # select_best: dict(replica int64 [B0], score fp32 [B0], scores fp32 [p, B0]) of the last t2i
         self.vl_gpt = MultiModalityCausalLM(engine)
         self.args = args or SimpleNamespace(seed=cfg.seed, parallel_size=1, cfg_weight=cfg.cfg_weight,
                                             temperature=cfg.temperature, top_k=cfg.top_k, top_p=cfg.top_p, use_teacher_forcing=False,
@@ -102,12 +105,13 @@ class System:
                      seed: int = 0, edit_region: Optional[torch.Tensor] = None,
                      gt_labels: Optional[torch.Tensor] = None, force_tokens: Optional[torch.Tensor] = None,
                      n_tokens: Optional[int] = None, return_logits: bool = False, top_k: Optional[int] = None,
-                     top_p: Optional[float] = None, replicas: int = 1, alias: bool = True):
+                     top_p: Optional[float] = None, replicas: int = 1, alias: bool = True, return_logprobs: bool = False):
         """The 576-step CFG loop, fused on device (one pg_prefill + one pg_decode_image_tokens).
         tokens int32 [2B, L] CFG-interleaved ids, mask [2B, L+T].  temperature<=0 -> greedy.
         top_k / top_p (default: self.args, else off) filter the sampled draws.
         replicas > 1: ``tokens`` is the UN-replicated batch [2B0, L] and the loop runs on replicas * 2B0 rows (row t * 2B0 + r = replica t of
-        row r) with every prompt prefilled once (Engine.prefill_replicated); mask / edit_region / gt_labels / force_tokens are the replicated ones."""
+        row r) with every prompt prefilled once (Engine.prefill_replicated); mask / edit_region / gt_labels / force_tokens are the replicated ones.
+        return_logprobs: the emitted tokens' log-probabilities fp32 [B, T] are appended to what is returned."""
         top_k = getattr(self.args, "top_k", 0) if top_k is None else top_k
         top_p = getattr(self.args, "top_p", 1.0) if top_p is None else top_p
         L = tokens.shape[1]
@@ -122,7 +126,31 @@ class System:
             ft, fm = gt_labels, (edit_region != 0).to(torch.uint8)
         elif force_tokens is not None:
             ft = force_tokens
-        return self.engine.decode_image_tokens(n_tokens, cfg_weight, temperature, seed, ft, fm, return_logits, top_k=top_k, top_p=top_p)
+        lpkw = {"return_logprobs": True} if return_logprobs else {}        # without it: exactly the call made before scores existed
+        return self.engine.decode_image_tokens(n_tokens, cfg_weight, temperature, seed, ft, fm, return_logits, top_k=top_k, top_p=top_p, **lpkw)
+
+    @staticmethod
+    def select_best_replicas(logprobs: torch.Tensor, p: int, scored: Optional[torch.Tensor] = None):
+        """The select_best rule on the device.  logprobs fp32 [p * B0, T] in the replica layout (row t * B0 + i = replica t of prompt i);
+        scored bool [B0, T] or None: the positions that count (teacher forcing: the positions that were NOT forced -- the first replica is
+        forced there, and the others are scored on the same positions so that the means compare).  A replica's score is the mean of its
+        scored log-probs (0 scored positions: 0.0); per prompt the arg-max wins, ties go to the lowest t, and a replica with a -inf
+        token (score -inf) loses to any finite one.  Returns (rows int64 [B0] = t * B0 + i, replica int64 [B0], scores fp32 [p, B0])."""
+        n, T = logprobs.shape
+        B0 = n // p
+        lp = logprobs.view(p, B0, T)
+        if scored is None:
+            scores = lp.sum(-1) / T
+        else:
+            m = scored.to(lp.device).bool().reshape(1, B0, T)
+            scores = torch.where(m, lp, torch.zeros_like(lp)).sum(-1) / m.sum(-1).clamp(min=1)
+        scores = torch.nan_to_num(scores, nan=float("-inf"), posinf=float("inf"), neginf=float("-inf"))
+        # first maximum along t: max over (score, -t) -- torch.argmax's choice among equal values is not part of its contract on every device
+        best = scores.max(0, keepdim=True).values
+        t_idx = torch.arange(p, device=lp.device).view(p, 1).expand(p, B0)
+        replica = torch.where(scores == best, t_idx, torch.full_like(t_idx, p)).min(0).values
+        rows = replica * B0 + torch.arange(B0, device=lp.device)
+        return rows, replica, scores
 
     @torch.no_grad()
     def sample_image_stepwise(self, inputs_embeds: torch.Tensor, mask: torch.Tensor, cfg_weight: float,
@@ -154,7 +182,10 @@ class System:
         """System.t2i (plangen_base.py:525-565): (teacher forcing: VQ-encode the ground truth :528-532) -> replicate x
         parallel_size (:547) -> sample_image -> decode_code (:555).  Returns ``(dec, mask_image)`` like the reference:
         dec [B*p,3,S,S] fp32; mask_image = the edit region resized to janus_hw (:557-560) under use_teacher_forcing,
-        else None.  The generated tokens stay in ``self.last_generated_tokens`` (int32 [B*p, T])."""
+        else None.  The generated tokens stay in ``self.last_generated_tokens`` (int32 [B*p, T]).
+        args.select_best with p > 1: the loop also returns every token's log-probability, each prompt keeps the replica with the highest
+        mean (``select_best_replicas``; a device arg-max + gather, no host round trip) and ONLY those B rows go through the VQ decoder:
+        dec is [B,3,S,S] in prompt order, ``last_generated_tokens`` [B, T], and ``self.last_selection`` holds replica / score / scores."""
         a = self.args
         cfg_weight = a.cfg_weight if cfg_weight is None else cfg_weight
         temperature = a.temperature if temperature is None else temperature
@@ -171,7 +202,10 @@ class System:
         # share_replicas (cfg key, default 0): the ids stay un-replicated and every prompt is prefilled once; the mask, the forced labels and the
         # all-ones regions of replicas 2..p are built as below either way
         share = p > 1 and bool(int(getattr(a, "share_replicas", 0)))
-        num_gen = tokens.shape[0] // 2 * p
+        B0 = tokens.shape[0] // 2
+        num_gen = B0 * p
+        select = p > 1 and bool(getattr(a, "select_best", False))
+        self.last_selection = None
         if p > 1:
             if not share:
                 tokens = torch.cat([tokens] * p)
@@ -184,7 +218,14 @@ class System:
                 force_region = torch.cat([edit_region] + [torch.ones_like(edit_region)] * (p - 1))
         toks = self.sample_image(tokens, mask, cfg_weight, temperature, a.seed,
                                  force_region if gt_labels is not None else None, gt_labels, top_k=top_k, top_p=top_p,
-                                 replicas=p if share else 1)
+                                 replicas=p if share else 1, **({"return_logprobs": True} if select else {}))
+        if select:
+            toks, lp = toks
+            scored = (edit_region != 0).reshape(B0, -1) if gt_labels is not None else None
+            rows, replica, scores = self.select_best_replicas(lp, p, scored)
+            toks = toks.index_select(0, rows)
+            num_gen = B0
+            self.last_selection = dict(replica=replica, score=scores.gather(0, replica.view(1, B0))[0], scores=scores)
         dec = self.vl_gpt.gen_vision_model.decode_code(toks.to(dtype=torch.int),
                                                        shape=[num_gen, self.cfg.img_dim, self.cfg.grid, self.cfg.grid])
         self.last_generated_tokens = toks
@@ -265,8 +306,25 @@ class System:
                     raise PlanGenError("layout_grammar needs a tokenizer (System(codec=...)): the automaton is built over its vocabulary")
                 from .grammar import layout_token_dfa
                 dfa = layout_token_dfa(self.codec, self.cfg.vocab)
+            best_of = 1 if is_mmu else int(getattr(self.args, "layout_best_of", 1))
+            if best_of > 1:
+                # draw N layouts per row and keep the one the model finds most probable: the batch is replicated like parallel_size replicates
+                # images (row t * B + i = draw t of row i; different global rows, hence different draws), generated with log-probs, and each row
+                # is scored by its sequence log-probability / its number of scored tokens (up to and including its EOS)
+                nb = emb.shape[0]
+                if not float(getattr(self.args, "text_temperature", 0.0)) > 0:
+                    raise PlanGenError(f"layout_best_of={best_of} needs text_temperature > 0: greedy decode would draw the same layout {best_of} times")
+                if best_of * nb > self.engine.max_rows:
+                    raise PlanGenError(f"layout_best_of={best_of} x {nb} stage-1 rows = {best_of * nb} rows exceed the engine's max_rows={self.engine.max_rows}")
+                emb = torch.cat([emb] * best_of)
+                attention_mask = torch.cat([attention_mask] * best_of)
             outputs = self.x2t(emb, attention_mask.to(dev), max_new_tokens=max_new_tokens, min_new_tokens=min_new_tokens,
-                               **({} if dfa is None else {"dfa": dfa}))
+                               **({} if dfa is None else {"dfa": dfa}), **({} if best_of == 1 else {"return_logprobs": True}))
+            if best_of > 1:
+                outputs, lp = outputs
+                rows_best, replica, score = self.select_best_layouts(outputs, lp, best_of, self.cfg.eos_id)
+                outputs = outputs.index_select(0, rows_best)
+                out["pr_layout_replica"], out["pr_layout_score"] = replica, score
             out["pr_text_ids" if is_mmu else "pr_layout_ids"] = outputs
             rows = outputs.cpu().tolist()
             if self.codec is not None:
@@ -304,6 +362,8 @@ class System:
             cfg_ids, cfg_mask = self.t2i_infer_collate_batch(cond, neg)
             dec, edit_mask = self.t2i(cfg_ids, cfg_mask, gt_image=batch.get("image"), edit_region=batch.get("edit_region"))
             out["pr_tokens"] = self.last_generated_tokens
+            if self.last_selection is not None:
+                out["pr_replica"], out["pr_score"] = self.last_selection["replica"], self.last_selection["score"]
             out["pr_image"] = dec.float()
             out["edit_mask"] = edit_mask
         else:
@@ -315,19 +375,36 @@ class System:
             import os
             os.makedirs(gen_path, exist_ok=True)
             with open(os.path.join(gen_path, f"{batch_idx}_layout.json"), "w") as f:
+                extra = {k: out[k].cpu().tolist() for k in ("pr_replica", "pr_score", "pr_layout_replica", "pr_layout_score") if k in out}
                 json.dump(dict(base_caption=base_caption, gt_grounding=batch.get("gt_grounding"),
-                               pr_grounding=pr_grounding if pred_layout else ""), f)
+                               pr_grounding=pr_grounding if pred_layout else "", **extra), f)
         return out
+
+    @staticmethod
+    def select_best_layouts(tokens: torch.Tensor, logprobs: torch.Tensor, n: int, eos_id: int):
+        """The layout_best_of rule.  tokens int64 [n * B, L] and logprobs fp32 [n * B, L] of one replicated stage-1 batch (row t * B + i =
+        draw t of row i).  A row's score = sum of its log-probs (finished columns are 0.0) / the number of scored columns = up to and
+        including its first EOS (L when it has none).  Per row the arg-max wins, ties -> the lowest t, -inf loses to any finite score.
+        Returns (rows int64 [B], replica int64 [B], score fp32 [B])."""
+        N, L = tokens.shape
+        B = N // n
+        is_eos = tokens == eos_id
+        first = torch.where(is_eos.any(-1), is_eos.int().argmax(-1) + 1, torch.full((N,), L, device=tokens.device))
+        total = logprobs.sum(-1) if L else logprobs.new_zeros((N,))
+        score = total / first.clamp(min=1)
+        rows, replica, scores = System.select_best_replicas(score.view(N, 1), n)
+        return rows, replica, scores.gather(0, replica.view(1, B))[0]
 
     @torch.no_grad()
     def x2t(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
             max_new_tokens: int = 512, min_new_tokens: int = 0, temperature: Optional[float] = None,
-            top_k: Optional[int] = None, top_p: Optional[float] = None, dfa=None) -> torch.Tensor:
+            top_k: Optional[int] = None, top_p: Optional[float] = None, dfa=None, return_logprobs: bool = False) -> torch.Tensor:
         """System.x2t (:513-523): text / layout-token decode.  Greedy like the reference unless ``text_temperature`` > 0 (argument,
         else self.args, else 0): then every row is sampled with ``text_top_k`` / ``text_top_p`` (HF order temperature -> top-k -> top-p)
         from seed = args.seed, the seed t2i uses.  The draw is keyed on the row's index in the batch, so two rows that carry the same
         prompt get different layouts: repeat a caption N times in one batch for N layouts of it.
-        ``dfa`` (grammar.TokenDFA): the decode is constrained to the automaton's language, greedy or sampled (``layout_grammar``)."""
+        ``dfa`` (grammar.TokenDFA): the decode is constrained to the automaton's language, greedy or sampled (``layout_grammar``).
+        return_logprobs: returns (tokens, fp32 [B, n] log-probabilities of the emitted tokens, 0.0 once a row has finished)."""
         a = self.args
         temperature = float(getattr(a, "text_temperature", 0.0)) if temperature is None else float(temperature)
         top_k = int(getattr(a, "text_top_k", 0)) if top_k is None else int(top_k)
@@ -337,6 +414,8 @@ class System:
             kw = dict(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, seed=int(getattr(a, "seed", 0)))
         if dfa is not None:
             kw["dfa"] = dfa
+        if return_logprobs:
+            kw["return_logprobs"] = True
         return self.vl_gpt.language_model.generate(inputs_embeds=inputs_embeds, attention_mask=attention_mask,
                                                    pad_token_id=self.cfg.eos_id, bos_token_id=None,
                                                    eos_token_id=self.cfg.eos_id, max_new_tokens=max_new_tokens,

@@ -58,6 +58,8 @@ class System(_HotPath):
         cfg.layout_grammar = bool(getattr(args, "layout_grammar", False))
         cfg.kv_dtype = str(getattr(args, "kv_dtype", "bf16"))
         cfg.share_replicas = int(getattr(args, "share_replicas", 0))
+        select_best = bool(getattr(args, "select_best", False))
+        layout_best_of = max(1, int(getattr(args, "layout_best_of", 1)))
         bs = int(args.test_batch_size)
         device = int(os.environ.get("LOCAL_RANK", "0"))
         self.synthetic = td.get("data_name") == "synthetic" or bool(getattr(args, "synthetic", False))
@@ -71,7 +73,9 @@ class System(_HotPath):
             codec = None            # pre-tokenised rows only; text steps raise a clear error
         text_new = int(getattr(args, "max_new_tokens", 512))
         needs_image = task in ("t2i", "uni", "uni_2stage")
-        eng = Engine(cfg, dtype=args.dtype, max_rows=2 * bs * int(args.parallel_size), max_prompt=int(getattr(args, "max_prompt", 768)),
+        # rows: the CFG batch of every replica, or the stage-1 batch with layout_best_of draws per row, whichever is larger
+        stage1 = task in ("uni_2stage", "plan")
+        eng = Engine(cfg, dtype=args.dtype, max_rows=max(2 * bs * int(args.parallel_size), bs * layout_best_of if stage1 else 0), max_prompt=int(getattr(args, "max_prompt", 768)),
                      max_new=max(cfg.img_tokens if needs_image else 1, text_new if task != "uni" and task != "t2i" else 1),
                      max_images=bs * int(args.parallel_size), with_lm_head=task in ("uni_2stage", "mmu", "plan"),
                      with_vq_encoder=bool(args.use_teacher_forcing), with_vision=task == "mmu", device=device,
@@ -79,7 +83,7 @@ class System(_HotPath):
         super().__init__(cfg, eng, SimpleNamespace(seed=args.seed, parallel_size=args.parallel_size, cfg_weight=args.cfg_weight,
                                                    temperature=args.temperature, top_k=cfg.top_k, top_p=cfg.top_p,
                                                    text_temperature=cfg.text_temperature, text_top_k=cfg.text_top_k, text_top_p=cfg.text_top_p,
-                                                   layout_grammar=cfg.layout_grammar,
+                                                   layout_grammar=cfg.layout_grammar, select_best=select_best, layout_best_of=layout_best_of,
                                                    use_teacher_forcing=args.use_teacher_forcing, share_replicas=cfg.share_replicas,
                                                    debug_max_seq_len=args.debug_max_seq_len, janus_hw=args.janus_hw,
                                                    neg_prompt=getattr(args, "neg_prompt", ""),
@@ -286,6 +290,8 @@ class System(_HotPath):
             layouts.append(out.get("pr_grounding"))
             bs = len(image_id)
             p = int(a.parallel_size)
+            if "pr_replica" in out:            # select_best: one image per prompt came back, the tree is parallel_size = 1's
+                p = 1
             for i in range(bs):
                 if pr_image is not None:
                     if image_id[i] != "":
