@@ -2,7 +2,9 @@
 // pair and slab-folding elementwise kernels (tests/test_gpu_decode_ops.py), of the VQ-16 decoder kernels (tests/test_gpu_vq_ops.py) and of the prefill
 // GEMM epilogues -- RoPE + KV write (act 3), SwiGLU (act 2), rope_kv_kernel alone and the two weight interleavers (tests/test_gpu_prefill_ops.py) -- and of
 // the understanding path's input-side kernels (SigLIP LayerNorm / patchify / add_pos, the VQ encoder's conv_in and nearest-code search, l2norm_rows, the
-// two-level batched GEMM of SigLIP's scores and P . V: tests/test_gpu_vision_ops.py) for the operator tests.  Each one points the calling thread's pg_tune at a local PgTune (no diagnostics hooks, one kernel-form selector set), calls the PRODUCTION launcher and restores
+// two-level batched GEMM of SigLIP's scores and P . V: tests/test_gpu_vision_ops.py) and of the decode GEMM dispatch itself -- launch_gemm_skinny /
+// launch_gemm_skinny_swiglu on the tiled copy or on row-major weights, with the caller's split count and stream_gemm mask: tests/test_gpu_skinny_ops.py --
+// for the operator tests.  Each one points the calling thread's pg_tune at a local PgTune (no diagnostics hooks, one kernel-form selector set), calls the PRODUCTION launcher and restores
 // pg_tune.  Shapes the kernels do not support are refused with PG_ERR_ARG and never launched.  Head dimension: 128 for the LLM kernels (implied
 // by the [.., nh * 128] layouts), 64 for SigLIP (C / NH).  Row lengths, slots and token maps live in device memory; they are copied back and
 // checked on the host before anything is launched (these are test entry points: the synchronisation does not matter).
@@ -754,6 +756,33 @@ int pg_diag_op_gemm_heads(int engine_bf16, int form, const void* A, long lda, lo
                           float* stats, float eps, int* nsplit_out, pg_stream stream) {
     return gemm_epi_impl(engine_bf16, form, A, lda, strideA, W, ldb, strideB, out, out_f32, ldc, strideC, bias_n, bias_m, residual, res_f32, ldr, strideR, scale, act,
                          M, N, K, batch, batch2, strideA2, strideB2, strideC2, gn_hw, ws, ws_floats, stats, eps, nsplit_out, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ decode GEMM dispatch (tests/test_gpu_skinny_ops.py)
+// The skinny decode GEMMs through their production launchers.  x bf16 [M][K], W_rowmajor bf16 [N][K].  form 0: launch_gemm_skinny with a tiled copy built by
+// launch_tile_weights, as pg_finalize_weights / pg_op_gemm kind 4 do (the decode dispatch: v4, v3 on the tiled copy); form 1: launch_gemm_skinny with Wt == nullptr
+// (row-major v3, which falls back to v1 when the chunk count has no instantiation); out fp32 [S][M][N], slab s at out + s M N.  form 2 / 3: launch_gemm_skinny_swiglu
+// with / without the tiled copy, S == 1, W rows already [8 gate | 8 up] interleaved, out bf16 [M][N / 2]; PG_ERR_ARG, out untouched, when the launcher has no fused
+// instantiation for the shape.  stream_gemm: PgTune::stream_gemm (-1 auto, else the bit mask of gemm.hip sk4_prod).  S is the caller's, not skinny_pick_splits'.
+// M <= 512 is what pg_engine::gemm_llm sends this way.  Synchronises the stream before it returns.
+int pg_diag_op_gemm_skinny(int form, int stream_gemm, const void* x, const void* W_rowmajor, void* out, int M, int N, int K, int S, pg_stream stream) {
+    if (!x || !W_rowmajor || !out || form < 0 || form > 3) return PG_ERR_ARG;
+    if (!aligned16({x, W_rowmajor, out})) return PG_ERR_ARG;                                          // 16-byte x / W loads (LDS-DMA in v4), 16-byte slab stores
+    if (M < 1 || M > 512 || N < 16 || (N & 15) || K < SK_BK || (K % SK_BK) || S < 1 || (K / SK_BK) % S) return PG_ERR_ARG;
+    if ((long)N * K > 0x7fffffffL || (form >= 2 && S != 1)) return PG_ERR_ARG;
+    LocalTune lt;
+    lt.t.stream_gemm = stream_gemm;
+    const hipStream_t s = (hipStream_t)stream;
+    Scratch wt;
+    if (form == 0 || form == 2) {
+        if (!wt.get((size_t)N * K * 2)) return PG_ERR_HIP;
+        launch_tile_weights(s, (const bf16*)W_rowmajor, (bf16*)wt.p, N, K);
+    }
+    bool ok = true;
+    if (form < 2) launch_gemm_skinny(s, (const bf16*)x, (const bf16*)W_rowmajor, (float*)out, M, N, K, S, (const bf16*)wt.p);
+    else ok = launch_gemm_skinny_swiglu(s, (const bf16*)x, (const bf16*)W_rowmajor, (bf16*)out, M, N, K, (const bf16*)wt.p);
+    const int rc = finish(s);                                                                        // before the tiled copy goes away
+    return ok ? rc : PG_ERR_ARG;
 }
 
 }  // extern "C"
