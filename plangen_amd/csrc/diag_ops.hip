@@ -4,6 +4,7 @@
 // the understanding path's input-side kernels (SigLIP LayerNorm / patchify / add_pos, the VQ encoder's conv_in and nearest-code search, l2norm_rows, the
 // two-level batched GEMM of SigLIP's scores and P . V: tests/test_gpu_vision_ops.py) and of the decode GEMM dispatch itself -- launch_gemm_skinny /
 // launch_gemm_skinny_swiglu on the tiled copy or on row-major weights, with the caller's split count and stream_gemm mask: tests/test_gpu_skinny_ops.py --
+// and of the samplers' draw -- launch_cfg_sample / launch_cfg_sample_filtered and launch_text_argmax / launch_text_sample on the caller's slabs: tests/test_gpu_draws.py --
 // for the operator tests.  Each one points the calling thread's pg_tune at a local PgTune (no diagnostics hooks, one kernel-form selector set), calls the PRODUCTION launcher and restores
 // pg_tune.  Shapes the kernels do not support are refused with PG_ERR_ARG and never launched.  Head dimension: 128 for the LLM kernels (implied
 // by the [.., nh * 128] layouts), 64 for SigLIP (C / NH).  Row lengths, slots and token maps live in device memory; they are copied back and
@@ -783,6 +784,71 @@ int pg_diag_op_gemm_skinny(int form, int stream_gemm, const void* x, const void*
     else ok = launch_gemm_skinny_swiglu(s, (const bf16*)x, (const bf16*)W_rowmajor, (bf16*)out, M, N, K, (const bf16*)wt.p);
     const int rc = finish(s);                                                                        // before the tiled copy goes away
     return ok ? rc : PG_ERR_ARG;
+}
+
+// ------------------------------------------------------------------------------------------------ the samplers' draw (tests/test_gpu_draws.py)
+// The image sampler's step through its production launchers: launch_cfg_sample, or launch_cfg_sample_filtered when filtered != 0, on the caller's buffers.
+// partial fp32: slab s at partial + s * slab, rows [2B][V] (row 2b = cond, 2b + 1 = uncond), slab >= 2 B V; bias fp32 [V] or null; force_tok int32 [B_total][T] or
+// null (has_force), force_mask uint8 [B_total][T] or null (has_mask; needs force_tok); out_tok int32 [B_total][T]; logits_out fp32 [T][B_total][V] or null (then
+// step < T); embed_table fp32 [V][H]; x fp32 [2B][H].  The launch covers images [b_off, b_off + B) of B_total.  SampleParams, the step counter, the 16 B winner
+// slots and (filtered) the mixed rows are allocated here.  Synchronises the stream before it returns.
+int pg_diag_op_cfg_sample(int filtered, const float* partial, int S, long slab, const float* bias, int V, int B, const int32_t* force_tok, const uint8_t* force_mask,
+                          int32_t* out_tok, float* logits_out, const float* embed_table, float* x, int H, float cfg_weight, float temperature, uint64_t seed,
+                          int top_k, float top_p, int T, int step, int img_off, int b_off, int B_total, pg_stream stream) {
+    if (!partial || !out_tok || !embed_table || !x || (force_mask && !force_tok)) return PG_ERR_ARG;
+    if (S < 1 || V < 1 || B < 1 || B > kMaxGridYZ / 2 || H < 4 || (H & 3) || T < 1 || step < 0 || img_off < 0 || b_off < 0 || B_total < 1) return PG_ERR_ARG;
+    if ((long)b_off + B > B_total || slab < 2L * B * V || (long)V * H >= (1L << 40) || !aligned16({embed_table, x})) return PG_ERR_ARG;
+    if (logits_out && step >= T) return PG_ERR_ARG;                                                  // the tap has T steps
+    if (!(cfg_weight == cfg_weight) || !(temperature == temperature)) return PG_ERR_ARG;
+    if (filtered && (V > SEL_MAXV || !(temperature > 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f))) return PG_ERR_ARG;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    Scratch sp, nd, pv, pi, mix;
+    if (!sp.get(sizeof(SampleParams)) || !nd.get(4) || !pv.get((size_t)B * 16 * 4) || !pi.get((size_t)B * 16 * 4)) return PG_ERR_HIP;
+    if (filtered && !mix.get((size_t)B * V * 4)) return PG_ERR_HIP;
+    const int32_t hstep = step;
+    if (hipMemcpy(nd.p, &hstep, 4, hipMemcpyHostToDevice) != hipSuccess) return PG_ERR_HIP;
+    SampleParams p{};
+    p.cfg_weight = cfg_weight; p.temperature = temperature; p.seed = seed; p.T = T; p.has_force = force_tok != nullptr; p.has_mask = force_mask != nullptr;
+    p.img_off = img_off; p.top_k = top_k; p.top_p = top_p;
+    launch_set_sample_params(s, (SampleParams*)sp.p, p);
+    SampleArgs a{};
+    a.logits_partial = partial; a.S = S; a.slab = slab; a.bias = bias; a.V = V; a.p = (const SampleParams*)sp.p;
+    a.force_tok = force_tok; a.force_mask = force_mask; a.out_tok = out_tok; a.logits_out = logits_out;
+    a.embed_table = embed_table; a.x = x; a.H = H; a.n_dec = (const int32_t*)nd.p; a.b_off = b_off; a.B_total = B_total;
+    if (filtered) launch_cfg_sample_filtered(s, a, B, (float*)pv.p, (int*)pi.p, (float*)mix.p);
+    else launch_cfg_sample(s, a, B, (float*)pv.p, (int*)pi.p);
+    return finish(s);                                                                                // before the scratch goes away
+}
+
+// The text sampler's step through launch_text_argmax (mode 0) or launch_text_sample (mode 1: the in-scan Gumbel draw, temperature > 0).  partial fp32: slab s at
+// partial + s * slab, rows [B][V], slab >= B V -- an odd slab or V sends the scan down its scalar branch, multiples of 4 down the 16-byte one (then partial and
+// logits_out are 16-byte aligned).  out int64 [B][max_new] (written when step < max_new); unfinished int32 [B] in / out; logits_out fp32 [max_new][B][V] or null
+// (then step < max_new); embed_table fp32 [V][H]; x fp32 [B][H].  TextParams, the step counter, the winner slots and the any-unfinished ring are allocated here.
+// Synchronises the stream before it returns.
+int pg_diag_op_text_draw(int mode, const float* partial, int S, long slab, int V, int B, int64_t* out, int32_t* unfinished, float* logits_out,
+                         const float* embed_table, float* x, int H, int eos, int min_new, int max_new, int step, float temperature, uint64_t seed, int row_off,
+                         pg_stream stream) {
+    if (!partial || !out || !unfinished || !embed_table || !x || (mode != 0 && mode != 1)) return PG_ERR_ARG;
+    if (S < 1 || V < 1 || B < 1 || B > kMaxGridYZ || H < 4 || (H & 3) || max_new < 1 || min_new < 0 || step < 0 || row_off < 0) return PG_ERR_ARG;
+    if (slab < (long)B * V || (long)V * H >= (1L << 40) || !aligned16({embed_table, x})) return PG_ERR_ARG;
+    if (((V | (int)(slab & 3)) & 3) == 0 && !aligned16({partial, logits_out})) return PG_ERR_ARG;     // the 16-byte branch of the scan
+    if (logits_out && step >= max_new) return PG_ERR_ARG;                                            // the tap has max_new steps
+    if (mode == 1 && !(temperature > 0.f)) return PG_ERR_ARG;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    Scratch tp, nd, pv, pi, any;
+    if (!tp.get(sizeof(TextParams)) || !nd.get(4) || !pv.get((size_t)B * 16 * 4) || !pi.get((size_t)B * 16 * 4) || !any.get(1024 * 4)) return PG_ERR_HIP;
+    if (hipMemsetAsync(any.p, 0, 1024 * 4, s) != hipSuccess) return PG_ERR_HIP;
+    TextParams p{};
+    p.eos = eos; p.min_new = min_new; p.max_new = max_new; p.temperature = temperature; p.top_p = 1.f; p.row_off = row_off; p.seed = seed;
+    launch_set_text_op_params(s, (TextParams*)tp.p, p, (int32_t*)nd.p, step);
+    TextArgs a{};
+    a.logits_partial = partial; a.S = S; a.slab = slab; a.V = V; a.p = (const TextParams*)tp.p; a.out = out; a.unfinished = unfinished;
+    a.any_unfinished = (int32_t*)any.p; a.embed_table = embed_table; a.x = x; a.H = H; a.n_dec = (const int32_t*)nd.p; a.logits_out = logits_out;
+    if (mode == 1) launch_text_sample(s, a, B, (float*)pv.p, (int*)pi.p);
+    else launch_text_argmax(s, a, B, (float*)pv.p, (int*)pi.p);
+    return finish(s);                                                                                // before the scratch goes away
 }
 
 }  // extern "C"
