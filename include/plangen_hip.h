@@ -303,6 +303,29 @@ int pg_generate_text_constrained(pg_handle h, int max_new, int eos_id, float tem
  * B * T / B * max_new, or the "lanes" = 2 decode. */
 int pg_request_token_logprobs(pg_handle h, float* out_dev, int64_t capacity_floats);
 
+/* -- scoring given text ---------------------------------------------------------------------
+ * log softmax(lm_head(hidden))[target] for n chosen rows of a hidden-state tensor, logits never materialised: the evaluation half of
+ * pg_request_token_logprobs.  hidden_dev [rows, hidden] in the compute dtype (hidden_dtype must say so) -- typically what pg_prefill /
+ * pg_prefill_embeds wrote to hidden_out_dev, viewed as [R * L, hidden]; row_idx_dev int32 [n] names the rows to score (NULL: rows
+ * 0 .. n-1), target_dev int32 [n] the token each is scored on:
+ *   y_v = sum_k hidden[row_idx[i]][k] * lm_head[v][k]   (fp32 accumulation; operands in the compute dtype),
+ *   x = y * (1 / temperature) when temperature > 0 (the rounded fp32 product of pg_request_token_logprobs), else x = y,
+ *   logprob[i] = (x[t] - m) - logf(sum_v expf(x_v - m)),  m = max_v x_v,  t = target[i];  t outside [0, vocab) gives -inf.
+ * Non-finite hidden states or weights are NOT covered (the NaN-as--inf rule of the sampling loops is not reproduced).
+ * PG_BF16 handles run one fused kernel over the vocabulary (MFMA tiles of 256 rows x 256 columns, running maximum and sum of
+ * exponentials per row in registers) and a small merge kernel; the only HBM traffic besides the operands is a library-owned partials
+ * workspace of 8 * G * n bytes (G column groups, a function of (n, vocab, hidden) alone), allocated on first use, grown on demand
+ * (growing frees the old one) and counted by pg_device_bytes.  A row's bits depend on its hidden row, lm_head, its target, the
+ * temperature and (n, vocab, hidden) only -- not on its slot in the batch nor on the other rows.  PG_F32 handles (parity mode) compose
+ * the f32 GEMM and the scoring kernel of pg_op_token_logprob over row chunks whose logits stay <= 64 MB (same workspace rule).
+ * Asynchronous on s, no synchronisation; the sequence state of the handle is not touched.  hidden must be a multiple of 64 (the
+ * kernel's K step).  row_idx entries outside [0, rows) are the caller's fault: they are never read on the host.
+ * PG_ERR_STATE: a handle without lm_head (with_lm_head = 0) or before pg_finalize_weights.  PG_ERR_ARG: a null pointer, n < 1, rows < 1,
+ * hidden_dtype != compute dtype, hidden % 64 != 0, row_idx_dev == NULL with n > rows.  After an error the handle stays usable. */
+int pg_score_tokens(pg_handle h, const void* hidden_dev, int hidden_dtype /* = compute dtype */, int64_t rows,
+                    const int32_t* row_idx_dev /*[n] or NULL*/, const int32_t* target_dev /*[n]*/, int64_t n,
+                    float temperature, float* logprob_dev /*[n]*/, pg_stream s);
+
 /* -- VQ-16 tokenizer ---------------------------------------------------------------------- */
 /* gen_vision_model.decode_code(codes, shape=[B,8,g,g]) (vq_model.py:505-508; call site
  * plangen_base.py:555): codes_dev int32 [B, g*g] -> img_out_dev [B, 3, S, S] (NCHW like the
@@ -470,6 +493,12 @@ int pg_op_text_constrain(pg_handle h, const float* logits_dev /*[B,V]*/, int B, 
  * any handle.  PG_ERR_ARG: a null pointer, B < 1, V < 1. */
 int pg_op_token_logprob(pg_handle h, const float* x_dev, int B, int V, const int32_t* tok_dev, float temperature,
                         float* logprob_dev, pg_stream s);
+
+/* The device code of pg_score_tokens on caller-given weights: x_dev [rows, K], w_dev [V, K] row-major, both in the handle's compute
+ * dtype; any n >= 1 and V >= 1, K a positive multiple of 64.  Works on any handle.  PG_ERR_ARG as pg_score_tokens. */
+int pg_op_head_logprob(pg_handle h, const void* x_dev, int64_t rows, const void* w_dev, int V, int K,
+                       const int32_t* row_idx_dev, const int32_t* target_dev, int64_t n, float temperature,
+                       float* logprob_dev, pg_stream s);
 
 /* The quantiser of the FP8 KV cache (the device code the decode append and the prefill conversion run; format above):
  * x_dev bf16 [n, 128] -> codes_dev uint8 [n, 128] (e4m3fn), scale_dev fp32 [n] (powers of two).  Works on any handle. */

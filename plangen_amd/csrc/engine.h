@@ -141,6 +141,9 @@ struct pg_engine {
     void* ip_dev = nullptr; long ip_dev_bytes = 0;
     uint8_t* ip_host[2] = {nullptr, nullptr}; long ip_host_bytes[2] = {0, 0};
     hipEvent_t ip_ev[2] = {nullptr, nullptr}; bool ip_used[2] = {false, false}; int ip_sel = 0;
+    // pg_score_tokens / pg_op_head_logprob: library-owned workspace, allocated on first use and grown on demand (the old one is freed, like ip_dev).
+    // bf16: the fused head's (max, sum) partials [G][n][2]; f32 (parity mode): one row chunk's logits (<= 64 MB) + its gathered rows
+    void* sh_ws = nullptr; long sh_ws_bytes = 0;
     // ---- streams / graph / timing
     hipStream_t istream = nullptr; hipEvent_t ev_in = nullptr, ev_out = nullptr;
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_p0 = nullptr, ev_p1 = nullptr, ev_v0 = nullptr, ev_v1 = nullptr;
@@ -243,6 +246,8 @@ struct pg_engine {
                       float* logits_out, hipStream_t s, bool constrained = false, int32_t* state_out = nullptr);
     int set_text_dfa(const pg_text_dfa* dfa, hipStream_t s);
     int token_logprob(const float* x, int B, int V, const int32_t* tok, float temp, float* out, hipStream_t s);
+    int head_logprob(const char* who, const void* x, int64_t rows, const void* w, int V, int K, const int32_t* row_idx, const int32_t* target, int64_t n,
+                     float temp, float* out, hipStream_t s);
     int text_constrain(const float* logits, int B, int V, const int32_t* state, int remaining, int eos, float temp, int top_k, float top_p,
                        uint64_t seed, int row_offset, int step, uint8_t* keep, int32_t* tok, int32_t* next_state, hipStream_t s);
     template <typename T> int vq_decode(const int32_t* codes, void* img_out, int out_dtype, int B, hipStream_t s);

@@ -321,6 +321,19 @@ int pg_op_token_logprob(pg_handle h, const float* x_dev, int B, int V, const int
     if (!h || !x_dev || !tok_dev || !logprob_dev) return PG_ERR_ARG;
     return h->token_logprob(x_dev, B, V, tok_dev, temperature, logprob_dev, (hipStream_t)s);
 }
+int pg_score_tokens(pg_handle h, const void* hidden_dev, int hidden_dtype, int64_t rows, const int32_t* row_idx_dev, const int32_t* target_dev, int64_t n,
+                    float temperature, float* logprob_dev, pg_stream s) { TuneGuard _tg(h);
+    if (!h) return PG_ERR_ARG;
+    if (!h->finalized) { h->err = "pg_score_tokens: pg_finalize_weights not called"; return PG_ERR_STATE; }
+    if (!h->cfg.with_lm_head || !h->lm_head) { h->err = "pg_score_tokens: the handle was created without lm_head (with_lm_head = 0)"; return PG_ERR_STATE; }
+    if (hidden_dtype != (h->bf ? PG_BF16 : PG_F32)) { h->err = "pg_score_tokens: hidden_dtype must be the compute dtype"; return PG_ERR_ARG; }
+    return h->head_logprob("pg_score_tokens", hidden_dev, rows, h->lm_head, h->cfg.vocab, h->H(), row_idx_dev, target_dev, n, temperature, logprob_dev, (hipStream_t)s);
+}
+int pg_op_head_logprob(pg_handle h, const void* x_dev, int64_t rows, const void* w_dev, int V, int K, const int32_t* row_idx_dev, const int32_t* target_dev,
+                       int64_t n, float temperature, float* logprob_dev, pg_stream s) { TuneGuard _tg(h);
+    if (!h) return PG_ERR_ARG;
+    return h->head_logprob("pg_op_head_logprob", x_dev, rows, w_dev, V, K, row_idx_dev, target_dev, n, temperature, logprob_dev, (hipStream_t)s);
+}
 int pg_op_kv_quantize(pg_handle h, const void* x_dev, uint8_t* codes_dev, float* scale_dev, int64_t n, pg_stream s) {
     if (!h || !x_dev || !codes_dev || !scale_dev || n < 0) return PG_ERR_ARG;
     (void)hipSetDevice(h->dev);

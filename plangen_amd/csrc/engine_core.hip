@@ -378,6 +378,7 @@ void pg_engine::destroy() {
     for (void* p : allocs) (void)hipFree(p);
     if (stage_dev) (void)hipFree(stage_dev);
     if (ip_dev) (void)hipFree(ip_dev);
+    if (sh_ws) (void)hipFree(sh_ws);
     for (int i = 0; i < 2; ++i) { if (ip_host[i]) (void)hipHostFree(ip_host[i]); if (ip_ev[i]) (void)hipEventDestroy(ip_ev[i]); }
     for (int i = 0; i < 2; ++i) { if (h_stage2[i]) (void)hipHostFree(h_stage2[i]); if (ev_stage[i]) (void)hipEventDestroy(ev_stage[i]); }
     if (h_flag) (void)hipHostFree(h_flag);

@@ -580,6 +580,41 @@ int pg_engine::token_logprob(const float* x, int B, int V, const int32_t* tok, f
     return PG_OK;
 }
 
+// pg_score_tokens / pg_op_head_logprob: log softmax(x . w^T)[target] for n chosen rows.  bf16: the fused head (score_head.hip), only its
+// (max, sum) partials touch HBM.  f32 (parity mode): the f32 GEMM + token_logprob_kernel over row chunks whose logits stay <= 64 MB.
+int pg_engine::head_logprob(const char* who, const void* x, int64_t rows, const void* w, int V, int K, const int32_t* row_idx, const int32_t* target,
+                            int64_t n, float temp, float* out, hipStream_t s) {
+    if (!x || !w || !target || !out) FAIL(PG_ERR_ARG, "%s: null pointer", who);
+    if (n < 1 || rows < 1 || V < 1 || n > (1L << 30)) FAIL(PG_ERR_ARG, "%s: needs 1 <= n <= 2^30, rows >= 1, V >= 1 (got n=%lld rows=%lld V=%d)", who, (long long)n, (long long)rows, V);
+    if (K < 64 || K % 64) FAIL(PG_ERR_ARG, "%s: K=%d must be a positive multiple of 64 (the kernel's K step)", who, K);
+    if (!row_idx && n > rows) FAIL(PG_ERR_ARG, "%s: n=%lld > rows=%lld without row_idx", who, (long long)n, (long long)rows);
+    HIPCHK(hipSetDevice(dev));
+    const long chunk = bf ? 0 : std::min<long>((long)n, std::max<long>(1, (64L << 20) / (4L * V)));
+    const long need = bf ? (long)head_logprob_ws_bytes((long)n, V, K) : (((chunk * V * 4 + 255) & ~255L) + chunk * K * 4);
+    if (need > sh_ws_bytes) {
+        if (sh_ws) { HIPCHK(hipFree(sh_ws)); bytes -= sh_ws_bytes; sh_ws = nullptr; sh_ws_bytes = 0; }   // hipFree waits for the work that still reads it
+        HIPCHK(hipMalloc(&sh_ws, (size_t)need));
+        sh_ws_bytes = need; bytes += need;
+    }
+    if (bf) {
+        if (!launch_head_logprob(s, (const bf16*)x, (const bf16*)w, row_idx, target, (long)n, V, K, temp, (float*)sh_ws, out)) FAIL(PG_ERR_ARG, "%s: shape not supported (n=%lld V=%d K=%d)", who, (long long)n, V, K);
+    } else {
+        float* logits = (float*)sh_ws;
+        float* xg = (float*)((char*)sh_ws + ((chunk * V * 4 + 255) & ~255L));
+        for (long r0 = 0; r0 < (long)n; r0 += chunk) {
+            const int cn = (int)std::min<long>(chunk, (long)n - r0);
+            const float* a = (const float*)x + r0 * K;
+            if (row_idx) { launch_copy_rows(s, x, row_idx + r0, xg, nullptr, cn, (long)K * 4); a = xg; }
+            GemmA ga; ga.ptr = a; ga.lda = K;
+            GemmEpi e; e.out = logits; e.out_f32 = 1; e.ldc = V;
+            launch_gemm<float>(s, ga, (const float*)w, K, 0, e, cn, V, K, 1);
+            launch_token_logprob_op(s, logits, cn, V, target + r0, temp, out + r0);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return PG_OK;
+}
+
 int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int top_k, float top_p, uint64_t seed, int64_t* out, int* out_len,
                              float* logits_out, hipStream_t s, bool constrained, int32_t* state_out) {
     float* const lp_out = lp_req; const int64_t lp_cap = lp_req_cap;      // the one-shot log-prob request: consumed whatever this call answers

@@ -302,6 +302,14 @@ void launch_token_logprob_image(hipStream_t s, const SampleArgs& a, int B, const
 // also leaves chunk maxima in scratch_v / scratch_i: launch it BEFORE the step's own scan, which overwrites them with its winners.
 void launch_text_store(hipStream_t s, const TextArgs& a, const TextDfaArgs* d, int B, float* scratch_v, int* scratch_i, float* mix);
 void launch_token_logprob_text(hipStream_t s, const TextArgs& a, int B, const float* mix, float* out);
+// Fused lm_head + log-softmax at a target (score_head.hip; contract and geometry in its header): X bf16 [rows, K], W bf16 [V, K] row-major,
+// row_idx int32 [n] or null (identity), target int32 [n] -> out fp32 [n].  part: >= head_logprob_ws_bytes(n, V, K) bytes of workspace
+// ([G][n] (max, sum) pairs).  K % 64 == 0 (the kernel's K step).  False (nothing launched) on a shape it does not take.
+struct HeadGeom { int ntm, ntn, cpt, G; };      // row tiles, column tiles, column tiles per group, groups
+HeadGeom head_logprob_geom(long n, int V, int K);
+size_t head_logprob_ws_bytes(long n, int V, int K);
+bool launch_head_logprob(hipStream_t s, const bf16* X, const bf16* W, const int32_t* row_idx, const int32_t* target, long n, int V, int K,
+                         float temperature, float* part, float* out);
 void launch_advance(hipStream_t s, int32_t* n_dec);
 void launch_rows_differ(hipStream_t s, const int32_t* ids, int L, int first, int stride, int ref, int n, int from, int32_t* flag);
 void launch_uniform_from_bits(hipStream_t s, const uint64_t* z, float* out, int n);

@@ -38,6 +38,39 @@ def replica_owner(row: int, R0: int, shared: bool) -> int:
     return 1 if (shared and row % 2 == 1) else row % R0
 
 
+def score_index(L: int, pad_len: Sequence[int], score_from: Sequence[int], device=None) -> torch.Tensor:
+    """Index builder of ``Engine.score_text``: the flat positions r * L + j of the scored columns of an [R, L] id tensor, row-major --
+    column j of row r is scored iff j >= score_from[r].  The hidden state that scores it sits at flat position - 1 (column j - 1 of the
+    same row), which must be a real token: score_from[r] >= pad_len[r] + 1, else ValueError (a pad slot carries no hidden state, and
+    column pad_len[r] has no predecessor).  score_from[r] == L scores nothing in row r."""
+    pad_len = [int(v) for v in pad_len]
+    score_from = [int(v) for v in score_from]
+    if len(pad_len) != len(score_from):
+        raise ValueError(f"score_from has {len(score_from)} entries for {len(pad_len)} rows")
+    for r, (p, f) in enumerate(zip(pad_len, score_from)):
+        if f < p + 1 or f > L:
+            raise ValueError(f"row {r}: score_from={f} must lie in [pad_len + 1, L] = [{p + 1}, {L}]")
+    sf = torch.tensor(score_from, dtype=torch.int64, device=device).view(-1, 1)
+    j = torch.arange(L, dtype=torch.int64, device=device).view(1, -1)
+    flat = torch.arange(len(score_from) * L, dtype=torch.int64, device=device).view(-1, L)
+    return flat[j >= sf]
+
+
+def head_logprob_geometry(n: int, V: int, K: int) -> dict:
+    """The fused scoring head's tiling (score_head.hip::head_logprob_geom, mirrored): 256-row x 256-column tiles, G column groups of ``cpt``
+    consecutive column tiles each -- a function of (n, V, K) alone.  ``ws_bytes``: the partials workspace a bf16 handle allocates for it."""
+    tile, target_blocks = 256, 256
+    ntm, ntn = (n + tile - 1) // tile, (V + tile - 1) // tile
+    best = None
+    for cpt in range(ntn, 0, -1):
+        G = (ntn + cpt - 1) // cpt
+        cost = ((ntm * G + target_blocks - 1) // target_blocks) * (cpt + 1)
+        if best is None or cost < best[0]:
+            best = (cost, cpt, G)
+    _, cpt, G = best
+    return dict(tile_rows=tile, tile_cols=tile, k_step=64, ntm=ntm, ntn=ntn, cpt=cpt, G=G, ws_bytes=(2 * 4 * G * n + 255) // 256 * 256)
+
+
 class Engine:
     """MI355X engine for the layout->image path.
 
@@ -462,6 +495,71 @@ class Engine:
                     "pg_op_token_logprob")
         self._keep = [x, t, out]
         return out
+
+    # ------------------------------------------------------------------ scoring given text
+    def score_tokens(self, hidden: torch.Tensor, target: torch.Tensor, row_idx: Optional[torch.Tensor] = None,
+                     temperature: float = 0.0) -> torch.Tensor:
+        """``pg_score_tokens``: log softmax(lm_head(hidden[row_idx[i]]) / temperature)[target[i]] -> fp32 [n]; ``hidden`` [..., hidden] in
+        the compute dtype (what ``prefill*(return_hidden=True, hidden_dtype=engine.tdtype)`` returns), logits never materialised."""
+        if hidden.dtype != self.tdtype:
+            raise PlanGenError(f"score_tokens: hidden must be {self.tdtype} (the compute dtype), got {hidden.dtype}")
+        h = self._dev(hidden).reshape(-1, hidden.shape[-1])
+        t = self._dev(torch.as_tensor(target), torch.int32).reshape(-1)
+        ri = self._dev(torch.as_tensor(row_idx), torch.int32).reshape(-1) if row_idx is not None else None
+        if ri is not None and ri.numel() != t.numel():
+            raise PlanGenError(f"score_tokens: {ri.numel()} row indices for {t.numel()} targets")
+        out = torch.full((t.numel(),), float("nan"), dtype=torch.float32, device=self.device)
+        self._check(self.lib.pg_score_tokens(self.h, self._p(h), _dt(h), h.shape[0], self._p(ri), self._p(t), t.numel(), float(temperature),
+                                             self._p(out), self.stream), "pg_score_tokens")
+        self._keep = [h, t, ri, out]
+        return out
+
+    def head_logprob(self, x: torch.Tensor, w: torch.Tensor, target: torch.Tensor, row_idx: Optional[torch.Tensor] = None,
+                     temperature: float = 0.0) -> torch.Tensor:
+        """``pg_op_head_logprob``: the device code of ``score_tokens`` on caller-given weights: x [rows, K], w [V, K] (converted to the
+        compute dtype), target [n], row_idx [n] or None (rows 0 .. n-1) -> fp32 [n]."""
+        x = self._dev(x, self.tdtype)
+        w = self._dev(w, self.tdtype)
+        rows, K = x.shape
+        V = w.shape[0]
+        t = self._dev(torch.as_tensor(target), torch.int32).reshape(-1)
+        ri = self._dev(torch.as_tensor(row_idx), torch.int32).reshape(-1) if row_idx is not None else None
+        out = torch.full((t.numel(),), float("nan"), dtype=torch.float32, device=self.device)
+        self._check(self.lib.pg_op_head_logprob(self.h, self._p(x), rows, self._p(w), V, K, self._p(ri), self._p(t), t.numel(),
+                                                float(temperature), self._p(out), self.stream), "pg_op_head_logprob")
+        self._keep = [x, w, t, ri, out]
+        return out
+
+    def _score_hidden(self, hidden: torch.Tensor, target_ids: torch.Tensor, pad_len, score_from, temperature: float) -> torch.Tensor:
+        R, L = target_ids.shape
+        sel = score_index(L, pad_len, score_from, device=self.device)
+        out = torch.zeros((R, L), dtype=torch.float32, device=self.device)
+        if sel.numel():
+            tgt = target_ids.reshape(-1).index_select(0, sel)
+            lp = self.score_tokens(hidden, tgt, sel - 1, temperature)
+            out.view(-1).index_copy_(0, sel, lp)
+        return out
+
+    def score_text(self, ids: torch.Tensor, pad_len: Sequence[int], score_from: Sequence[int], position_mode: int = 1,
+                   temperature: float = 0.0) -> torch.Tensor:
+        """Teacher-forced log-probabilities of given text in one prefill.  ``ids`` [R, L] left-padded (``pad_len``); column j of row r is
+        scored from the hidden state at column j - 1, only columns j >= score_from[r] are scored (score_from[r] >= pad_len[r] + 1, else
+        ValueError).  Returns fp32 [R, L]: log softmax(lm_head(h[r, j-1]) / temperature)[ids[r, j]] at the scored columns and 0.0
+        elsewhere, so a row's sum is the log-probability of its scored span (the text loop's convention for finished rows).  The engine
+        is left prefilled with ``ids``."""
+        score_index(ids.shape[1], pad_len, score_from)      # validate before anything is launched
+        ids = self._dev(ids, torch.int32)
+        hid = self.prefill(ids, pad_len, position_mode=position_mode, return_hidden=True, hidden_dtype=self.tdtype)
+        return self._score_hidden(hid, ids, pad_len, score_from, temperature)
+
+    def score_text_embeds(self, embeds: torch.Tensor, pad_len: Sequence[int], target_ids: torch.Tensor, score_from: Sequence[int],
+                          position_mode: int = 1, temperature: float = 0.0) -> torch.Tensor:
+        """``score_text`` through ``pg_prefill_embeds``: ``embeds`` [R, L, hidden] is the input sequence (text and image embeddings, the
+        ``mmu`` prompt) and ``target_ids`` [R, L] the token at every column (only the scored columns are read)."""
+        score_index(target_ids.shape[1], pad_len, score_from)
+        tgt = self._dev(target_ids, torch.int32)
+        hid = self.prefill_embeds(embeds, pad_len, position_mode=position_mode, return_hidden=True, hidden_dtype=self.tdtype)
+        return self._score_hidden(hid, tgt, pad_len, score_from, temperature)
 
     def generate_text(self, max_new_tokens: int, eos_id: int, min_new_tokens: int = 0, temperature: float = 0.0, top_k: int = 0,
                       top_p: float = 1.0, seed: int = 0, return_logits: bool = False, return_logprobs: bool = False):

@@ -75,7 +75,7 @@ class System:
     off when absent), top_k / top_p (image sampling filters, off when absent)
     and text_temperature / text_top_k / text_top_p (sampled layout / caption decode, greedy when absent); select_best (parallel_size > 1:
     keep each prompt's most probable replica, off when absent) and layout_best_of (stage 1: draw N layouts per row and keep the most
-    probable, 1 when absent).
+    probable, 1 when absent); score_gt_layout (plan / uni_2stage / mmu: also score batch['gt_grounding'], see score_layouts; off when absent).
     """
 
     def __init__(self, cfg: PlanGenConfig, engine: Engine, args: Optional[SimpleNamespace] = None, codec=None):
@@ -369,6 +369,10 @@ class System:
         else:
             out["pr_image"] = batch.get("image")
         out["pr_grounding"] = pr_grounding
+        if getattr(self.args, "score_gt_layout", False) and pred_layout and batch.get("gt_grounding") is not None:
+            # plan / uni_2stage: P(ground-truth layout | caption); mmu: P(ground-truth layout | image).  Runs after the generation: it re-prefills.
+            sc = self.score_layouts(batch, given="image" if is_mmu else "caption")
+            out["gt_layout_logprob"] = {k: sc[k] for k in ("sum", "mean", "n_tokens")}
         if save_local and gen_path is not None:
             # the reference's per-batch layout record (:416-420); its annotated PNG grid is box drawing, not part of the path
             import json
@@ -376,9 +380,65 @@ class System:
             os.makedirs(gen_path, exist_ok=True)
             with open(os.path.join(gen_path, f"{batch_idx}_layout.json"), "w") as f:
                 extra = {k: out[k].cpu().tolist() for k in ("pr_replica", "pr_score", "pr_layout_replica", "pr_layout_score") if k in out}
+                if "gt_layout_logprob" in out:
+                    extra["gt_layout_logprob"] = out["gt_layout_logprob"]
                 json.dump(dict(base_caption=base_caption, gt_grounding=batch.get("gt_grounding"),
                                pr_grounding=pr_grounding if pred_layout else "", **extra), f)
         return out
+
+    def _layout_ids(self, grounding: str, strip_open: bool) -> List[int]:
+        """Token ids of a layout string without BOS; strip_open: also without the leading ``<grounding>`` the stage-1 prompt already carries."""
+        codec = self._codec()
+
+        def enc(text):
+            ids = [int(t) for t in codec.encode(text)]
+            return ids[1:] if ids and ids[0] == getattr(codec, "bos_token_id", None) else ids
+        ids = enc(grounding)
+        if strip_open:
+            from .textproc import GROUNDING_OPEN
+            opn = enc(GROUNDING_OPEN)
+            if ids[:len(opn)] == opn:
+                ids = ids[len(opn):]
+        return ids
+
+    @torch.no_grad()
+    def score_layouts(self, batch: dict, given: str = "caption", temperature: float = 0.0) -> dict:
+        """How probable the model finds the layouts of ``batch['gt_grounding']``: one teacher-forced prefill + the fused scoring head
+        (``Engine.score_text`` / ``score_text_embeds``), nothing generated.
+        given='caption': P(layout | caption) -- the stage-1 prompt ``wrap_uni_prompt(caption, '<grounding>', in_stage1=True)`` followed by
+            the layout's tokens (without the ``<grounding>`` the prompt ends with) and EOS: what stage 1 would have to emit.
+        given='image'  : P(layout | image) through the understanding path (the ``mmu`` form) -- ``prepare_inputs_embeds`` of
+            ``batch['prepare_inputs_infer']`` (vision_encode + the embedding assembly) followed by the embeddings of the whole layout string and EOS.
+        Only the appended tokens are scored.  Returns dict(sum, mean, n_tokens: one entry per row; logprobs fp32 [B, L], 0.0 at unscored
+        columns): sum = the sequence log-probability, n_tokens = layout tokens + 1 (EOS), mean = sum / n_tokens."""
+        if given not in ("caption", "image"):
+            raise PlanGenError(f"score_layouts: given={given!r} must be 'caption' or 'image'")
+        eos, eng = int(self.cfg.eos_id), self.engine
+        lay = [self._layout_ids(g, strip_open=given == "caption") + [eos] for g in batch["gt_grounding"]]
+        if given == "caption":
+            prompts = [self.wrap_uni_prompt(c, "<grounding>", in_stage1=True)[1].tolist() for c in batch["base_caption"]]
+            seqs = [p + l for p, l in zip(prompts, lay)]
+            ids, _ = pad_input_ids(seqs, self.cfg.pad_id)
+            L = ids.shape[1]
+            lp = eng.score_text(ids, [L - len(q) for q in seqs], [L - len(l) for l in lay], position_mode=1, temperature=temperature)
+        else:
+            pin = batch["prepare_inputs_infer"]
+            emb = self.vl_gpt.prepare_inputs_embeds(**{k: v for k, v in pin.items() if k != "attention_mask"})
+            Lp = emb.shape[1]
+            plen = [int(v) for v in pin["attention_mask"][:, :Lp].sum(-1)]
+            L = max(p + len(l) for p, l in zip(plen, lay))
+            embeds = torch.zeros((len(lay), L, emb.shape[2]), dtype=emb.dtype, device=emb.device)
+            target = torch.full((len(lay), L), int(self.cfg.pad_id), dtype=torch.int32)
+            embed = self.vl_gpt.language_model.get_input_embeddings()
+            for i, (p, l) in enumerate(zip(plen, lay)):
+                embeds[i, L - len(l) - p:L - len(l)] = emb[i, Lp - p:]
+                embeds[i, L - len(l):] = embed(torch.tensor(l, dtype=torch.int32)).to(emb.dtype)
+                target[i, L - len(l):] = torch.tensor(l, dtype=torch.int32)
+            lp = eng.score_text_embeds(embeds, [L - p - len(l) for p, l in zip(plen, lay)], target, [L - len(l) for l in lay],
+                                       position_mode=1, temperature=temperature)
+        n_tok = [len(l) for l in lay]
+        sums = lp.sum(-1).cpu().tolist()
+        return dict(sum=sums, mean=[s / n for s, n in zip(sums, n_tok)], n_tokens=n_tok, logprobs=lp)
 
     @staticmethod
     def select_best_layouts(tokens: torch.Tensor, logprobs: torch.Tensor, n: int, eos_id: int):

@@ -20,6 +20,7 @@ kv_dtype = 'bf16'                      # KV cache: 'bf16' = the compute dtype; '
 share_replicas = 0                     # parallel_size > 1: 1 = prefill every prompt once and let its replicas read its K/V in the decode loop (same tokens; an extension beyond the reference)
 select_best = False                    # parallel_size > 1: score every replica by the mean log-probability of its image tokens, VQ-decode and keep only the best one per prompt (an extension beyond the reference)
 layout_best_of = 1                     # uni_2stage / plan with text_temperature > 0: draw this many layouts per row and keep the one with the highest mean token log-probability (an extension beyond the reference)
+score_gt_layout = False                # plan / uni_2stage / mmu: also write gt_layout_logprob = {sum, mean, n_tokens} per row to the batch JSON: log P(gt_grounding + EOS | caption) (mmu: | image) from one teacher-forced prefill (an extension beyond the reference)
 use_teacher_forcing = False            # base.py:36
 use_neg_box = False                    # base.py:121
 neg_prompt = ""                        # base.py:129: wrapped as wrap_uni_prompt(neg_prompt, '') for every uncond CFG row (:673)

@@ -84,6 +84,7 @@ class System(_HotPath):
                                                    temperature=args.temperature, top_k=cfg.top_k, top_p=cfg.top_p,
                                                    text_temperature=cfg.text_temperature, text_top_k=cfg.text_top_k, text_top_p=cfg.text_top_p,
                                                    layout_grammar=cfg.layout_grammar, select_best=select_best, layout_best_of=layout_best_of,
+                                                   score_gt_layout=bool(getattr(args, "score_gt_layout", False)),
                                                    use_teacher_forcing=args.use_teacher_forcing, share_replicas=cfg.share_replicas,
                                                    debug_max_seq_len=args.debug_max_seq_len, janus_hw=args.janus_hw,
                                                    neg_prompt=getattr(args, "neg_prompt", ""),

@@ -231,6 +231,9 @@ SPECS = [
                                                      "after its last read with the read drained (lgkmcnt(0)) in front of that barrier (wave groups one barrier apart)")),
     ("gemm256", r"gemm256_kernel", dict(kind="fifo", g=2, need=None, tile_cls=lambda n: n & 3, slot_reuse=lambda c: 8, strict=True, stagger=True,
                                         why="four-phase form: half-tiles retired by vmcnt(8) in the phase before they are read; a slot is re-staged >= 2 phases after its last read")),
+    ("score_head", r"head_logprob_kernel", dict(kind="fifo", g=2, need="ph2", tile_cls=lambda n: n & 3, slot_reuse=lambda c: 8, strict=True, stagger=True,
+                                                why="the fused scoring head walks its column tiles on gemm256's two-phase stream (same half-tile order, counted waits and drained "
+                                                    "fragment reads); its fold and merge touch LDS only past the staging buffers")),
     ("diag_gemm_bw", r"gemm_bw_kernel", dict(kind="fifo", g=8, need="bw", tile_cls=lambda n: 0, slot_reuse=lambda c: 4, strict=False,
                                             why="libplangen_diag.so experiment: 4-stage ring, tile t+1 retired by vmcnt(8) + the barrier of iteration t and first read behind that barrier (weak form)")),
     ("gemm", r"gemm_sk4_kernel", dict(kind="sk4")),
