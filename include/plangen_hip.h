@@ -326,6 +326,35 @@ int pg_score_tokens(pg_handle h, const void* hidden_dev, int hidden_dtype /* = c
                     const int32_t* row_idx_dev /*[n] or NULL*/, const int32_t* target_dev /*[n]*/, int64_t n,
                     float temperature, float* logprob_dev /*[n]*/, pg_stream s);
 
+/* -- scoring given images ---------------------------------------------------------------------
+ * The image-side counterpart of pg_score_tokens: the log-probability of given image tokens under the GUIDED distribution the image
+ * sampler draws from, for n positions of a hidden-state tensor, without the 576-step loop and without logits in HBM.  hidden_dev
+ * [rows, hidden] in the compute dtype (hidden_dtype must say so) -- typically what pg_prefill_embeds(position_mode = 0) wrote to
+ * hidden_out_dev for [prompt | image embeddings], viewed as [R * L, hidden].  Position i names its conditional row cond_idx_dev[i], its
+ * unconditional row uncond_idx_dev[i] (both int32 [n], indices into the rows of hidden_dev; the two lists may name the same row, and one row
+ * may serve many positions) and the image token target_dev[i] it is scored on:
+ *   g       = GELU_erf(hidden . W1^T + b1) in the compute dtype        (gen_head layer 1, as pg_gen_head / the decode loop leave it),
+ *   yc_v    = sum_k g[cond_idx[i]][k] * W2[v][k] + b2[v],  yu_v likewise with uncond_idx[i]   (fp32 accumulation),
+ *   y_v     = yu_v + cfg_weight * (yc_v - yu_v)                         (fp32; the sampler's expression),
+ *   x       = y * (1 / temperature) when temperature > 0 (the rounded fp32 product of pg_request_token_logprobs), else x = y,
+ *   logprob[i] = (x[t] - m) - logf(sum_v expf(x_v - m)),  m = max_v x_v,  t = target[i];  t outside [0, img_vocab) gives -inf.
+ * Non-finite hidden states or weights are NOT covered.
+ * Layer 1 runs over ALL ``rows`` rows of hidden_dev (one large-M GEMM with the bias and the GELU in its epilogue; no compaction: pass
+ * only the rows worth a GEMM row); its output [rows, gen_head_dim] lives in the library-owned scoring workspace.  PG_BF16 handles then run
+ * one fused kernel: 256 x 256 MFMA tiles that hold 128 (cond, uncond) pairs, the mix and a running maximum and sum of exponentials per
+ * pair in registers, and a small merge kernel; besides the operands it moves 8 * G * n bytes of partials (G column groups, a function
+ * of (n, img_vocab, gen_head_dim) alone).  A position's bits depend on its two hidden rows, the weights, its target, cfg_weight, the
+ * temperature and (n, img_vocab, gen_head_dim) only -- not on its slot nor on the other positions.  PG_F32 handles (parity mode)
+ * compose the f32 GEMM, a mix kernel and the scoring kernel of pg_op_token_logprob over chunks of pairs whose logits stay <= 64 MB.
+ * The workspace is the one of pg_score_tokens: allocated on first use, grown on demand (growing frees the old one), counted by
+ * pg_device_bytes.  Asynchronous on s, no synchronisation; the sequence state of the handle is not touched.  Index entries outside
+ * [0, rows) are the caller's fault: they are never read on the host.
+ * PG_ERR_STATE: before pg_finalize_weights.  PG_ERR_ARG: a null pointer, n < 1 or n > 2^29, rows < 1 or rows * max(hidden, gen_head_dim)
+ * >= 2^31, hidden_dtype != compute dtype.  After an error the handle stays usable. */
+int pg_score_image_tokens(pg_handle h, const void* hidden_dev, int hidden_dtype /* = compute dtype */, int64_t rows,
+                          const int32_t* cond_idx_dev /*[n]*/, const int32_t* uncond_idx_dev /*[n]*/, const int32_t* target_dev /*[n]*/,
+                          int64_t n, float cfg_weight, float temperature, float* logprob_dev /*[n]*/, pg_stream s);
+
 /* -- VQ-16 tokenizer ---------------------------------------------------------------------- */
 /* gen_vision_model.decode_code(codes, shape=[B,8,g,g]) (vq_model.py:505-508; call site
  * plangen_base.py:555): codes_dev int32 [B, g*g] -> img_out_dev [B, 3, S, S] (NCHW like the
@@ -445,7 +474,9 @@ int64_t pg_device_bytes(pg_handle h);
 /* Debug taps for parity tests: copy an internal buffer to dst_dev.
  * name: "kcache"/"vcache" (layer in ``index``; compute dtype [max_rows, heads, slots, 128] -- with the FP8 KV cache the uint8 codes of
  * the same shape, and "kscale"/"vscale" return the scales as fp32 [max_rows, heads, slots]), "x" (residual stream), "xn", "hfin", "gen_table", "pq_table", "qbuf", "obuf",
- * "vit_feat" (SigLIP features of the last pg_vision_encode, after the final LayerNorm, compute dtype [B, P, vit_width]). */
+ * "vit_feat" (SigLIP features of the last pg_vision_encode, after the final LayerNorm, compute dtype [B, P, vit_width]),
+ * "score_mid" (gen_head layer-1 output of the last pg_score_image_tokens, compute dtype [rows, gen_head_dim]; PG_ERR_NAME once another
+ * scoring call has reused the workspace). */
 int pg_debug_read(pg_handle h, const char* name, int index, void* dst_dev, int64_t max_bytes, pg_stream s);
 
 /* Stand-alone operator entry points (unit parity tests call these through the ABI;
@@ -499,6 +530,13 @@ int pg_op_token_logprob(pg_handle h, const float* x_dev, int B, int V, const int
 int pg_op_head_logprob(pg_handle h, const void* x_dev, int64_t rows, const void* w_dev, int V, int K,
                        const int32_t* row_idx_dev, const int32_t* target_dev, int64_t n, float temperature,
                        float* logprob_dev, pg_stream s);
+
+/* The head of pg_score_image_tokens (everything after layer 1) on caller-given operands: x_dev [rows, K] and w_dev [V, K] row-major in the
+ * handle's compute dtype, bias_dev fp32 [V] or NULL (no bias); any n >= 1 and V >= 1, K a positive multiple of 64.  Works on any handle.
+ * PG_ERR_ARG: a null pointer (bias_dev excepted), n < 1 or n > 2^29, rows < 1, V < 1, K not a positive multiple of 64. */
+int pg_op_cfg_head_logprob(pg_handle h, const void* x_dev, int64_t rows, const void* w_dev, int V, int K, const float* bias_dev /*[V] or NULL*/,
+                           const int32_t* cond_idx_dev, const int32_t* uncond_idx_dev, const int32_t* target_dev, int64_t n,
+                           float cfg_weight, float temperature, float* logprob_dev, pg_stream s);
 
 /* The quantiser of the FP8 KV cache (the device code the decode append and the prefill conversion run; format above):
  * x_dev bf16 [n, 128] -> codes_dev uint8 [n, 128] (e4m3fn), scale_dev fp32 [n] (powers of two).  Works on any handle. */

@@ -68,6 +68,7 @@ SYMBOLS = [
     ("pg_generate_text_constrained", C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_int32, C.c_float, C.c_uint64, _P, C.POINTER(C.c_int), _P, _P, _P]),
     ("pg_request_token_logprobs", C.c_int, [_P, _P, C.c_int64]),
     ("pg_score_tokens", C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.c_int64, C.c_float, _P, _P]),
+    ("pg_score_image_tokens", C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, _P, C.c_int64, C.c_float, C.c_float, _P, _P]),
     ("pg_vq_decode", C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     ("pg_vq_encode", C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P]),
     ("pg_vision_encode", C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
@@ -87,6 +88,7 @@ SYMBOLS = [
                                        _P, _P, _P, _P]),
     ("pg_op_token_logprob", C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_float, _P, _P]),
     ("pg_op_head_logprob", C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.c_int, _P, _P, C.c_int64, C.c_float, _P, _P]),
+    ("pg_op_cfg_head_logprob", C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, _P, _P]),
     ("pg_op_kv_quantize", C.c_int, [_P, _P, _P, _P, C.c_int64, _P]),
     ("pg_op_conv3x3", C.c_int, [_P, _P, _P, _P, _P, _P] + [C.c_int] * 7 + [_P]),
     ("pg_op_groupnorm", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

@@ -143,7 +143,9 @@ struct pg_engine {
     hipEvent_t ip_ev[2] = {nullptr, nullptr}; bool ip_used[2] = {false, false}; int ip_sel = 0;
     // pg_score_tokens / pg_op_head_logprob: library-owned workspace, allocated on first use and grown on demand (the old one is freed, like ip_dev).
     // bf16: the fused head's (max, sum) partials [G][n][2]; f32 (parity mode): one row chunk's logits (<= 64 MB) + its gathered rows
+    // pg_score_image_tokens / pg_op_cfg_head_logprob use it too: [gen_head layer-1 output of all rows | the head's own part, as above with pairs]
     void* sh_ws = nullptr; long sh_ws_bytes = 0;
+    long sh_mid_bytes = 0;              // bytes of gen_head layer-1 output the last pg_score_image_tokens left at the start of sh_ws (debug tap "score_mid")
     // ---- streams / graph / timing
     hipStream_t istream = nullptr; hipEvent_t ev_in = nullptr, ev_out = nullptr;
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_p0 = nullptr, ev_p1 = nullptr, ev_v0 = nullptr, ev_v1 = nullptr;
@@ -248,6 +250,14 @@ struct pg_engine {
     int token_logprob(const float* x, int B, int V, const int32_t* tok, float temp, float* out, hipStream_t s);
     int head_logprob(const char* who, const void* x, int64_t rows, const void* w, int V, int K, const int32_t* row_idx, const int32_t* target, int64_t n,
                      float temp, float* out, hipStream_t s);
+    int sh_reserve(long need);
+    long cfg_head_need(int64_t n, int V, int K) const;
+    int cfg_head_run(const char* who, const void* x, const void* w, int V, int K, const float* bias, const int32_t* cond_idx, const int32_t* uncond_idx,
+                     const int32_t* target, int64_t n, float cfgw, float temp, float* out, hipStream_t s, char* ws);
+    int cfg_head_logprob(const char* who, const void* x, int64_t rows, const void* w, int V, int K, const float* bias, const int32_t* cond_idx,
+                         const int32_t* uncond_idx, const int32_t* target, int64_t n, float cfgw, float temp, float* out, hipStream_t s);
+    int score_image_tokens(const void* hidden, int64_t rows, const int32_t* cond_idx, const int32_t* uncond_idx, const int32_t* target, int64_t n,
+                           float cfgw, float temp, float* out, hipStream_t s);
     int text_constrain(const float* logits, int B, int V, const int32_t* state, int remaining, int eos, float temp, int top_k, float top_p,
                        uint64_t seed, int row_offset, int step, uint8_t* keep, int32_t* tok, int32_t* next_state, hipStream_t s);
     template <typename T> int vq_decode(const int32_t* codes, void* img_out, int out_dtype, int B, hipStream_t s);

@@ -223,6 +223,7 @@ int pg_debug_read(pg_handle h, const char* name, int index, void* dst_dev, int64
     else if (nm == "gen_table") { src = h->gen_table; n = (int64_t)h->cfg.img_vocab * h->H() * 4; }
     else if (nm == "pq_table") { src = h->pq_table; n = (int64_t)h->cfg.img_vocab * h->cfg.vq_z * h->esz; }
     else if (nm == "qbuf") { src = h->qbuf; n = (int64_t)h->max_tok * h->HD() * h->esz; }
+    else if (nm == "score_mid" && h->sh_mid_bytes > 0) { src = h->sh_ws; n = h->sh_mid_bytes; }
     else if (nm == "obuf") { src = h->obuf; n = (int64_t)h->max_tok * h->HD() * h->esz; }
     else if (nm == "vit_feat" && h->cfg.with_vision) {   // SigLIP features (after the final LayerNorm, compute dtype) of the last pg_vision_encode
         const int64_t P = (h->cfg.vit_img / h->cfg.vit_patch) * (h->cfg.vit_img / h->cfg.vit_patch);
@@ -333,6 +334,20 @@ int pg_op_head_logprob(pg_handle h, const void* x_dev, int64_t rows, const void*
                        int64_t n, float temperature, float* logprob_dev, pg_stream s) { TuneGuard _tg(h);
     if (!h) return PG_ERR_ARG;
     return h->head_logprob("pg_op_head_logprob", x_dev, rows, w_dev, V, K, row_idx_dev, target_dev, n, temperature, logprob_dev, (hipStream_t)s);
+}
+int pg_score_image_tokens(pg_handle h, const void* hidden_dev, int hidden_dtype, int64_t rows, const int32_t* cond_idx_dev, const int32_t* uncond_idx_dev,
+                          const int32_t* target_dev, int64_t n, float cfg_weight, float temperature, float* logprob_dev, pg_stream s) { TuneGuard _tg(h);
+    if (!h) return PG_ERR_ARG;
+    if (!h->finalized) { h->err = "pg_score_image_tokens: pg_finalize_weights not called"; return PG_ERR_STATE; }
+    if (hidden_dtype != (h->bf ? PG_BF16 : PG_F32)) { h->err = "pg_score_image_tokens: hidden_dtype must be the compute dtype"; return PG_ERR_ARG; }
+    return h->score_image_tokens(hidden_dev, rows, cond_idx_dev, uncond_idx_dev, target_dev, n, cfg_weight, temperature, logprob_dev, (hipStream_t)s);
+}
+int pg_op_cfg_head_logprob(pg_handle h, const void* x_dev, int64_t rows, const void* w_dev, int V, int K, const float* bias_dev, const int32_t* cond_idx_dev,
+                           const int32_t* uncond_idx_dev, const int32_t* target_dev, int64_t n, float cfg_weight, float temperature, float* logprob_dev,
+                           pg_stream s) { TuneGuard _tg(h);
+    if (!h) return PG_ERR_ARG;
+    return h->cfg_head_logprob("pg_op_cfg_head_logprob", x_dev, rows, w_dev, V, K, bias_dev, cond_idx_dev, uncond_idx_dev, target_dev, n, cfg_weight,
+                               temperature, logprob_dev, (hipStream_t)s);
 }
 int pg_op_kv_quantize(pg_handle h, const void* x_dev, uint8_t* codes_dev, float* scale_dev, int64_t n, pg_stream s) {
     if (!h || !x_dev || !codes_dev || !scale_dev || n < 0) return PG_ERR_ARG;

@@ -591,6 +591,7 @@ int pg_engine::head_logprob(const char* who, const void* x, int64_t rows, const 
     HIPCHK(hipSetDevice(dev));
     const long chunk = bf ? 0 : std::min<long>((long)n, std::max<long>(1, (64L << 20) / (4L * V)));
     const long need = bf ? (long)head_logprob_ws_bytes((long)n, V, K) : (((chunk * V * 4 + 255) & ~255L) + chunk * K * 4);
+    sh_mid_bytes = 0;
     if (need > sh_ws_bytes) {
         if (sh_ws) { HIPCHK(hipFree(sh_ws)); bytes -= sh_ws_bytes; sh_ws = nullptr; sh_ws_bytes = 0; }   // hipFree waits for the work that still reads it
         HIPCHK(hipMalloc(&sh_ws, (size_t)need));
@@ -613,6 +614,84 @@ int pg_engine::head_logprob(const char* who, const void* x, int64_t rows, const 
     }
     HIPCHK(hipGetLastError());
     return PG_OK;
+}
+
+// ---- scoring given images: the CFG-mixed gen_head (pg_score_image_tokens / pg_op_cfg_head_logprob)
+// the scoring workspace holds at least ``need`` bytes afterwards (grown: the old one is freed; hipFree waits for the work that still reads it)
+int pg_engine::sh_reserve(long need) {
+    if (need <= sh_ws_bytes) return PG_OK;
+    if (sh_ws) { HIPCHK(hipFree(sh_ws)); bytes -= sh_ws_bytes; sh_ws = nullptr; sh_ws_bytes = 0; }
+    HIPCHK(hipMalloc(&sh_ws, (size_t)need));
+    sh_ws_bytes = need; bytes += need;
+    return PG_OK;
+}
+// bf16: the fused head's (max, sum) partials.  f32: one chunk of pairs -- its 2 * chunk logit rows (<= 64 MB) + its 2 * chunk gathered X rows
+static long cfg_head_chunk(int64_t n, int V) { return std::min<long>((long)n, std::max<long>(1, (64L << 20) / (8L * V))); }
+long pg_engine::cfg_head_need(int64_t n, int V, int K) const {
+    if (bf) return (long)cfg_head_logprob_ws_bytes((long)n, V, K);
+    const long chunk = cfg_head_chunk(n, V);
+    return ((2 * chunk * V * 4 + 255) & ~255L) + 2 * chunk * K * 4;
+}
+// the head on operands already validated, in workspace ``ws`` (>= cfg_head_need bytes).  bf16: score_cfg_head.hip.  f32 (parity mode), per
+// chunk of pairs: gather [cond rows | uncond rows] -> f32 GEMM -> cfg_mix_rows_kernel (bias + mix, in place) -> token_logprob_kernel
+int pg_engine::cfg_head_run(const char* who, const void* x, const void* w, int V, int K, const float* bias, const int32_t* cond_idx, const int32_t* uncond_idx,
+                            const int32_t* target, int64_t n, float cfgw, float temp, float* out, hipStream_t s, char* ws) {
+    if (bf) {
+        if (!launch_cfg_head_logprob(s, (const bf16*)x, (const bf16*)w, bias, cond_idx, uncond_idx, target, (long)n, V, K, cfgw, temp, (float*)ws, out))
+            FAIL(PG_ERR_ARG, "%s: shape not supported (n=%lld V=%d K=%d)", who, (long long)n, V, K);
+    } else {
+        const long chunk = cfg_head_chunk(n, V);
+        float* logits = (float*)ws;
+        float* xg = (float*)(ws + ((2 * chunk * V * 4 + 255) & ~255L));
+        for (long r0 = 0; r0 < (long)n; r0 += chunk) {
+            const int cn = (int)std::min<long>(chunk, (long)n - r0);
+            launch_copy_rows(s, x, cond_idx + r0, xg, nullptr, cn, (long)K * 4);
+            launch_copy_rows(s, x, uncond_idx + r0, xg + (long)cn * K, nullptr, cn, (long)K * 4);
+            GemmA ga; ga.ptr = xg; ga.lda = K;
+            GemmEpi e; e.out = logits; e.out_f32 = 1; e.ldc = V;
+            launch_gemm<float>(s, ga, (const float*)w, K, 0, e, 2 * cn, V, K, 1);
+            launch_cfg_mix_rows(s, logits, bias, cn, V, cfgw);
+            launch_token_logprob_op(s, logits, cn, V, target + r0, temp, out + r0);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return PG_OK;
+}
+static const char* cfg_head_args(const void* x, const void* w, const int32_t* ci, const int32_t* ui, const int32_t* t, const float* out, int64_t n, int64_t rows,
+                                 int V, int K) {
+    if (!x || !w || !ci || !ui || !t || !out) return "null pointer";
+    if (n < 1 || rows < 1 || V < 1 || n > (1L << 29)) return "needs 1 <= n <= 2^29, rows >= 1, V >= 1";
+    if (K < 64 || K % 64) return "K must be a positive multiple of 64 (the kernel's K step)";
+    return nullptr;
+}
+int pg_engine::cfg_head_logprob(const char* who, const void* x, int64_t rows, const void* w, int V, int K, const float* bias, const int32_t* cond_idx,
+                                const int32_t* uncond_idx, const int32_t* target, int64_t n, float cfgw, float temp, float* out, hipStream_t s) {
+    if (const char* why = cfg_head_args(x, w, cond_idx, uncond_idx, target, out, n, rows, V, K))
+        FAIL(PG_ERR_ARG, "%s: %s (got n=%lld rows=%lld V=%d K=%d)", who, why, (long long)n, (long long)rows, V, K);
+    HIPCHK(hipSetDevice(dev));
+    sh_mid_bytes = 0;
+    TRY(sh_reserve(cfg_head_need(n, V, K)));
+    return cfg_head_run(who, x, w, V, K, bias, cond_idx, uncond_idx, target, n, cfgw, temp, out, s, (char*)sh_ws);
+}
+// gen_head layer 1 (Linear + b1 -> GELU(erf), both in the large-M GEMM's epilogue; output in the compute dtype, as head_logits leaves it) over
+// ALL ``rows`` of hidden -- no compaction: the index lists address the layer-1 output as they address hidden -- then the head on gh_w2 / gh_b2
+int pg_engine::score_image_tokens(const void* hidden, int64_t rows, const int32_t* cond_idx, const int32_t* uncond_idx, const int32_t* target, int64_t n,
+                                  float cfgw, float temp, float* out, hipStream_t s) {
+    const char* who = "pg_score_image_tokens";
+    const int Hh = H(), G = cfg.gen_head_dim, V = cfg.img_vocab;
+    if (const char* why = cfg_head_args(hidden, gh_w2, cond_idx, uncond_idx, target, out, n, rows, V, G))
+        FAIL(PG_ERR_ARG, "%s: %s (got n=%lld rows=%lld V=%d K=%d)", who, why, (long long)n, (long long)rows, V, G);
+    if (rows > 0x7fffffffL / std::max(Hh, G)) FAIL(PG_ERR_ARG, "%s: rows=%lld x max(hidden, gen_head_dim) must stay below 2^31 elements", who, (long long)rows);
+    HIPCHK(hipSetDevice(dev));
+    const long mid_bytes = ((long)rows * G * (long)esz + 255) & ~255L;
+    sh_mid_bytes = 0;
+    TRY(sh_reserve(mid_bytes + cfg_head_need(n, V, G)));
+    sh_mid_bytes = (long)rows * G * (long)esz;
+    GemmA ga; ga.ptr = hidden; ga.lda = Hh;
+    GemmEpi e; e.out = sh_ws; e.out_f32 = 0; e.ldc = G; e.bias_n = gh_b1; e.act = 1;
+    if (bf) launch_gemm<bf16>(s, ga, (const bf16*)gh_w1, Hh, 0, e, (int)rows, G, Hh, 1);
+    else launch_gemm<float>(s, ga, (const float*)gh_w1, Hh, 0, e, (int)rows, G, Hh, 1);
+    return cfg_head_run(who, sh_ws, gh_w2, V, G, gh_b2, cond_idx, uncond_idx, target, n, cfgw, temp, out, s, (char*)sh_ws + mid_bytes);
 }
 
 int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int top_k, float top_p, uint64_t seed, int64_t* out, int* out_len,

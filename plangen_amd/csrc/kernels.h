@@ -310,6 +310,16 @@ HeadGeom head_logprob_geom(long n, int V, int K);
 size_t head_logprob_ws_bytes(long n, int V, int K);
 bool launch_head_logprob(hipStream_t s, const bf16* X, const bf16* W, const int32_t* row_idx, const int32_t* target, long n, int V, int K,
                          float temperature, float* part, float* out);
+// out[i] holds x_t: merge the G groups' (max, sum) partials [G][n][2] in ascending order and finish the log-probability (both fused heads)
+void launch_head_combine(hipStream_t s, const float* part, const int32_t* target, long n, int V, int G, float* out);
+// Fused CFG-mixed gen_head layer 2 + log-softmax at a target (score_cfg_head.hip; contract in its header): position i scores target[i] under
+// softmax((yu + cfg_weight * (yc - yu)) / temperature), yc / yu = X[cond_idx[i]] / X[uncond_idx[i]] . W^T + bias (fp32 [V] or null).  The
+// geometry is head_logprob_geom(2 n, V, K) (128 pairs per row tile); part: >= cfg_head_logprob_ws_bytes(n, V, K) bytes.  K % 64 == 0.
+size_t cfg_head_logprob_ws_bytes(long n, int V, int K);
+bool launch_cfg_head_logprob(hipStream_t s, const bf16* X, const bf16* W, const float* bias, const int32_t* cond_idx, const int32_t* uncond_idx,
+                             const int32_t* target, long n, int V, int K, float cfg_weight, float temperature, float* part, float* out);
+// fp32 composition (parity mode): logits fp32 [2 cn, V], cond rows first, then the uncond rows -> row i = the mixed row of pair i (bias added to both), in place
+void launch_cfg_mix_rows(hipStream_t s, float* logits, const float* bias, int cn, int V, float cfg_weight);
 void launch_advance(hipStream_t s, int32_t* n_dec);
 void launch_rows_differ(hipStream_t s, const int32_t* ids, int L, int first, int stride, int ref, int n, int from, int32_t* flag);
 void launch_uniform_from_bits(hipStream_t s, const uint64_t* z, float* out, int n);

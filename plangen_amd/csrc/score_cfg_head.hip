@@ -1,50 +1,37 @@
-// Fused lm_head + log-softmax at a target (pg_score_tokens / pg_op_head_logprob): the flash-attention idea over the vocabulary.
+// Fused CFG-mixed gen_head layer 2 + log-softmax at a target (pg_score_image_tokens / pg_op_cfg_head_logprob): score_head.hip's kernel with
+// a classifier-free-guidance mix between the accumulators and the fold.  Per scored position i (c = cond_idx[i], u = uncond_idx[i], t = target[i]):
 //
-//   y_v    = sum_k X[row_idx[i]][k] * W[v][k]                       (bf16 operands, fp32 accumulation on the MFMA units)
-//   x_v    = y_v * (1 / temperature)  when temperature > 0, else y_v (the rounded fp32 product, as token_logprob_kernel)
-//   out[i] = (x_t - m) - logf(sum_v expf(x_v - m)),  m = max_v x_v,  t = target[i];   t outside [0, V) gives -inf
+//   yc_v = sum_k X[c][k] * W[v][k] + bias[v],   yu_v likewise with X[u]     (bf16 operands, fp32 accumulation on the MFMA units; bias fp32 or absent)
+//   y_v  = yu_v + cfg_weight * (yc_v - yu_v)                                (fp32, the expression of cfg_scan_kernel in llm_kernels.hip)
+//   x_v  = y_v * (1 / temperature)  when temperature > 0, else y_v          (the rounded fp32 product)
+//   out[i] = (x_t - m) - logf(sum_v expf(x_v - m)),  m = max_v x_v;   t outside [0, V) gives -inf
 //
-// The [n, V] logits never leave registers.  NaN / inf operands are NOT covered (a NaN logit poisons its row; token_logprob_kernel's
-// NaN-as--inf rule is not reproduced).
+// Neither the two [n, V] logit tensors nor the mixed one leave registers.  NaN / inf operands are NOT covered, as in score_head.hip.
 //
-// Geometry (fixed; G is a function of (n, V, K) alone -- head_logprob_geom, mirrored by plangen_amd.engine.head_logprob_geometry):
-// * SH_BM = 256 scored rows x SH_BN = 256 vocabulary columns per tile, K step SH_BK = 64 (K % 64 == 0), eight waves, each owning 128 x 64 of
-//   the tile as 8 x 4 MFMA tiles (mfma_f32_16x16x32_bf16): the staging stream, the swizzled LDS layout, the two-phase schedule and its counted
-//   waits are those of gemm256.hip's 256x256 two-phase form (the invariants are written down there); the A rows are gathered through row_idx.
-// * A block owns ONE row tile and a contiguous group of `cpt` column tiles (G = ceil(ntn / cpt) groups) and walks them with the K loop per
-//   tile; the next tile's first loads go out before the current tile's fold, as gemm256 does before its stores.
-// * Fold after each column tile: a lane holds, for each of its 8 rows, 16 columns of the tile (4 n-tiles x 4).  It keeps a running (m, s)
-//   per row for ITS columns: m' = max(m, max of the 16), s = s * expf(m - m') + sum expf(x - m') -- 17 accurate expf per row and tile.  The
-//   lane that holds the target column stores x_t to out[i]: exactly one lane of one block does (plain store, no atomics).
-// * End of block: the four lanes of a row (shuffles, fixed order), then the four column waves (LDS, ascending) merge into one (m, s) per row,
-//   written to the partials workspace [G][n][2] fp32.  head_combine_kernel merges the G groups in ascending order and finishes out[i].
-// * Every reduction has a fixed shape that does not depend on the row's slot in the batch or on other rows: a row's bits are a function of
-//   its X row, W, its target, the temperature and (n, V, K).
-// * Rows >= n of the last row tile re-read row n - 1 (results dropped); columns >= V re-read W row V - 1 and are folded as -inf.
-// * LDS: 128 KiB of staging + 8 KiB for the end-of-block merge (its own region: the clamped tail stages of the last K tile may still be
-//   landing in the staging buffers) = 136 KiB, one block per CU, like gemm256 (MI355X: 160 KiB per CU).
+// Everything but the fold is head_logprob_kernel's (tiles of 256 rows x 256 columns, K step 64, the glds16 staging stream, the swizzle, the
+// two-phase schedule and its counted waits, column-tile groups, the XCD remap, [G][n][2] partials merged by head_combine_kernel); the
+// geometry is head_logprob_geom(2 n, V, K): a row tile holds CH_PAIRS = 128 pairs.  What differs:
+// * Pair placement.  The A tile is gathered through BOTH index lists so that pair p of a tile (p = wave row * 64 + q * 16 + lane row) has
+//   its cond row at accumulator row mt = 2q and its uncond row at mt = 2q + 1 of the lane that holds it: tile rows wr*128 + mt*16 + lr.  A
+//   pair never straddles a tile or a lane.  Pairs >= n of the last row tile re-read pair n - 1 (results dropped).
+// * Fold.  A lane loads its 16 bias values of the column tile, adds them to both rows, mixes in registers and runs the online (m, s) update
+//   on 4 mixed rows instead of 8 raw ones: no shuffle and no LDS for the mix.
+// * Merge: 4 lanes of a pair (shuffles, fixed order), the 4 column waves (LDS, ascending), the G groups (combine kernel, ascending): every
+//   reduction has a fixed shape, so a position's bits are a function of its two X rows, W, bias, its target, cfg_weight, the temperature
+//   and (n, V, K) -- not of its slot nor of the other positions.
 #include "score_head.h"
 
-HeadGeom head_logprob_geom(long n, int V, int K) {
-    HeadGeom g{};
-    g.ntm = (int)((n + SH_BM - 1) / SH_BM); g.ntn = (V + SH_BN - 1) / SH_BN;
-    // cost of a choice = rounds of SH_TARGET_BLOCKS blocks x (column tiles per block + 1 for the pipeline fill and the merge); ties keep fewer groups
-    long best = -1;
-    for (int cpt = g.ntn; cpt >= 1; --cpt) {
-        const int G = (g.ntn + cpt - 1) / cpt;
-        const long cost = (((long)g.ntm * G + SH_TARGET_BLOCKS - 1) / SH_TARGET_BLOCKS) * (cpt + 1);
-        if (best < 0 || cost < best) { best = cost; g.cpt = cpt; g.G = G; }
-    }
-    return g;
-}
-size_t head_logprob_ws_bytes(long n, int V, int K) {
-    const HeadGeom g = head_logprob_geom(n, V, K);
+#define CH_PAIRS (SH_BM / 2)
+
+size_t cfg_head_logprob_ws_bytes(long n, int V, int K) {
+    const HeadGeom g = head_logprob_geom(2 * n, V, K);
     return (((size_t)2 * 4 * g.G * (size_t)n) + 255) & ~(size_t)255;
 }
 
-__global__ __launch_bounds__(512) void head_logprob_kernel(const bf16* __restrict__ X, const bf16* __restrict__ W, const int32_t* __restrict__ row_idx,
-                                                           const int32_t* __restrict__ target, int n, int V, int K, int ntm, int ntn, int cpt, int G,
-                                                           float temperature, float* __restrict__ part, float* __restrict__ out) {
+__global__ __launch_bounds__(512) void cfg_head_logprob_kernel(const bf16* __restrict__ X, const bf16* __restrict__ W, const float* __restrict__ bias,
+                                                               const int32_t* __restrict__ cond_idx, const int32_t* __restrict__ uncond_idx,
+                                                               const int32_t* __restrict__ target, int n, int V, int K, int ntm, int ntn, int cpt, int G,
+                                                               float cfg_weight, float temperature, float* __restrict__ part, float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, l = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -53,7 +40,7 @@ __global__ __launch_bounds__(512) void head_logprob_kernel(const bf16* __restric
     // block -> (row tile, group): an XCD's share of the grid is 4 row tiles x all groups, so its L2 holds 4 A panels while the W tiles stream
     const int t = xcd_remap(blockIdx.x, gridDim.x);
     const int per = 4 * G, mg = t / per, rem = t - mg * per, gm = min(4, ntm - mg * 4);
-    const int m0 = (mg * 4 + rem % gm) * SH_BM, grp = rem / gm;
+    const int p0 = (mg * 4 + rem % gm) * CH_PAIRS, grp = rem / gm;      // first pair of the row tile
     const int c0 = grp * cpt, c1 = min(ntn, c0 + cpt);
 
     const int srow = w * 8 + (l >> 3);                           // + i*64
@@ -71,8 +58,10 @@ __global__ __launch_bounds__(512) void head_logprob_kernel(const bf16* __restric
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int r = i * 64 + srow;                         // LDS row of the half-tile -> (wave row r>>6, row r&63)
-            const int m = m0 + (r >> 6) * 128 + h * 64 + (r & 63), mc = m < n ? m : n - 1;
-            arow[h * 2 + i] = X + (long)(row_idx ? row_idx[mc] : mc) * K;
+            // wave row r>>6, accumulator row mt = h*4 + ((r&63)>>4), lane row r&15: pair (wave row)*64 + (mt>>1)*16 + (r&15), cond when mt is even
+            const int mt = h * 4 + ((r & 63) >> 4);
+            const int p = p0 + (r >> 6) * 64 + (mt >> 1) * 16 + (r & 15), pc = p < n ? p : n - 1;
+            arow[h * 2 + i] = X + (long)((mt & 1) ? uncond_idx[pc] : cond_idx[pc]) * K;
         }
     int n0 = 0;
     auto setup = [&](int ct) __attribute__((always_inline)) {
@@ -102,9 +91,9 @@ __global__ __launch_bounds__(512) void head_logprob_kernel(const bf16* __restric
 
     f32x4 acc[8][4];
     bf16x8 a[4][2], b0[2][2], b1[2][2];
-    float mrun[8], srun[8];
+    float mrun[4], srun[4];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { mrun[i] = -INFINITY; srun[i] = 0.f; }
+    for (int i = 0; i < 4; ++i) { mrun[i] = -INFINITY; srun[i] = 0.f; }
     const float invT = temperature > 0.f ? 1.f / temperature : 1.f;
     const bool scaled = temperature > 0.f;
 
@@ -176,85 +165,89 @@ __global__ __launch_bounds__(512) void head_logprob_kernel(const bf16* __restric
         const int ecol = n0 + wc * 64 + g * 4;                // the lane's first column; n-tile nt, element j -> ecol + nt*16 + j
         if (ct + 1 < c1) { setup(ct + 1); prologue(); }
         const int lim = V - ecol;                             // columns nt*16 + j >= lim are past the vocabulary
-        int tcol[8];
+        float bv[16];                                         // the lane's 16 bias values of this column tile (columns past V: clamped, folded as -inf)
 #pragma unroll
-        for (int mt = 0; mt < 8; ++mt) {
-            const int m = m0 + wr * 128 + mt * 16 + lr;
-            const int tg = target[m < n ? m : n - 1];
-            tcol[mt] = (m < n && tg >= 0 && tg < V) ? tg - ecol : -1;
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int v = ecol + nt * 16 + j;
+                bv[nt * 4 + j] = bias ? bias[v < V ? v : V - 1] : 0.f;
+            }
+        int tcol[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int p = p0 + wr * 64 + q * 16 + lr;
+            const int tg = target[p < n ? p : n - 1];
+            tcol[q] = (p < n && tg >= 0 && tg < V) ? tg - ecol : -1;
         }
 #pragma unroll
-        for (int mt = 0; mt < 8; ++mt) {
+        for (int q = 0; q < 4; ++q) {                         // pair q: cond in accumulator row 2q, uncond in 2q + 1 -- the mix never leaves the lane
             float xs[16];
             float mx = -INFINITY, xt = 0.f;
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float y = acc[mt][nt][j];
+                    const float c = acc[2 * q][nt][j] + bv[nt * 4 + j], u = acc[2 * q + 1][nt][j] + bv[nt * 4 + j];
+                    const float y = u + cfg_weight * (c - u);     // the expression of cfg_scan_kernel
                     float x = scaled ? __fmul_rn(y, invT) : y;
                     if (nt * 16 + j >= lim) x = -INFINITY;
-                    if (nt * 16 + j == tcol[mt]) xt = x;
+                    if (nt * 16 + j == tcol[q]) xt = x;
                     xs[nt * 4 + j] = x;
                     mx = fmaxf(mx, x);
                 }
-            const float mn = fmaxf(mrun[mt], mx), mref = mn == -INFINITY ? 0.f : mn;
+            const float mn = fmaxf(mrun[q], mx), mref = mn == -INFINITY ? 0.f : mn;
             float sum = 0.f;
 #pragma unroll
             for (int i = 0; i < 16; ++i) sum += expf(xs[i] - mref);
-            srun[mt] = srun[mt] * expf(mrun[mt] - mref) + sum;
-            mrun[mt] = mn;
-            const int tc = tcol[mt];
-            if (tc >= 0 && tc < 64 && (tc & 15) < 4) out[m0 + wr * 128 + mt * 16 + lr] = xt;      // the one lane that holds column t of this row
+            srun[q] = srun[q] * expf(mrun[q] - mref) + sum;
+            mrun[q] = mn;
+            const int tc = tcol[q];
+            if (tc >= 0 && tc < 64 && (tc & 15) < 4) out[p0 + wr * 64 + q * 16 + lr] = xt;      // the one lane that holds column t of this pair
         }
     }
 #undef SH_MFMA_SECTION
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // clamped tail stages must not outlive the block's LDS
     // ---- merge: the row's four lanes (g = 0..3), then the four column waves in ascending order
-    float2* red = (float2*)(smem + 2 * SH_BUF);           // [wc][SH_BM]
+    float2* red = (float2*)(smem + 2 * SH_BUF);           // [wc][CH_PAIRS]
 #pragma unroll
-    for (int mt = 0; mt < 8; ++mt) {
-        float m = mrun[mt], s = srun[mt];
+    for (int q = 0; q < 4; ++q) {
+        float m = mrun[q], s = srun[q];
         sh_merge(m, s, __shfl_xor(m, 16, 64), __shfl_xor(s, 16, 64));
         sh_merge(m, s, __shfl_xor(m, 32, 64), __shfl_xor(s, 32, 64));
-        if (g == 0) red[wc * SH_BM + wr * 128 + mt * 16 + lr] = make_float2(m, s);
+        if (g == 0) red[wc * CH_PAIRS + wr * 64 + q * 16 + lr] = make_float2(m, s);
     }
     __syncthreads();
-    if (tid < SH_BM && m0 + tid < n) {
+    if (tid < CH_PAIRS && p0 + tid < n) {
         float2 p = red[tid];
         float m = p.x, s = p.y;
 #pragma unroll
-        for (int c = 1; c < 4; ++c) { p = red[c * SH_BM + tid]; sh_merge(m, s, p.x, p.y); }
-        *(float2*)(part + ((long)grp * n + m0 + tid) * 2) = make_float2(m, s);
+        for (int c = 1; c < 4; ++c) { p = red[c * CH_PAIRS + tid]; sh_merge(m, s, p.x, p.y); }
+        *(float2*)(part + ((long)grp * n + p0 + tid) * 2) = make_float2(m, s);
     }
 }
 
-// out[i] holds x_t (written by the one block that met column t; untouched when t is outside [0, V)): merge the G groups' (m, s) in ascending
-// group order and finish the log-probability
-__global__ __launch_bounds__(256) void head_combine_kernel(const float* __restrict__ part, const int32_t* __restrict__ target, int n, int V, int G,
-                                                           float* __restrict__ out) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int t = target[i];
-    float m = -INFINITY;
-    for (int g = 0; g < G; ++g) m = fmaxf(m, part[((long)g * n + i) * 2]);
-    float s = 0.f;
-    for (int g = 0; g < G; ++g) { const float2 p = *(const float2*)(part + ((long)g * n + i) * 2); s += p.y * expf(p.x - m); }
-    out[i] = (t >= 0 && t < V) ? (out[i] - m) - logf(s) : -INFINITY;
-}
-
-void launch_head_combine(hipStream_t s, const float* part, const int32_t* target, long n, int V, int G, float* out) {
-    hipLaunchKernelGGL(head_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, target, (int)n, V, G, out);
-}
-
-bool launch_head_logprob(hipStream_t s, const bf16* X, const bf16* W, const int32_t* row_idx, const int32_t* target, long n, int V, int K,
-                         float temperature, float* part, float* out) {
-    if (n < 1 || V < 1 || K < SH_BK || K % SH_BK || n > (1L << 30)) return false;
-    const HeadGeom g = head_logprob_geom(n, V, K);
+bool launch_cfg_head_logprob(hipStream_t s, const bf16* X, const bf16* W, const float* bias, const int32_t* cond_idx, const int32_t* uncond_idx,
+                             const int32_t* target, long n, int V, int K, float cfg_weight, float temperature, float* part, float* out) {
+    if (n < 1 || V < 1 || K < SH_BK || K % SH_BK || n > (1L << 29)) return false;
+    const HeadGeom g = head_logprob_geom(2 * n, V, K);
     if ((long)g.ntm * g.G > 0x7fffffffL) return false;
-    auto kfn = head_logprob_kernel;
+    auto kfn = cfg_head_logprob_kernel;
     if (!PG_DYN_LDS(kfn, SH_LDS)) return false;
-    hipLaunchKernelGGL(kfn, dim3(g.ntm * g.G), dim3(512), SH_LDS, s, X, W, row_idx, target, (int)n, V, K, g.ntm, g.ntn, g.cpt, g.G, temperature, part, out);
+    hipLaunchKernelGGL(kfn, dim3(g.ntm * g.G), dim3(512), SH_LDS, s, X, W, bias, cond_idx, uncond_idx, target, (int)n, V, K, g.ntm, g.ntn, g.cpt, g.G,
+                       cfg_weight, temperature, part, out);
     launch_head_combine(s, part, target, n, V, g.G, out);
     return true;
+}
+
+// fp32 engines (parity mode): logits [2 cn, V] of one chunk, cond rows first -- row i <- the mixed row of pair i (bias included), in place
+__global__ __launch_bounds__(256) void cfg_mix_rows_kernel(float* __restrict__ logits, const float* __restrict__ bias, int cn, int V, float cfg_weight) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)cn * V) return;
+    const float b = bias ? bias[i % V] : 0.f;
+    const float c = logits[i] + b, u = logits[(long)cn * V + i] + b;
+    logits[i] = u + cfg_weight * (c - u);
+}
+void launch_cfg_mix_rows(hipStream_t s, float* logits, const float* bias, int cn, int V, float cfg_weight) {
+    hipLaunchKernelGGL(cfg_mix_rows_kernel, dim3((unsigned)(((long)cn * V + 255) / 256)), dim3(256), 0, s, logits, bias, cn, V, cfg_weight);
 }

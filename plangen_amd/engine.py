@@ -71,6 +71,23 @@ def head_logprob_geometry(n: int, V: int, K: int) -> dict:
     return dict(tile_rows=tile, tile_cols=tile, k_step=64, ntm=ntm, ntn=ntn, cpt=cpt, G=G, ws_bytes=(2 * 4 * G * n + 255) // 256 * 256)
 
 
+def image_score_index(L: int, T: int, R: int, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Index builder of ``Engine.score_image``: (cond, uncond) int64 [B * T], B = R // 2, image-major -- the rows of the [R, L + T - 1, hidden]
+    hidden tensor of one teacher-forced prefill of [prompt (L columns) | image embeddings 0 .. T-2], viewed as [R * (L + T - 1), hidden], that
+    score image token j of image b: column L - 1 + j (the last prompt column scores token 0, the embedding of token j - 1 scores token j) of
+    row 2b (cond) and of row 2b + 1 (uncond).  R must be even and >= 2, L >= 1 and T >= 1, else ValueError."""
+    L, T, R = int(L), int(T), int(R)
+    if R < 2 or R % 2:
+        raise ValueError(f"R={R} must be even and >= 2 (CFG-interleaved rows: 2b cond, 2b + 1 uncond)")
+    if L < 1 or T < 1:
+        raise ValueError(f"L={L} and T={T} must be >= 1")
+    W = L + T - 1
+    col = L - 1 + torch.arange(T, dtype=torch.int64, device=device).view(1, T)
+    row = 2 * torch.arange(R // 2, dtype=torch.int64, device=device).view(-1, 1)
+    cond = (row * W + col).reshape(-1)
+    return cond, cond + W
+
+
 class Engine:
     """MI355X engine for the layout->image path.
 
@@ -101,6 +118,7 @@ class Engine:
         self.tdtype = _torch_dt(self.code)
         self.device = torch.device("cuda", device)
         self.max_rows = max_rows
+        self.max_prompt = max_prompt
         self.max_new = max_new if max_new is not None else cfg.img_tokens
         self.max_images = max_images if max_images is not None else max(1, max_rows // 2)
         c = _lib.pg_config()
@@ -560,6 +578,87 @@ class Engine:
         tgt = self._dev(target_ids, torch.int32)
         hid = self.prefill_embeds(embeds, pad_len, position_mode=position_mode, return_hidden=True, hidden_dtype=self.tdtype)
         return self._score_hidden(hid, tgt, pad_len, score_from, temperature)
+
+    # ------------------------------------------------------------------ scoring given images
+    def _cfg_score_args(self, what, target, cond_idx, uncond_idx):
+        t = self._dev(torch.as_tensor(target), torch.int32).reshape(-1)
+        ci = self._dev(torch.as_tensor(cond_idx), torch.int32).reshape(-1)
+        ui = self._dev(torch.as_tensor(uncond_idx), torch.int32).reshape(-1)
+        if ci.numel() != t.numel() or ui.numel() != t.numel():
+            raise PlanGenError(f"{what}: {ci.numel()} cond / {ui.numel()} uncond indices for {t.numel()} targets")
+        return t, ci, ui, torch.full((t.numel(),), float("nan"), dtype=torch.float32, device=self.device)
+
+    def cfg_head_logprob(self, x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], target: torch.Tensor, cond_idx: torch.Tensor,
+                         uncond_idx: torch.Tensor, cfg_weight: float = 5.0, temperature: float = 1.0) -> torch.Tensor:
+        """``pg_op_cfg_head_logprob``: log softmax((yu + cfg_weight * (yc - yu)) / temperature)[target[i]] with yc / yu = x[cond_idx[i]] /
+        x[uncond_idx[i]] . w^T + bias -> fp32 [n]; x [rows, K] and w [V, K] are converted to the compute dtype, bias fp32 [V] or None."""
+        x = self._dev(x, self.tdtype)
+        w = self._dev(w, self.tdtype)
+        b = self._dev(bias, torch.float32).reshape(-1) if bias is not None else None
+        rows, K = x.shape
+        V = w.shape[0]
+        if b is not None and b.numel() != V:
+            raise PlanGenError(f"cfg_head_logprob: bias has {b.numel()} entries for V={V}")
+        t, ci, ui, out = self._cfg_score_args("cfg_head_logprob", target, cond_idx, uncond_idx)
+        self._check(self.lib.pg_op_cfg_head_logprob(self.h, self._p(x), rows, self._p(w), V, K, self._p(b), self._p(ci), self._p(ui), self._p(t),
+                                                    t.numel(), float(cfg_weight), float(temperature), self._p(out), self.stream),
+                    "pg_op_cfg_head_logprob")
+        self._keep = [x, w, b, t, ci, ui, out]
+        return out
+
+    def score_image_tokens(self, hidden: torch.Tensor, target: torch.Tensor, cond_idx: torch.Tensor, uncond_idx: torch.Tensor,
+                           cfg_weight: float = 5.0, temperature: float = 1.0) -> torch.Tensor:
+        """``pg_score_image_tokens``: the guided log-probability of image token target[i] from the hidden rows cond_idx[i] / uncond_idx[i] of
+        ``hidden`` [..., hidden] (compute dtype): gen_head on every row of ``hidden``, CFG mix, temperature, log-softmax -> fp32 [n]."""
+        if hidden.dtype != self.tdtype:
+            raise PlanGenError(f"score_image_tokens: hidden must be {self.tdtype} (the compute dtype), got {hidden.dtype}")
+        h = self._dev(hidden).reshape(-1, hidden.shape[-1])
+        t, ci, ui, out = self._cfg_score_args("score_image_tokens", target, cond_idx, uncond_idx)
+        self._check(self.lib.pg_score_image_tokens(self.h, self._p(h), _dt(h), h.shape[0], self._p(ci), self._p(ui), self._p(t), t.numel(),
+                                                   float(cfg_weight), float(temperature), self._p(out), self.stream), "pg_score_image_tokens")
+        self._keep = [h, t, ci, ui, out]
+        return out
+
+    def score_image_max_tokens(self) -> int:
+        """Largest number of packed tokens (rows x columns, pads excluded) ``score_image`` sends through one prefill: every per-token buffer of
+        the prefill -- the widest is the fp32 gate|up tensor, 2 * inter floats per token -- stays below 2^31 BYTES, so no index of any kernel on
+        the way can pass 2^31 whatever unit it counts in."""
+        c = self.cfg
+        widest = max(2 * int(c.inter), 3 * int(c.n_heads) * int(c.head_dim), int(c.hidden), int(c.gen_head_dim))
+        return (2 ** 31 - 1) // (4 * widest)
+
+    def score_image(self, ids: torch.Tensor, pad_len: Sequence[int], codes: torch.Tensor, cfg_weight: float = 5.0,
+                    temperature: float = 1.0) -> torch.Tensor:
+        """Teacher-forced log-probabilities of given image tokens under the guided distribution the image sampler draws from, in ONE
+        prefill instead of the 576-step loop.  ``ids`` int [2B, L]: the CFG-interleaved left-padded prompts ``prefill`` takes (``pad_len``
+        [2B]); ``codes`` int [B, T]: the image tokens.  Returns fp32 [B, T]: log softmax((u + cfg_weight * (c - u)) / temperature)[codes[b, j]]
+        with c / u the gen_head logits of rows 2b / 2b + 1 after [prompt | codes[b, :j]] -- what ``decode_image_tokens(force_tokens=codes,
+        force_mask=zeros, return_logprobs=True)`` returns.  Needs max_prompt >= L + T - 1 and at most ``score_image_max_tokens()`` packed
+        tokens (PlanGenError otherwise).  The engine is left prefilled with the L + T - 1 columns."""
+        if ids.dim() != 2 or ids.shape[0] < 2 or ids.shape[0] % 2:
+            raise PlanGenError(f"score_image: ids must be [2B, L] with CFG-interleaved rows (got {tuple(ids.shape)})")
+        R, L = ids.shape
+        B = R // 2
+        if codes.dim() != 2 or codes.shape[0] != B or codes.shape[1] < 1:
+            raise PlanGenError(f"score_image: codes must be [B, T] = [{B}, T >= 1] for {R} prompt rows (got {tuple(codes.shape)})")
+        if len(pad_len) != R:
+            raise PlanGenError(f"score_image: {len(pad_len)} pad lengths for {R} rows")
+        T = codes.shape[1]
+        W = L + T - 1
+        longest = W - min(int(p) for p in pad_len)
+        if longest > self.max_prompt:
+            raise PlanGenError(f"score_image: [prompt | image tokens] is {longest} tokens long: the engine needs max_prompt >= {longest} (it has {self.max_prompt})")
+        ntok = sum(W - int(p) for p in pad_len)
+        if ntok > self.score_image_max_tokens():
+            raise PlanGenError(f"score_image: {ntok} packed tokens in one prefill exceed the limit of {self.score_image_max_tokens()}: score fewer images per call")
+        cond, uncond = image_score_index(L, T, R, device=self.device)
+        codes = self._dev(codes, torch.int32)
+        emb = torch.empty((R, W, self.cfg.hidden), dtype=torch.float32, device=self.device)
+        emb[:, :L] = self.embed_tokens(ids)
+        if T > 1:
+            emb[:, L:] = self.gen_embed(codes[:, :T - 1]).view(B, T - 1, -1).repeat_interleave(2, dim=0)      # the same tokens on both rows of a pair
+        hid = self.prefill_embeds(emb, pad_len, position_mode=0, return_hidden=True, hidden_dtype=self.tdtype)
+        return self.score_image_tokens(hid, codes.reshape(-1), cond, uncond, cfg_weight, temperature).view(B, T)
 
     def generate_text(self, max_new_tokens: int, eos_id: int, min_new_tokens: int = 0, temperature: float = 0.0, top_k: int = 0,
                       top_p: float = 1.0, seed: int = 0, return_logits: bool = False, return_logprobs: bool = False):

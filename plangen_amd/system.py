@@ -75,7 +75,8 @@ class System:
     off when absent), top_k / top_p (image sampling filters, off when absent)
     and text_temperature / text_top_k / text_top_p (sampled layout / caption decode, greedy when absent); select_best (parallel_size > 1:
     keep each prompt's most probable replica, off when absent) and layout_best_of (stage 1: draw N layouts per row and keep the most
-    probable, 1 when absent); score_gt_layout (plan / uni_2stage / mmu: also score batch['gt_grounding'], see score_layouts; off when absent).
+    probable, 1 when absent); score_gt_layout (plan / uni_2stage / mmu: also score batch['gt_grounding'], see score_layouts; off when absent);
+    score_gt_image (uni / uni_2stage: also score batch['image'], see score_images; off when absent).
     """
 
     def __init__(self, cfg: PlanGenConfig, engine: Engine, args: Optional[SimpleNamespace] = None, codec=None):
@@ -345,21 +346,7 @@ class System:
         if pred_image:
             if not use_uni_prompt_in_t2i:
                 raise PlanGenError("use_uni_prompt_in_t2i=False: the reference asserts False on this branch too (plangen_base.py:645-648)")
-            ids, mask = batch["uni_inputs_ids"], batch["uni_attention_mask"]
-            L = ids.shape[1]
-            m = mask[:, :L]
-            cond = [ids[i][m[i].bool()].tolist() for i in range(ids.shape[0])]
-            neg = batch.get("neg_inputs_ids")
-            if getattr(self.args, "use_neg_box", False):
-                # plangen_base.py:652-670: ONE negative prompt PER SAMPLE, wrap_uni_prompt(neg_base_caption, neg_gt_grounding)
-                if "neg_base_caption" in batch and self.codec is not None:
-                    neg = [self.wrap_uni_prompt(c, g)[1].tolist() for c, g in zip(batch["neg_base_caption"], batch["neg_gt_grounding"])]
-                elif not (neg is not None and len(neg) and isinstance(neg[0], (list, tuple, torch.Tensor))):
-                    raise PlanGenError("use_neg_box=True needs batch['neg_base_caption'] / ['neg_gt_grounding'] (with a tokenizer) "
-                                       "or one pre-tokenised negative prompt per sample in batch['neg_inputs_ids']")
-            if neg is None:
-                neg = self.wrap_uni_prompt(getattr(self.args, "neg_prompt", ""), "")[1].tolist()
-            cfg_ids, cfg_mask = self.t2i_infer_collate_batch(cond, neg)
+            cfg_ids, cfg_mask = self._cfg_prompt(batch)
             dec, edit_mask = self.t2i(cfg_ids, cfg_mask, gt_image=batch.get("image"), edit_region=batch.get("edit_region"))
             out["pr_tokens"] = self.last_generated_tokens
             if self.last_selection is not None:
@@ -369,6 +356,11 @@ class System:
         else:
             out["pr_image"] = batch.get("image")
         out["pr_grounding"] = pr_grounding
+        if getattr(self.args, "score_gt_image", False) and pred_image and batch.get("image") is not None:
+            # uni / uni_2stage: P(ground-truth image | the prompt the image above was generated from) under the guided distribution.  Runs after
+            # the generation: it re-prefills.
+            sc = self.score_images(batch, scored=(batch["edit_region"] != 0) if batch.get("edit_region") is not None else None)
+            out["gt_image_logprob"] = {k: sc[k] for k in ("sum", "mean", "n_tokens")}
         if getattr(self.args, "score_gt_layout", False) and pred_layout and batch.get("gt_grounding") is not None:
             # plan / uni_2stage: P(ground-truth layout | caption); mmu: P(ground-truth layout | image).  Runs after the generation: it re-prefills.
             sc = self.score_layouts(batch, given="image" if is_mmu else "caption")
@@ -382,9 +374,67 @@ class System:
                 extra = {k: out[k].cpu().tolist() for k in ("pr_replica", "pr_score", "pr_layout_replica", "pr_layout_score") if k in out}
                 if "gt_layout_logprob" in out:
                     extra["gt_layout_logprob"] = out["gt_layout_logprob"]
+                if "gt_image_logprob" in out:
+                    extra["gt_image_logprob"] = out["gt_image_logprob"]
                 json.dump(dict(base_caption=base_caption, gt_grounding=batch.get("gt_grounding"),
                                pr_grounding=pr_grounding if pred_layout else "", **extra), f)
         return out
+
+    def _cfg_prompt(self, batch: dict) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The CFG batch of the image stage: cond rows from batch['uni_inputs_ids' / 'uni_attention_mask'], the negative prompt from
+        batch['neg_inputs_ids'] / args.use_neg_box / args.neg_prompt -> (cfg_inputs_ids [2B, L], cfg_attention_mask [2B, L + T])."""
+        ids, mask = batch["uni_inputs_ids"], batch["uni_attention_mask"]
+        L = ids.shape[1]
+        m = mask[:, :L]
+        cond = [ids[i][m[i].bool()].tolist() for i in range(ids.shape[0])]
+        neg = batch.get("neg_inputs_ids")
+        if getattr(self.args, "use_neg_box", False):
+            # plangen_base.py:652-670: ONE negative prompt PER SAMPLE, wrap_uni_prompt(neg_base_caption, neg_gt_grounding)
+            if "neg_base_caption" in batch and self.codec is not None:
+                neg = [self.wrap_uni_prompt(c, g)[1].tolist() for c, g in zip(batch["neg_base_caption"], batch["neg_gt_grounding"])]
+            elif not (neg is not None and len(neg) and isinstance(neg[0], (list, tuple, torch.Tensor))):
+                raise PlanGenError("use_neg_box=True needs batch['neg_base_caption'] / ['neg_gt_grounding'] (with a tokenizer) "
+                                   "or one pre-tokenised negative prompt per sample in batch['neg_inputs_ids']")
+        if neg is None:
+            neg = self.wrap_uni_prompt(getattr(self.args, "neg_prompt", ""), "")[1].tolist()
+        return self.t2i_infer_collate_batch(cond, neg)
+
+    @torch.no_grad()
+    def score_images(self, batch: dict, scored: Optional[torch.Tensor] = None, cfg_weight: Optional[float] = None,
+                     temperature: Optional[float] = None) -> dict:
+        """How probable the model finds the images of ``batch['image']`` given the image-stage prompt: log P(image tokens | caption, layout)
+        under the guided distribution the sampler draws from (args.cfg_weight; args.temperature when > 0, else 1.0 -- greedy decoding has no
+        distribution of its own), nothing generated.  The images are VQ-encoded (the engine needs with_vq_encoder, PlanGenError otherwise),
+        the CFG prompt is the one ``uni_generate`` hands to ``t2i`` (``_cfg_prompt``), and the batch is scored in chunks of as many images as
+        the engine's max_rows and ``Engine.score_image_max_tokens`` allow, each one teacher-forced prefill + the fused CFG scoring head
+        (``Engine.score_image``).  scored: bool [B, T] (e.g. ``edit_region != 0``) -- only those positions count; None: all T.
+        Returns dict(sum, mean, n_tokens: one entry per image; logprobs fp32 [B, T], every position): mean = sum / n_tokens (0.0 when
+        nothing is scored)."""
+        eng = self.engine
+        if not eng._c.with_vq_encoder:
+            raise PlanGenError("score_images VQ-encodes batch['image']: the engine must be created with_vq_encoder=True")
+        a = self.args
+        cfg_weight = a.cfg_weight if cfg_weight is None else cfg_weight
+        if temperature is None:
+            temperature = a.temperature if float(a.temperature) > 0 else 1.0
+        img = batch["image"]
+        B = img.shape[0]
+        gi = img.to(torch.bfloat16) if eng.dtype == "bf16" else img
+        codes = self.vl_gpt.gen_vision_model.encode(gi)[-1][-1].reshape(B, -1).to(torch.int32)
+        T = codes.shape[1]
+        cfg_ids, cfg_mask = self._cfg_prompt(batch)
+        L = cfg_ids.shape[1]
+        pad = Engine.pad_len_from_mask(cfg_mask, L)
+        per = min(eng.max_rows // 2, eng.score_image_max_tokens() // (2 * (L + T - 1)))
+        if per < 1:
+            raise PlanGenError(f"score_images: one image pair of {L + T - 1} columns does not fit the engine (max_rows={eng.max_rows}, "
+                               f"at most {eng.score_image_max_tokens()} packed tokens per prefill)")
+        lp = torch.cat([eng.score_image(cfg_ids[2 * b0:2 * (b0 + per)], pad[2 * b0:2 * (b0 + per)], codes[b0:b0 + per], cfg_weight, temperature)
+                        for b0 in range(0, B, per)])
+        m = torch.ones((B, T), dtype=torch.bool, device=lp.device) if scored is None else scored.to(lp.device).bool().reshape(B, T)
+        n_tok = m.sum(-1)
+        sums = torch.where(m, lp, torch.zeros_like(lp)).sum(-1)
+        return dict(sum=sums.cpu().tolist(), mean=(sums / n_tok.clamp(min=1)).cpu().tolist(), n_tokens=n_tok.cpu().tolist(), logprobs=lp)
 
     def _layout_ids(self, grounding: str, strip_open: bool) -> List[int]:
         """Token ids of a layout string without BOS; strip_open: also without the leading ``<grounding>`` the stage-1 prompt already carries."""

@@ -21,6 +21,7 @@ share_replicas = 0                     # parallel_size > 1: 1 = prefill every pr
 select_best = False                    # parallel_size > 1: score every replica by the mean log-probability of its image tokens, VQ-decode and keep only the best one per prompt (an extension beyond the reference)
 layout_best_of = 1                     # uni_2stage / plan with text_temperature > 0: draw this many layouts per row and keep the one with the highest mean token log-probability (an extension beyond the reference)
 score_gt_layout = False                # plan / uni_2stage / mmu: also write gt_layout_logprob = {sum, mean, n_tokens} per row to the batch JSON: log P(gt_grounding + EOS | caption) (mmu: | image) from one teacher-forced prefill (an extension beyond the reference)
+score_gt_image = False                 # uni / uni_2stage: also write gt_image_logprob = {sum, mean, n_tokens} per row to the batch JSON: log P(VQ tokens of the ground-truth image | prompt) under the guided distribution (cfg_weight, temperature), from one teacher-forced prefill; with edit_region only the edited positions count (an extension beyond the reference)
 use_teacher_forcing = False            # base.py:36
 use_neg_box = False                    # base.py:121
 neg_prompt = ""                        # base.py:129: wrapped as wrap_uni_prompt(neg_prompt, '') for every uncond CFG row (:673)

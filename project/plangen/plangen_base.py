@@ -75,16 +75,19 @@ class System(_HotPath):
         needs_image = task in ("t2i", "uni", "uni_2stage")
         # rows: the CFG batch of every replica, or the stage-1 batch with layout_best_of draws per row, whichever is larger
         stage1 = task in ("uni_2stage", "plan")
-        eng = Engine(cfg, dtype=args.dtype, max_rows=max(2 * bs * int(args.parallel_size), bs * layout_best_of if stage1 else 0), max_prompt=int(getattr(args, "max_prompt", 768)),
+        # score_gt_image prefills [prompt | image tokens]: the prompt capacity grows by the image's length
+        max_prompt = int(getattr(args, "max_prompt", 768)) + (cfg.img_tokens - 1 if getattr(args, "score_gt_image", False) else 0)
+        eng = Engine(cfg, dtype=args.dtype, max_rows=max(2 * bs * int(args.parallel_size), bs * layout_best_of if stage1 else 0), max_prompt=max_prompt,
                      max_new=max(cfg.img_tokens if needs_image else 1, text_new if task != "uni" and task != "t2i" else 1),
                      max_images=bs * int(args.parallel_size), with_lm_head=task in ("uni_2stage", "mmu", "plan"),
-                     with_vq_encoder=bool(args.use_teacher_forcing), with_vision=task == "mmu", device=device,
+                     with_vq_encoder=bool(args.use_teacher_forcing) or bool(getattr(args, "score_gt_image", False)), with_vision=task == "mmu", device=device,
                      kv_dtype=cfg.kv_dtype)
         super().__init__(cfg, eng, SimpleNamespace(seed=args.seed, parallel_size=args.parallel_size, cfg_weight=args.cfg_weight,
                                                    temperature=args.temperature, top_k=cfg.top_k, top_p=cfg.top_p,
                                                    text_temperature=cfg.text_temperature, text_top_k=cfg.text_top_k, text_top_p=cfg.text_top_p,
                                                    layout_grammar=cfg.layout_grammar, select_best=select_best, layout_best_of=layout_best_of,
                                                    score_gt_layout=bool(getattr(args, "score_gt_layout", False)),
+                                                   score_gt_image=bool(getattr(args, "score_gt_image", False)),
                                                    use_teacher_forcing=args.use_teacher_forcing, share_replicas=cfg.share_replicas,
                                                    debug_max_seq_len=args.debug_max_seq_len, janus_hw=args.janus_hw,
                                                    neg_prompt=getattr(args, "neg_prompt", ""),

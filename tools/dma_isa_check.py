@@ -234,6 +234,9 @@ SPECS = [
     ("score_head", r"head_logprob_kernel", dict(kind="fifo", g=2, need="ph2", tile_cls=lambda n: n & 3, slot_reuse=lambda c: 8, strict=True, stagger=True,
                                                 why="the fused scoring head walks its column tiles on gemm256's two-phase stream (same half-tile order, counted waits and drained "
                                                     "fragment reads); its fold and merge touch LDS only past the staging buffers")),
+    ("score_cfg_head", r"cfg_head_logprob_kernel", dict(kind="fifo", g=2, need="ph2", tile_cls=lambda n: n & 3, slot_reuse=lambda c: 8, strict=True, stagger=True,
+                                                        why="head_logprob_kernel's stream, schedule and waits unchanged (the A rows are gathered through two index lists); "
+                                                            "the CFG mix and the fold run in registers, the merge touches LDS only past the staging buffers")),
     ("diag_gemm_bw", r"gemm_bw_kernel", dict(kind="fifo", g=8, need="bw", tile_cls=lambda n: 0, slot_reuse=lambda c: 4, strict=False,
                                             why="libplangen_diag.so experiment: 4-stage ring, tile t+1 retired by vmcnt(8) + the barrier of iteration t and first read behind that barrier (weak form)")),
     ("gemm", r"gemm_sk4_kernel", dict(kind="sk4")),
