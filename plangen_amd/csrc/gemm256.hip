@@ -1,100 +1,50 @@
-// 256x256x64 (and 512x128x64) bf16 MFMA GEMM for gfx950, eight waves, 128 / 160 KiB of LDS, one persistent
-// block per CU.
+// 256x256x64 bf16 MFMA GEMM for gfx950, eight waves (2x4, 128x64 of C each), 128 KiB of LDS, one persistent block per CU.
 //
 //   C[M,N] = A[M,K] . W[N,K]^T      (same loaders / epilogue as gemm.hip's 128x128 kernel)
 //
-// Schedule (designed for this kernel; the numbers below are what the synchronisation relies on):
-//
-// * A K tile (64 wide) is staged as FOUR 16 KiB half-tiles named after the C quadrant that
-//   consumes them, not after their position in memory:
-//       HA0 = A rows {wr*128 + [0,64)}      (m-tiles 0-3 of every wave)      read in phase 1
-//       HB0 = W rows {wc*64  + [0,32)}      (n-tiles 0-1 of every wave)      read in phase 1
-//       HB1 = W rows {wc*64  + 32 + [0,32)} (n-tiles 2-3)                    read in phase 2
-//       HA1 = A rows {wr*128 + 64 + [0,64)} (m-tiles 4-7)                    read in phase 3
-//   Every wave owns a 128x64 piece of C = 8 x 4 MFMA tiles and walks its four 64x32 quadrants in
-//   the order (0,0) (0,1) (1,1) (1,0): one quadrant = 16 MFMAs (4 m x 2 n x 2 k-steps) per phase,
-//   each phase needs only ONE new half-tile's fragments (phase 4 none: B0 stays in registers).
-// * Two LDS buffers (even / odd K tile).  Because a half-tile is dead as soon as its fragments
-//   are in registers, its slot is re-staged for tile kt+2 long before the tile ends:
-//       phase 1 of tile kt stages HB1(kt+1), phase 2 HA1(kt+1), phase 3 HA0(kt+2), phase 4 HB0(kt+2)
-//   i.e. the global_load_lds stream is simply "tile after tile, halves in the order HA0 HB0 HB1
-//   HA1", running 5-6 phases (more than one whole K tile) ahead of its consumer.  Four half-tiles
-//   (64 KiB per CU) are in flight at any time; the loop never waits for vmcnt(0).
-// * WAR: a slot is re-staged >= 2 phases after the phase that read it (HA0/HB0: read P1, staged
-//   P3/P4; HB1: read P2, staged P1 of the next tile; HA1: read P3, staged P2 of the next tile).
-//   RAW: the phase BEFORE a half-tile is read ends its load section with s_waitcnt vmcnt(8)
-//   (8 = 2 loads x the 4 half-tiles issued after the one needed), then the phase barriers.
-//   Both margins hold with the two wave groups running one barrier apart (below).
-//   TWO-PHASE FORM (PH == 2, the default since round 5; invariants restated in round 6 after ADVICE r5): phase A reads HB0, HA0, HB1 and
-//   stages HB1(kt+1), HA1(kt+1); phase B reads HA1 and stages HA0(kt+2), HB0(kt+2).  A slot is therefore re-staged in the phase RIGHT
-//   AFTER the one that read it (HA0 / HB0: read A(kt), staged B(kt); HA1: read B(kt), staged A(kt+1); HB1: read A(kt), staged A(kt+1)), and
-//   with the groups one barrier apart the LEADING group issues that re-stage right behind the very barrier that ends the LAGGING group's
-//   load section.  WAR rule of this form: every wave executes `s_waitcnt lgkmcnt(0)` BEFORE the barrier that ends its load section (its
-//   fragments are in registers when it arrives), so one barrier separates the last read of a slot from any global_load_lds into it.  (Round 5
-//   had the lgkmcnt(0) BEHIND that barrier: only the DMA's memory latency separated the two.  tools/dma_isa_check.py checks the new rule:
-//   a re-stage needs >= 2 barriers since the slot's last read, or 1 barrier with the read drained in front of it.)
-//   RAW of the two-phase form: phase B's load section ends with vmcnt(6) (HB1(kt+1) and everything older landed), phase A's with vmcnt(8)
-//   (HA1(kt) landed); both one full phase (two barriers) before the fragments are read.
-// * Every phase = [ds_read fragments, issue 2 global_load_lds, counted vmcnt] s_barrier
-//   [lgkmcnt(0), 16 MFMAs under s_setprio 1] s_barrier.  Waves with wr == 1 pass one extra barrier
-//   before the loop, so on every SIMD one wave is in its MFMA section while the other one is in
-//   its load section: LDS reads and address arithmetic hide under the other wave's MFMAs.
-// * K tiles past the end are staged from the last valid tile (never read): the loop is
-//   branch-free and the vmcnt counts stay exact.
-// * Geometry is a template (WM x WN waves, 128x64 of C per wave): 2x4 = 256x256 (A half-tile 16 KiB = 2 loads
-//   per thread, W half-tile 16 KiB = 2 loads, counted wait vmcnt(8)) is what runs; 4x2 = 512x128 (A half-tile
-//   32 KiB = 4 loads, W half-tile 8 KiB = 1 load, vmcnt(10), all 160 KiB of LDS) is correct but slower (below).
-//   Any 4 consecutive half-tiles of the stream are two A and two W halves, hence one count per geometry.
-#include <type_traits>
-#include "gemm_common.h"
+// The tile pipeline -- half-tile names, staging stream, swizzle, the two-phase schedule with its counted waits, RAW / WAR rules and the
+// one-barrier stagger of the two wave groups -- is tile256.h's; its invariants are written down there.  This file adds:
+// * the persistent tile loop (XCD-grouped tile order) and the tile height MT1 (below);
+// * the epilogues, chosen per instantiation / at run time: RoPE + KV-cache write (ROPE, act 3), SwiGLU (act 2), GroupNorm partial sums
+//   next to the plain store (GN), and the plain batched store (bias / residual / GELU) of gemm_common.h;
+// * the FOUR-PHASE A/B form (PH == 4, option gemm256 & 8; the default before round 5) on the same stream, LDS layout and staging
+//   functions: one quadrant = 16 MFMAs (4 m x 2 n x 2 k-steps) per phase, each phase needs only ONE new half-tile's fragments (phase 4
+//   none: B0 stays in registers) and stages one half-tile:
+//       phase 1 of tile kt reads HB0 HA0, stages HB1(kt+1); phase 2 reads HB1, stages HA1(kt+1); phase 3 reads HA1, stages HA0(kt+2);
+//       phase 4 stages HB0(kt+2).
+//   Every phase = [ds_read fragments, issue 2 global_load_lds, counted vmcnt] s_barrier [lgkmcnt(0), 16 MFMAs under s_setprio 1] s_barrier.
+//   WAR: a slot is re-staged >= 2 phases after the phase that read it.  RAW: the phase BEFORE a half-tile is read ends its load section
+//   with the four half-tiles issued after the one needed still in flight (phase 3 needs no wait: phase 2's covers HA1).
+// (A 4x2-wave 512x128 geometry was measured for the Cout = 128 convolutions: 470-560 TFLOP/s against 640-690 for the 128x128 kernel; removed.)
+#include "tile256.h"
 
-#define G2_BK 64
-
-__device__ __forceinline__ void g2_barrier() { asm volatile("s_barrier" ::: "memory"); }
-
-// MT1 (round 5): m-tiles of a wave's SECOND row half (4 = the 256-row tile; 3 / 2 = 224 / 192 rows per block at WM = 2).  The tile height is
+// MT1 (round 5): m-tiles of a wave's SECOND row half (4 = the 256-row tile; 3 / 2 = 224 / 192 rows per block).  The tile height is
 // picked per launch so that ceil(tiles / 256 CUs) x height is smallest: at the bench's packed prompt batch (13.4 k tokens) o_proj / down_proj are
 // 424 tiles of 256 rows = 1.66 rounds on 256 CUs (17 % of the launch idle) but 480 tiles of 224 rows = 1.875 rounds of 7/8 the work.  Only
-// the fragment reads and MFMAs of the second half shrink (phases 3 / 4: 4 x MT1 MFMAs... MT1 m-tiles x 2 n-tiles x 2 k-steps); the staging
+// the fragment reads and MFMAs of the second half shrink (MT1 m-tiles x 2 n-tiles x 2 k-steps per quadrant); the staging
 // stream, its counted waits and the LDS layout are unchanged (the half-tile HA1 still brings 64 rows per wave row, 64 - 16 MT1 of them unused).
-template <class AL, class EP, int WM, int WN, bool ROPE = false, int MT1 = 4, int PH = 4, bool GN = false>      // GN (round 6): the epilogue also emits GroupNorm partial sums -- its own instantiation: in the common one its
-                                                                                                              // extra live registers spilled 27-61 VGPRs and cost the prefill GEMMs 1.5 %.  ROPE: the prefill QKV instantiation (RoPE + KV-write epilogue, act 3) -- its own kernel so its
+// PH == 2 (round 5): two phases per K tile instead of four, half the barriers per MFMA: the four-phase form measured only -3.5 % when a quarter of the
+// MFMAs of phases 3 / 4 was removed (224-row tiles), i.e. its phases are bound by their fixed part (two barriers, fragment reads, staging, counted wait).
+template <class AL, class EP, bool ROPE = false, int MT1 = 4, int PH = 4, bool GN = false>      // GN (round 6): the epilogue also emits GroupNorm partial sums -- its own instantiation: in the common one its
+                                                                                              // extra live registers spilled 27-61 VGPRs and cost the prefill GEMMs 1.5 %.  ROPE: the prefill QKV instantiation (RoPE + KV-write epilogue, act 3) -- its own kernel so its
 __global__ __launch_bounds__(512) void gemm256_kernel(                 // register needs do not reach the other users of this template
 AL al, const bf16* __restrict__ W, long ldb, long strideA, long strideB,
                                                      long strideA2, long strideB2, EP ep, int M, int N, int K, int ntm, int ntn) {
-    static_assert(WM * WN == 8 && (WN == 2 || WN == 4), "eight waves, 128x64 of C each");
-    static_assert(MT1 >= 1 && MT1 <= 4, "second row half: 1..4 m-tiles");
-    static_assert(PH == 4 || (PH == 2 && WM == 2 && WN == 4), "two-phase schedule: 2x4 waves only (its counted waits assume 2 loads per half-tile)");
+    static_assert(MT1 >= 1 && MT1 <= 4 && (PH == 2 || PH == 4), "second row half: 1..4 m-tiles; two or four phases per K tile");
     constexpr int WROWS = 64 + 16 * MT1, NMT = 4 + MT1;          // rows / m-tiles of C per wave row
-    constexpr int BM = WM * WROWS, BN = WN * 64;
-    constexpr int AH = WM * 64 * 128, BH = WN * 32 * 128;        // bytes per A / W half-tile
-    constexpr int BUF = 2 * AH + 2 * BH;                         // one K tile: [HA0 | HA1 | HB0 | HB1]
-    constexpr int NA = WM, NB = WN / 2;                          // global_load_lds per thread per half-tile
+    constexpr int BM = 2 * WROWS, BN = 256;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, l = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int batch = blockIdx.y, batch2 = blockIdx.z;
     const long coff = (long)batch * ep.e.strideC + (long)batch2 * ep.e.strideC2;
     const long roff = (long)batch * ep.e.strideR;
     al.A_offset(strideA * batch + strideA2 * batch2);
     const bf16* Wb = W + strideB * batch + strideB2 * batch2;
-    const int nk = K / G2_BK;
+    const int nk = K / T256_BK;
     const int NT = ntm * ntn, G = gridDim.x;
     const bool vec = ep.vec_ok(coff, roff);
+    Tile256<AL> T(al, smem, K);
+    const int wr = T.wr, wc = T.wc, g = T.g, lr = T.lr;
 
-    // staging: wave w, instruction i covers LDS rows (i*8 + w)*8 .. +7 of a half-tile; the swizzle term
-    // (row>>1)&7 = (w&1)*4 + (l>>4) does not depend on i
-    const int srow = w * 8 + (l >> 3);                           // + i*64
-    const int sc = ((l & 7) ^ (((w & 1) << 2) + (l >> 4))) * 8;  // swizzled SOURCE chunk (elements)
-    char* const swave = smem + w * 1024;
-
-    const int wr = w / WN, wc = w % WN, g = l >> 4, lr = l & 15;
-    // fragment addresses: row*128 + ((ks*4+g) ^ ((row>>1)&7))*16; (row>>1)&7 == (lr>>1)&7 for every tile of this lane
-    const int swz = (lr >> 1) & 7;
-    const int aoff0 = (wr * 64 + lr) * 128 + ((g ^ swz) << 4), aoff1 = aoff0 ^ 64;
-    const int boff0 = 2 * AH + (wc * 32 + lr) * 128 + ((g ^ swz) << 4), boff1 = boff0 ^ 64;
-
-    const bf16* wrow[2 * NB];
     int m0 = 0, n0 = 0;
     // persistent tile loop: round `base` handles tiles [base, base+G); inside a round block b takes the
     // XCD-grouped position, and consecutive tile indices walk 4 tile rows x all tile columns, so the 32
@@ -107,51 +57,19 @@ AL al, const bf16* __restrict__ W, long ldb, long strideA, long strideB,
         const int gm = min(4, ntm - mg * 4);
         m0 = (mg * 4 + rem % gm) * BM; n0 = (rem / gm) * BN;
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
+        for (int h = 0; h < 2; ++h) {                    // A slots and W rows half by half: all four (division-heavy) ConvLoaderS inits ahead of the W rows spilled two more VGPRs
 #pragma unroll
-            for (int i = 0; i < NA; ++i) {
-                const int r = i * 64 + srow;                     // LDS row of the half-tile -> (wave row r>>6, row r&63)
-                al.init(h * NA + i, m0 + (r >> 6) * WROWS + h * 64 + (r & 63));   // (MT1 < 4: rows 16 MT1 .. 63 of HA1 are staged but never read)
-            }
-#pragma unroll
-            for (int i = 0; i < NB; ++i) {
-                const int r = i * 64 + srow;
-                const int n = n0 + (r >> 5) * 64 + h * 32 + (r & 31);
-                wrow[h * NB + i] = Wb + (long)(n < N ? n : N - 1) * ldb;
-            }
+            for (int s = h * 2; s < h * 2 + 2; ++s) al.init(s, m0 + T.slot_wr(s) * WROWS + T.slot_row(s));   // (MT1 < 4: rows 16 MT1 .. 63 of HA1 are staged but never read)
+            T.set_W_half(h, Wb, ldb, n0, N);
         }
         return true;
     };
-    auto stage_A = [&](auto hc, int T) __attribute__((always_inline)) {
-        constexpr int h = decltype(hc)::value;
-        const int k0 = (T < nk ? T : nk - 1) * G2_BK;
-        char* d = swave + (T & 1) * BUF + h * AH;
-        al.set_ktile(k0);
-#pragma unroll
-        for (int i = 0; i < NA; ++i) glds16(al.ptr(h * NA + i, k0 + sc), d + i * 8192);
-    };
-    auto stage_B = [&](auto hc, int T) __attribute__((always_inline)) {
-        constexpr int h = decltype(hc)::value;
-        const int k0 = (T < nk ? T : nk - 1) * G2_BK;
-        char* d = swave + (T & 1) * BUF + 2 * AH + h * BH;
-#pragma unroll
-        for (int i = 0; i < NB; ++i) glds16(wrow[h * NB + i] + k0 + sc, d + i * 8192);
-    };
-    // tile 0 complete + the first two halves of tile 1, in stream order
-    constexpr std::integral_constant<int, 0> H0{}; constexpr std::integral_constant<int, 1> H1{};
-    auto prologue = [&]() __attribute__((always_inline)) { stage_A(H0, 0); stage_B(H0, 0); stage_B(H1, 0); stage_A(H1, 0); stage_A(H0, 1); stage_B(H0, 1); };
 
     f32x4 acc[NMT][4];
-    bf16x8 a[4][2], b0[2][2], b1[2][2];
 
-    // counted wait: the four half-tiles issued after the one needed next = 2 A + 2 W halves
-#define G2_WAIT()                                                                                           \
-    if constexpr (2 * NA + 2 * NB == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                   \
-    else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    // operands swapped (W fragment first): D rows = n, D cols = m, so a lane holds 4 CONSECUTIVE columns
-    // n = g*4 .. +3 of row m = lr -> one 16-byte store per MFMA tile in the epilogue
+    // MFMA section of the four-phase form (the two-phase one is tile256.h's)
 #define G2_MFMA_SECTION(MH, BF, NH)                                                                         \
-    g2_barrier();                                                                                           \
+    T.barrier();                                                                                            \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                      \
     __builtin_amdgcn_sched_barrier(0);                                                                      \
     __builtin_amdgcn_s_setprio(1);                                                                          \
@@ -162,128 +80,50 @@ AL al, const bf16* __restrict__ W, long ldb, long strideA, long strideB,
                     __builtin_amdgcn_mfma_f32_16x16x32_bf16(BF[nt][ks], a[mt][ks], acc[MH * 4 + mt][NH * 2 + nt], 0, 0, 0); \
     __builtin_amdgcn_s_setprio(0);                                                                          \
     __builtin_amdgcn_sched_barrier(0);                                                                      \
-    g2_barrier();
-
-    // PH == 2 (round 5): the SAME stream and LDS layout with TWO phases per K tile instead of four -- phase A = quadrants (0,0) (0,1) on the
-    // fragments of HB0, HA0, HB1 (32 MFMAs), phase B = quadrants (1,1) (1,0) on HA1 (8 MT1 MFMAs); each phase re-stages two half-tiles.  Half the
-    // barriers per MFMA: the four-phase form measured only -3.5 % when a quarter of the MFMAs of phases 3 / 4 was removed (224-row tiles), i.e. its
-    // phases are bound by their fixed part (two barriers, fragment reads, staging, counted wait), not by their 16 MFMAs.
-#define G2_MFMA_SECTION2(MH, BFA, NHA, BFB, NHB)                                                            \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      /* WAR (round 6): fragments in registers BEFORE the barrier, see the header */ \
-    g2_barrier();                                                                                           \
-    __builtin_amdgcn_sched_barrier(0);                                                                      \
-    __builtin_amdgcn_s_setprio(1);                                                                          \
-    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                        \
-        _Pragma("unroll") for (int mt = 0; mt < (MH ? MT1 : 4); ++mt)                                       \
-            _Pragma("unroll") for (int nt = 0; nt < 2; ++nt) {                                              \
-                acc[MH * 4 + mt][NHA * 2 + nt] =                                                            \
-                    __builtin_amdgcn_mfma_f32_16x16x32_bf16(BFA[nt][ks], a[mt][ks], acc[MH * 4 + mt][NHA * 2 + nt], 0, 0, 0); \
-                acc[MH * 4 + mt][NHB * 2 + nt] =                                                            \
-                    __builtin_amdgcn_mfma_f32_16x16x32_bf16(BFB[nt][ks], a[mt][ks], acc[MH * 4 + mt][NHB * 2 + nt], 0, 0, 0); \
-            }                                                                                               \
-    __builtin_amdgcn_s_setprio(0);                                                                          \
-    __builtin_amdgcn_sched_barrier(0);                                                                      \
-    g2_barrier();
+    T.barrier();
 
     bool have = setup(0);
-    if (have) prologue();
+    if (have) T.prologue();
     for (int base = 0; have; ) {
-#pragma unroll
-        for (int i = 0; i < NMT; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if constexpr (PH == 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");      // HB1(0) landed (younger: HA1(0) HA0(1) HB0(1))
-        else { G2_WAIT() }
-        g2_barrier();
-        if (wr >= WM / 2) g2_barrier();                   // second wave group runs one barrier behind
-
-        if constexpr (PH == 2) {
-        for (int kt = 0; kt < nk; ++kt) {
-            const char* buf = smem + (kt & 1) * BUF;
-            // ---- phase A: quadrants (0,0) (0,1): fragments of HB0, HA0, HB1; stage HB1(kt+1), HA1(kt+1)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                b0[nt][0] = *(const bf16x8*)(buf + boff0 + nt * 2048);
-                b0[nt][1] = *(const bf16x8*)(buf + boff1 + nt * 2048);
+        if constexpr (PH == 2) T.run(acc);
+        else {
+            bf16x8 a[4][2], b0[2][2], b1[2][2];
+            T.template open<4>(acc);
+            for (int kt = 0; kt < nk; ++kt) {
+                const char* buf = smem + (kt & 1) * T256_BUF;
+                // ---- phase 1: quadrant (0,0): fragments of HB0 and HA0; stage HB1(kt+1)
+                T.template read_B<0>(buf, b0);
+                T.template read_A<0, 4>(buf, a);
+                T.template stage_B<1>(kt + 1);
+                T.template wait_all_but<4>();
+                __builtin_amdgcn_sched_barrier(0);
+                G2_MFMA_SECTION(0, b0, 0)
+                // ---- phase 2: quadrant (0,1): fragments of HB1; stage HA1(kt+1)
+                T.template read_B<1>(buf, b1);
+                T.template stage_A<1>(kt + 1);
+                T.template wait_all_but<4>();
+                __builtin_amdgcn_sched_barrier(0);
+                G2_MFMA_SECTION(0, b1, 1)
+                // ---- phase 3: quadrant (1,1): fragments of HA1; stage HA0(kt+2)
+                T.template read_A<1, MT1>(buf, a);
+                T.template stage_A<0>(kt + 2);
+                __builtin_amdgcn_sched_barrier(0);
+                G2_MFMA_SECTION(1, b1, 1)
+                // ---- phase 4: quadrant (1,0): B0 still in registers; stage HB0(kt+2)
+                T.template stage_B<0>(kt + 2);
+                T.template wait_all_but<4>();
+                __builtin_amdgcn_sched_barrier(0);
+                G2_MFMA_SECTION(1, b0, 0)
             }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                a[mt][0] = *(const bf16x8*)(buf + aoff0 + mt * 2048);
-                a[mt][1] = *(const bf16x8*)(buf + aoff1 + mt * 2048);
-            }
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                b1[nt][0] = *(const bf16x8*)(buf + BH + boff0 + nt * 2048);
-                b1[nt][1] = *(const bf16x8*)(buf + BH + boff1 + nt * 2048);
-            }
-            stage_B(H1, kt + 1);
-            stage_A(H1, kt + 1);
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // HA1(kt) landed (younger: HA0 HB0 HB1 HA1 of kt+1)
-            __builtin_amdgcn_sched_barrier(0);
-            G2_MFMA_SECTION2(0, b0, 0, b1, 1)
-            // ---- phase B: quadrants (1,1) (1,0): fragments of HA1; stage HA0(kt+2), HB0(kt+2)
-#pragma unroll
-            for (int mt = 0; mt < MT1; ++mt) {
-                a[mt][0] = *(const bf16x8*)(buf + AH + aoff0 + mt * 2048);
-                a[mt][1] = *(const bf16x8*)(buf + AH + aoff1 + mt * 2048);
-            }
-            stage_A(H0, kt + 2);
-            stage_B(H0, kt + 2);
-            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");      // HB1(kt+1) (and the older HA0 / HB0(kt+1)) landed (younger: HA1(kt+1) HA0 HB0(kt+2))
-            __builtin_amdgcn_sched_barrier(0);
-            G2_MFMA_SECTION2(1, b1, 1, b0, 0)
+            T.close();
         }
-        } else
-        for (int kt = 0; kt < nk; ++kt) {
-            const char* buf = smem + (kt & 1) * BUF;
-            // ---- phase 1: quadrant (0,0): fragments of HB0 and HA0; stage HB1(kt+1)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                b0[nt][0] = *(const bf16x8*)(buf + boff0 + nt * 2048);
-                b0[nt][1] = *(const bf16x8*)(buf + boff1 + nt * 2048);
-            }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                a[mt][0] = *(const bf16x8*)(buf + aoff0 + mt * 2048);
-                a[mt][1] = *(const bf16x8*)(buf + aoff1 + mt * 2048);
-            }
-            stage_B(H1, kt + 1);
-            G2_WAIT()
-            __builtin_amdgcn_sched_barrier(0);
-            G2_MFMA_SECTION(0, b0, 0)
-            // ---- phase 2: quadrant (0,1): fragments of HB1; stage HA1(kt+1)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                b1[nt][0] = *(const bf16x8*)(buf + BH + boff0 + nt * 2048);
-                b1[nt][1] = *(const bf16x8*)(buf + BH + boff1 + nt * 2048);
-            }
-            stage_A(H1, kt + 1);
-            G2_WAIT()
-            __builtin_amdgcn_sched_barrier(0);
-            G2_MFMA_SECTION(0, b1, 1)
-            // ---- phase 3: quadrant (1,1): fragments of HA1; stage HA0(kt+2)
-#pragma unroll
-            for (int mt = 0; mt < MT1; ++mt) {
-                a[mt][0] = *(const bf16x8*)(buf + AH + aoff0 + mt * 2048);
-                a[mt][1] = *(const bf16x8*)(buf + AH + aoff1 + mt * 2048);
-            }
-            stage_A(H0, kt + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            G2_MFMA_SECTION(1, b1, 1)
-            // ---- phase 4: quadrant (1,0): B0 still in registers; stage HB0(kt+2)
-            stage_B(H0, kt + 2);
-            G2_WAIT()
-            __builtin_amdgcn_sched_barrier(0);
-            G2_MFMA_SECTION(1, b0, 0)
-        }
-        if (wr < WM / 2) g2_barrier();
         // every wave is past its last ds_read: the next tile's first loads go out before this tile's
         // stores (same vmcnt counter, but loads return in order among themselves and the clamped tail
         // stages of this tile were issued earlier by the same wave to the same LDS bytes)
         const int em0 = m0 + wr * WROWS + lr, en0 = n0 + wc * 64 + g * 4, ecol0 = n0 + wc * 64;   // setup() below moves m0 / n0 on
         base += G;
         have = base < NT && setup(base);
-        if (have) prologue();
+        if (have) T.prologue();
         if constexpr (ROPE) {
             // Prefill QKV projection: RoPE(q), RoPE(k) and the KV-cache write from the accumulators.  W rows of the q / k heads
             // are interleaved [8 | 8] per n-tile (launch_interleave_qk): lanes g = 0,1 hold rotary columns j = 8t + 4g .. +3, lanes g = 2,3
@@ -439,21 +279,19 @@ AL al, const bf16* __restrict__ W, long ldb, long strideA, long strideB,
         }
     }
 #undef G2_MFMA_SECTION
-#undef G2_MFMA_SECTION2
-#undef G2_WAIT
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // clamped tail stages must not outlive the block's LDS
+    T.drain();
 }
 
 
-template <class AL, int WM, int WN, bool ROPE = false, int MT1 = 4, int PH = 4, bool GN = false>
+template <class AL, bool ROPE = false, int MT1 = 4, int PH = 4, bool GN = false>
 static void launch256(hipStream_t s, AL al, const bf16* W, long ldb, long strideA, long strideB, long strideA2, long strideB2,
                       const Epi<bf16>& ep, int M, int N, int K, int batch, int batch2) {
-    constexpr int BM = WM * (64 + 16 * MT1), BN = WN * 64, LDS = 2 * (2 * WM * 64 * 128 + 2 * WN * 32 * 128);
+    constexpr int BM = 2 * (64 + 16 * MT1), BN = 256, LDS = T256_STAGING;
     const int ntm = (M + BM - 1) / BM, ntn = (N + BN - 1) / BN;
     const int ncu = pg_cu_count();
     const int per_batch = ncu / (batch * batch2) > 8 ? ncu / (batch * batch2) : 8;   // blocks per (batch) slice: one per CU overall
     dim3 grid(ntm * ntn < per_batch ? ntm * ntn : per_batch, batch, batch2), block(512);
-    auto kfn = gemm256_kernel<AL, Epi<bf16>, WM, WN, ROPE, MT1, PH, GN>;
+    auto kfn = gemm256_kernel<AL, Epi<bf16>, ROPE, MT1, PH, GN>;
     (void)PG_DYN_LDS(kfn, LDS);
     hipLaunchKernelGGL(kfn, grid, block, LDS, s, al, W, ldb, strideA, strideB, strideA2, strideB2, ep, M, N, K, ntm, ntn);
 }
@@ -481,10 +319,7 @@ static int pick_tile_height(int M, int N, int batches) {
 // Takes the shapes the big tiles fill well; everything else stays on the 128^2 kernel.
 bool gemm256_try(hipStream_t s, const GemmA& a, const bf16* W, long ldb, long strideB, const GemmEpi& e, int M, int N, int K,
                  int batch, int batch2, long strideB2) {
-    if (!pg_tune->gemm256 || K % G2_BK || K < 2 * G2_BK) return false;
-    // (a 4x2-wave 512x128 instantiation for the Cout = 128 convolutions was measured: 470-560 TFLOP/s against
-    // 640-690 for the 128x128 kernel -- K = 9*Cin is only 18-36 K tiles, so the fill / drain of one persistent
-    // block per CU and the 8-slot im2col address state outweigh the deeper pipeline; not instantiated)
+    if (!pg_tune->gemm256 || K % T256_BK || K < 2 * T256_BK) return false;
     const int BM = 256, BN = 256;
     const int ntm = (M + BM - 1) / BM, ntn = (N + BN - 1) / BN;
     // padding waste of the last tile row / column, and enough tiles to fill the chip
@@ -502,9 +337,9 @@ bool gemm256_try(hipStream_t s, const GemmA& a, const bf16* W, long ldb, long st
     if (a.kind == 0) {
         PlainLoaderB<bf16> al; al.A = (const bf16*)a.ptr; al.lda = a.lda; al.M = M;
         const int mt1 = want_gn ? 4 : pick_tile_height(M, N, batch * batch2);
-#define G2_LAUNCH(ROPE_, MT1_, PH_) launch256<PlainLoaderB<bf16>, 2, 4, ROPE_, MT1_, PH_>(s, al, W, ldb, a.strideA, strideB, a.strideA2, strideB2, ep, M, N, K, batch, batch2)
+#define G2_LAUNCH(ROPE_, MT1_, PH_) launch256<PlainLoaderB<bf16>, ROPE_, MT1_, PH_>(s, al, W, ldb, a.strideA, strideB, a.strideA2, strideB2, ep, M, N, K, batch, batch2)
         if (want_gn) {        // 1x1 convolution whose output feeds a GroupNorm (AttnBlock.proj_out): the GN instantiation, 256-row tiles, two phases
-            launch256<PlainLoaderB<bf16>, 2, 4, false, 4, 2, true>(s, al, W, ldb, a.strideA, strideB, a.strideA2, strideB2, ep, M, N, K, batch, batch2);
+            launch256<PlainLoaderB<bf16>, false, 4, 2, true>(s, al, W, ldb, a.strideA, strideB, a.strideA2, strideB2, ep, M, N, K, batch, batch2);
             return true;
         }
         // two phases per K tile by default (round 5: +2-3 % on every prefill shape, bit-identical); gemm256 bit 3 (value 8) selects the four-phase schedule for A/B
@@ -523,8 +358,8 @@ bool gemm256_try(hipStream_t s, const GemmA& a, const bf16* W, long ldb, long st
     const long in_elems = ((long)M / ((long)Ho * Wo)) * a.Hi * a.Wi * a.Cin;
     if (in_elems >= (1L << 31)) return false;             // the slim loader keeps 32-bit element offsets
     ConvLoaderS<4> al; al.setup(a, M);
-    if (want_gn) launch256<ConvLoaderS<4>, 2, 4, false, 4, 2, true>(s, al, W, ldb, a.strideA, strideB, a.strideA2, strideB2, ep, M, N, K, batch, batch2);      // GroupNorm partials from the epilogue (two-phase form only)
-    else if (pg_tune->gemm256 & 8) launch256<ConvLoaderS<4>, 2, 4, false, 4, 4>(s, al, W, ldb, a.strideA, strideB, a.strideA2, strideB2, ep, M, N, K, batch, batch2);
-    else launch256<ConvLoaderS<4>, 2, 4, false, 4, 2>(s, al, W, ldb, a.strideA, strideB, a.strideA2, strideB2, ep, M, N, K, batch, batch2);
+    if (want_gn) launch256<ConvLoaderS<4>, false, 4, 2, true>(s, al, W, ldb, a.strideA, strideB, a.strideA2, strideB2, ep, M, N, K, batch, batch2);      // GroupNorm partials from the epilogue (two-phase form only)
+    else if (pg_tune->gemm256 & 8) launch256<ConvLoaderS<4>, false, 4, 4>(s, al, W, ldb, a.strideA, strideB, a.strideA2, strideB2, ep, M, N, K, batch, batch2);
+    else launch256<ConvLoaderS<4>, false, 4, 2>(s, al, W, ldb, a.strideA, strideB, a.strideA2, strideB2, ep, M, N, K, batch, batch2);
     return true;
 }

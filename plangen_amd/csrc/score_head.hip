@@ -8,9 +8,8 @@
 // NaN-as--inf rule is not reproduced).
 //
 // Geometry (fixed; G is a function of (n, V, K) alone -- head_logprob_geom, mirrored by plangen_amd.engine.head_logprob_geometry):
-// * SH_BM = 256 scored rows x SH_BN = 256 vocabulary columns per tile, K step SH_BK = 64 (K % 64 == 0), eight waves, each owning 128 x 64 of
-//   the tile as 8 x 4 MFMA tiles (mfma_f32_16x16x32_bf16): the staging stream, the swizzled LDS layout, the two-phase schedule and its counted
-//   waits are those of gemm256.hip's 256x256 two-phase form (the invariants are written down there); the A rows are gathered through row_idx.
+// * SH_BM = 256 scored rows x SH_BN = 256 vocabulary columns per tile, K step 64 (K % 64 == 0): one tile of tile256.h's two-phase pipeline
+//   (eight waves, each owning 128 x 64 of the tile as 8 x 4 MFMA tiles); the A rows are gathered through row_idx.
 // * A block owns ONE row tile and a contiguous group of `cpt` column tiles (G = ceil(ntn / cpt) groups) and walks them with the K loop per
 //   tile; the next tile's first loads go out before the current tile's fold, as gemm256 does before its stores.
 // * Fold after each column tile: a lane holds, for each of its 8 rows, 16 columns of the tile (4 n-tiles x 4).  It keeps a running (m, s)
@@ -46,187 +45,40 @@ __global__ __launch_bounds__(512) void head_logprob_kernel(const bf16* __restric
                                                            const int32_t* __restrict__ target, int n, int V, int K, int ntm, int ntn, int cpt, int G,
                                                            float temperature, float* __restrict__ part, float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, l = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nk = K / SH_BK;
-
-    // block -> (row tile, group): an XCD's share of the grid is 4 row tiles x all groups, so its L2 holds 4 A panels while the W tiles stream
-    const int t = xcd_remap(blockIdx.x, gridDim.x);
-    const int per = 4 * G, mg = t / per, rem = t - mg * per, gm = min(4, ntm - mg * 4);
-    const int m0 = (mg * 4 + rem % gm) * SH_BM, grp = rem / gm;
-    const int c0 = grp * cpt, c1 = min(ntn, c0 + cpt);
-
-    const int srow = w * 8 + (l >> 3);                           // + i*64
-    const int sc = ((l & 7) ^ (((w & 1) << 2) + (l >> 4))) * 8;  // swizzled SOURCE chunk (elements)
-    char* const swave = smem + w * 1024;
-    const int wr = w >> 2, wc = w & 3, g = l >> 4, lr = l & 15;
-    const int swz = (lr >> 1) & 7;
-    const int aoff0 = (wr * 64 + lr) * 128 + ((g ^ swz) << 4), aoff1 = aoff0 ^ 64;
-    const int boff0 = 2 * SH_AH + (wc * 32 + lr) * 128 + ((g ^ swz) << 4), boff1 = boff0 ^ 64;
-
-    const bf16* arow[4];
-    const bf16* wrow[4];
+    const HeadBlock b = sh_block(ntm, ntn, cpt, G);
+    const int m0 = b.tile * SH_BM;
+    GatherLoader al;
+    Tile256<GatherLoader> T(al, smem, K);
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int r = i * 64 + srow;                         // LDS row of the half-tile -> (wave row r>>6, row r&63)
-            const int m = m0 + (r >> 6) * 128 + h * 64 + (r & 63), mc = m < n ? m : n - 1;
-            arow[h * 2 + i] = X + (long)(row_idx ? row_idx[mc] : mc) * K;
-        }
-    int n0 = 0;
-    auto setup = [&](int ct) __attribute__((always_inline)) {
-        n0 = ct * SH_BN;
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int r = i * 64 + srow;
-                const int v = n0 + (r >> 5) * 64 + h * 32 + (r & 31);
-                wrow[h * 2 + i] = W + (long)(v < V ? v : V - 1) * K;
-            }
-    };
-    auto stage_A = [&](int h, int T) __attribute__((always_inline)) {
-        const int k0 = (T < nk ? T : nk - 1) * SH_BK;
-        char* d = swave + (T & 1) * SH_BUF + h * SH_AH;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) glds16(arow[h * 2 + i] + k0 + sc, d + i * 8192);
-    };
-    auto stage_B = [&](int h, int T) __attribute__((always_inline)) {
-        const int k0 = (T < nk ? T : nk - 1) * SH_BK;
-        char* d = swave + (T & 1) * SH_BUF + 2 * SH_AH + h * SH_BH;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) glds16(wrow[h * 2 + i] + k0 + sc, d + i * 8192);
-    };
-    auto prologue = [&]() __attribute__((always_inline)) { stage_A(0, 0); stage_B(0, 0); stage_B(1, 0); stage_A(1, 0); stage_A(0, 1); stage_B(0, 1); };
+    for (int s = 0; s < 4; ++s) {
+        const int m = m0 + T.slot_wr(s) * 128 + T.slot_row(s), mc = m < n ? m : n - 1;
+        al.init(s, X + (long)(row_idx ? row_idx[mc] : mc) * K);
+    }
 
     f32x4 acc[8][4];
-    bf16x8 a[4][2], b0[2][2], b1[2][2];
     float mrun[8], srun[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) { mrun[i] = -INFINITY; srun[i] = 0.f; }
     const float invT = temperature > 0.f ? 1.f / temperature : 1.f;
     const bool scaled = temperature > 0.f;
+    const int row0 = m0 + T.wr * 128 + T.lr;                  // the lane's rows: row0 + mt*16
 
-#define SH_MFMA_SECTION(MH, BFA, NHA, BFB, NHB)                                                            \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      /* WAR: fragments in registers BEFORE the barrier (gemm256.hip) */ \
-    sh_barrier();                                                                                           \
-    __builtin_amdgcn_sched_barrier(0);                                                                      \
-    __builtin_amdgcn_s_setprio(1);                                                                          \
-    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                        \
-        _Pragma("unroll") for (int mt = 0; mt < 4; ++mt)                                                    \
-            _Pragma("unroll") for (int nt = 0; nt < 2; ++nt) {                                              \
-                acc[MH * 4 + mt][NHA * 2 + nt] =                                                            \
-                    __builtin_amdgcn_mfma_f32_16x16x32_bf16(BFA[nt][ks], a[mt][ks], acc[MH * 4 + mt][NHA * 2 + nt], 0, 0, 0); \
-                acc[MH * 4 + mt][NHB * 2 + nt] =                                                            \
-                    __builtin_amdgcn_mfma_f32_16x16x32_bf16(BFB[nt][ks], a[mt][ks], acc[MH * 4 + mt][NHB * 2 + nt], 0, 0, 0); \
-            }                                                                                               \
-    __builtin_amdgcn_s_setprio(0);                                                                          \
-    __builtin_amdgcn_sched_barrier(0);                                                                      \
-    sh_barrier();
-
-    setup(c0);
-    prologue();
-    for (int ct = c0; ct < c1; ++ct) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");      // HB1(0) landed (younger: HA1(0) HA0(1) HB0(1))
-        sh_barrier();
-        if (wr >= 1) sh_barrier();                            // second wave group runs one barrier behind
-
-        for (int kt = 0; kt < nk; ++kt) {
-            const char* buf = smem + (kt & 1) * SH_BUF;
-            // ---- phase A: quadrants (0,0) (0,1): fragments of HB0, HA0, HB1; stage HB1(kt+1), HA1(kt+1)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                b0[nt][0] = *(const bf16x8*)(buf + boff0 + nt * 2048);
-                b0[nt][1] = *(const bf16x8*)(buf + boff1 + nt * 2048);
-            }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                a[mt][0] = *(const bf16x8*)(buf + aoff0 + mt * 2048);
-                a[mt][1] = *(const bf16x8*)(buf + aoff1 + mt * 2048);
-            }
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                b1[nt][0] = *(const bf16x8*)(buf + SH_BH + boff0 + nt * 2048);
-                b1[nt][1] = *(const bf16x8*)(buf + SH_BH + boff1 + nt * 2048);
-            }
-            stage_B(1, kt + 1);
-            stage_A(1, kt + 1);
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // HA1(kt) landed (younger: HA0 HB0 HB1 HA1 of kt+1)
-            __builtin_amdgcn_sched_barrier(0);
-            SH_MFMA_SECTION(0, b0, 0, b1, 1)
-            // ---- phase B: quadrants (1,1) (1,0): fragments of HA1; stage HA0(kt+2), HB0(kt+2)
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                a[mt][0] = *(const bf16x8*)(buf + SH_AH + aoff0 + mt * 2048);
-                a[mt][1] = *(const bf16x8*)(buf + SH_AH + aoff1 + mt * 2048);
-            }
-            stage_A(0, kt + 2);
-            stage_B(0, kt + 2);
-            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");      // HB1(kt+1) (and the older HA0 / HB0(kt+1)) landed
-            __builtin_amdgcn_sched_barrier(0);
-            SH_MFMA_SECTION(1, b1, 1, b0, 0)
-        }
-        if (wr < 1) sh_barrier();
+    T.set_W(W, K, b.c0 * SH_BN, V);
+    T.prologue();
+    for (int ct = b.c0; ct < b.c1; ++ct) {
+        T.run(acc);
         // every wave is past its last ds_read: the next column tile's first loads go out before this tile's fold
-        const int ecol = n0 + wc * 64 + g * 4;                // the lane's first column; n-tile nt, element j -> ecol + nt*16 + j
-        if (ct + 1 < c1) { setup(ct + 1); prologue(); }
-        const int lim = V - ecol;                             // columns nt*16 + j >= lim are past the vocabulary
+        const int ecol = ct * SH_BN + T.wc * 64 + T.g * 4;    // the lane's first column; n-tile nt, element j -> ecol + nt*16 + j
+        if (ct + 1 < b.c1) { T.set_W(W, K, (ct + 1) * SH_BN, V); T.prologue(); }
         int tcol[8];
 #pragma unroll
-        for (int mt = 0; mt < 8; ++mt) {
-            const int m = m0 + wr * 128 + mt * 16 + lr;
-            const int tg = target[m < n ? m : n - 1];
-            tcol[mt] = (m < n && tg >= 0 && tg < V) ? tg - ecol : -1;
-        }
+        for (int mt = 0; mt < 8; ++mt) tcol[mt] = sh_target_col(target, row0 + mt * 16, n, V, ecol);
 #pragma unroll
-        for (int mt = 0; mt < 8; ++mt) {
-            float xs[16];
-            float mx = -INFINITY, xt = 0.f;
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float y = acc[mt][nt][j];
-                    float x = scaled ? __fmul_rn(y, invT) : y;
-                    if (nt * 16 + j >= lim) x = -INFINITY;
-                    if (nt * 16 + j == tcol[mt]) xt = x;
-                    xs[nt * 4 + j] = x;
-                    mx = fmaxf(mx, x);
-                }
-            const float mn = fmaxf(mrun[mt], mx), mref = mn == -INFINITY ? 0.f : mn;
-            float sum = 0.f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) sum += expf(xs[i] - mref);
-            srun[mt] = srun[mt] * expf(mrun[mt] - mref) + sum;
-            mrun[mt] = mn;
-            const int tc = tcol[mt];
-            if (tc >= 0 && tc < 64 && (tc & 15) < 4) out[m0 + wr * 128 + mt * 16 + lr] = xt;      // the one lane that holds column t of this row
-        }
+        for (int mt = 0; mt < 8; ++mt)
+            sh_fold16([&](int nt, int j) { return acc[mt][nt][j]; }, V - ecol, tcol[mt], scaled, invT, mrun[mt], srun[mt], out, row0 + mt * 16);
     }
-#undef SH_MFMA_SECTION
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // clamped tail stages must not outlive the block's LDS
-    // ---- merge: the row's four lanes (g = 0..3), then the four column waves in ascending order
-    float2* red = (float2*)(smem + 2 * SH_BUF);           // [wc][SH_BM]
-#pragma unroll
-    for (int mt = 0; mt < 8; ++mt) {
-        float m = mrun[mt], s = srun[mt];
-        sh_merge(m, s, __shfl_xor(m, 16, 64), __shfl_xor(s, 16, 64));
-        sh_merge(m, s, __shfl_xor(m, 32, 64), __shfl_xor(s, 32, 64));
-        if (g == 0) red[wc * SH_BM + wr * 128 + mt * 16 + lr] = make_float2(m, s);
-    }
-    __syncthreads();
-    if (tid < SH_BM && m0 + tid < n) {
-        float2 p = red[tid];
-        float m = p.x, s = p.y;
-#pragma unroll
-        for (int c = 1; c < 4; ++c) { p = red[c * SH_BM + tid]; sh_merge(m, s, p.x, p.y); }
-        *(float2*)(part + ((long)grp * n + m0 + tid) * 2) = make_float2(m, s);
-    }
+    T.drain();
+    sh_block_merge<8>(T, (float2*)(smem + T256_STAGING), mrun, srun, m0, n, b.grp, part);
 }
 
 // out[i] holds x_t (written by the one block that met column t; untouched when t is outside [0, V)): merge the G groups' (m, s) in ascending
@@ -249,9 +101,8 @@ void launch_head_combine(hipStream_t s, const float* part, const int32_t* target
 
 bool launch_head_logprob(hipStream_t s, const bf16* X, const bf16* W, const int32_t* row_idx, const int32_t* target, long n, int V, int K,
                          float temperature, float* part, float* out) {
-    if (n < 1 || V < 1 || K < SH_BK || K % SH_BK || n > (1L << 30)) return false;
-    const HeadGeom g = head_logprob_geom(n, V, K);
-    if ((long)g.ntm * g.G > 0x7fffffffL) return false;
+    HeadGeom g;
+    if (!sh_launch_geom(n, V, K, g)) return false;
     auto kfn = head_logprob_kernel;
     if (!PG_DYN_LDS(kfn, SH_LDS)) return false;
     hipLaunchKernelGGL(kfn, dim3(g.ntm * g.G), dim3(512), SH_LDS, s, X, W, row_idx, target, (int)n, V, K, g.ntm, g.ntn, g.cpt, g.G, temperature, part, out);

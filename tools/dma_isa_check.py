@@ -225,15 +225,15 @@ def gemm256_ph2_need_factory():
 SPECS = [
     ("attn_prefill", r"attn_prefill_flash2_kernel", dict(kind="fifo", g=4, need=flash2_need, tile_cls=lambda n: n & 1, slot_reuse=lambda c: 4, strict=True,
                                                          why="two barriers per tile: A(t) retires V(t), B(t) retires K(t+1)")),
-    # PH = 2 is the second-to-last template argument (GN, a bool, follows it): ...ELi<PH>ELb<GN>EEv
+    # PH = 2 is the second-to-last template argument (GN, a bool, follows it): ...ELi<PH>ELb<GN>EEv.  The two-phase invariants: plangen_amd/csrc/tile256.h
     ("gemm256", r"gemm256_kernel.*ELi2ELb[01]EEv", dict(kind="fifo", g=2, need="ph2", tile_cls=lambda n: n & 3, slot_reuse=lambda c: 8, strict=True, stagger=True,
                                                  why="two-phase form: half-tiles retired by vmcnt(8) / vmcnt(6) one phase before they are read; a slot is re-staged one barrier "
                                                      "after its last read with the read drained (lgkmcnt(0)) in front of that barrier (wave groups one barrier apart)")),
     ("gemm256", r"gemm256_kernel", dict(kind="fifo", g=2, need=None, tile_cls=lambda n: n & 3, slot_reuse=lambda c: 8, strict=True, stagger=True,
                                         why="four-phase form: half-tiles retired by vmcnt(8) in the phase before they are read; a slot is re-staged >= 2 phases after its last read")),
     ("score_head", r"head_logprob_kernel", dict(kind="fifo", g=2, need="ph2", tile_cls=lambda n: n & 3, slot_reuse=lambda c: 8, strict=True, stagger=True,
-                                                why="the fused scoring head walks its column tiles on gemm256's two-phase stream (same half-tile order, counted waits and drained "
-                                                    "fragment reads); its fold and merge touch LDS only past the staging buffers")),
+                                                why="the fused scoring head walks its column tiles on tile256.h's two-phase stream (the same Tile256::run() as gemm256: invariants in that header); "
+                                                    "its fold and merge touch LDS only past the staging buffers")),
     ("score_cfg_head", r"cfg_head_logprob_kernel", dict(kind="fifo", g=2, need="ph2", tile_cls=lambda n: n & 3, slot_reuse=lambda c: 8, strict=True, stagger=True,
                                                         why="head_logprob_kernel's stream, schedule and waits unchanged (the A rows are gathered through two index lists); "
                                                             "the CFG mix and the fold run in registers, the merge touches LDS only past the staging buffers")),
