@@ -5,6 +5,7 @@
 // two-level batched GEMM of SigLIP's scores and P . V: tests/test_gpu_vision_ops.py) and of the decode GEMM dispatch itself -- launch_gemm_skinny /
 // launch_gemm_skinny_swiglu on the tiled copy or on row-major weights, with the caller's split count and stream_gemm mask: tests/test_gpu_skinny_ops.py --
 // and of the samplers' draw -- launch_cfg_sample / launch_cfg_sample_filtered and launch_text_argmax / launch_text_sample on the caller's slabs: tests/test_gpu_draws.py --
+// and of the weight converters pg_engine::load_tensor launches and the row movers of every prefill / step / score call (tests/test_gpu_load_ops.py) --
 // for the operator tests.  Each one points the calling thread's pg_tune at a local PgTune (no diagnostics hooks, one kernel-form selector set), calls the PRODUCTION launcher and restores
 // pg_tune.  Shapes the kernels do not support are refused with PG_ERR_ARG and never launched.  Head dimension: 128 for the LLM kernels (implied
 // by the [.., nh * 128] layouts), 64 for SigLIP (C / NH).  Row lengths, slots and token maps live in device memory; they are copied back and
@@ -849,6 +850,113 @@ int pg_diag_op_text_draw(int mode, const float* partial, int S, long slab, int V
     if (mode == 1) launch_text_sample(s, a, B, (float*)pv.p, (int*)pi.p);
     else launch_text_argmax(s, a, B, (float*)pv.p, (int*)pi.p);
     return finish(s);                                                                                // before the scratch goes away
+}
+
+// ------------------------------------------------------------------------------------------------ weight converters and row movers (tests/test_gpu_load_ops.py)
+// Every entry point below synchronises the stream before it returns.
+
+// The converters of pg_engine::load_tensor: src fp32 or bf16 (src_bf16) -> dst fp32 or bf16 (dst_bf16).  kind 0: launch_convert<T> on n elements (T = float is
+// launch_to_f32 too); *kernel_out = 1 when launch_convert's own condition sends the call to convert_f32_bf16_vec_kernel (fp32 -> bf16, n >= 65536, n % 8 == 0, both
+// pointers 16-byte aligned), 0 = convert_kernel<T>.  kind 1: launch_convert_conv<T>, src [a = Cout][b = Cin][c = kk] -> dst [Cout][kk][Cin].  kind 2:
+// launch_convert_interleave16<T>, src [a = I][b = H] -> rows (r / 8) * 16 + which * 8 + r % 8 of dst [2 I][H]; I % 8 != 0 is refused (the last block's rows would
+// fall behind row 2 I - 1).  Pointers must be aligned to their element.
+int pg_diag_op_convert(int kind, int src_bf16, int dst_bf16, const void* src, void* dst, long n, int a, int b, int c, int which, int* kernel_out,
+                       pg_stream stream) {
+    if (!src || !dst || kind < 0 || kind > 2 || (src_bf16 != 0 && src_bf16 != 1) || (dst_bf16 != 0 && dst_bf16 != 1)) return PG_ERR_ARG;
+    if (((uintptr_t)src & (src_bf16 ? 1 : 3)) || ((uintptr_t)dst & (dst_bf16 ? 1 : 3))) return PG_ERR_ARG;
+    if (kind == 0) {
+        if (n < 1 || n >= (1L << 40) || !kernel_out) return PG_ERR_ARG;
+    } else {
+        if (a < 1 || b < 1 || (long)a * b >= (1L << 40)) return PG_ERR_ARG;
+        if (kind == 1 && (c < 1 || (long)a * b * c >= (1L << 40))) return PG_ERR_ARG;
+        if (kind == 2 && ((a & 7) || (which != 0 && which != 1))) return PG_ERR_ARG;
+    }
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    if (kind == 0) {
+        *kernel_out = dst_bf16 && !src_bf16 && n % 8 == 0 && n >= 65536 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;      // launch_convert's condition, restated
+        if (dst_bf16) launch_convert<bf16>(s, src, src_bf16, (bf16*)dst, n);
+        else if (which) launch_to_f32(s, src, src_bf16, (float*)dst, n);                                      // which = 1: through launch_to_f32 (the K_F32 slots)
+        else launch_convert<float>(s, src, src_bf16, (float*)dst, n);
+    } else if (kind == 1) {
+        if (dst_bf16) launch_convert_conv<bf16>(s, src, src_bf16, (bf16*)dst, a, b, c);
+        else launch_convert_conv<float>(s, src, src_bf16, (float*)dst, a, b, c);
+    } else {
+        if (dst_bf16) launch_convert_interleave16<bf16>(s, src, src_bf16, (bf16*)dst, a, b, which);
+        else launch_convert_interleave16<float>(s, src, src_bf16, (float*)dst, a, b, which);
+    }
+    return finish(s);
+}
+}  // extern "C"
+namespace {
+// idx [n] device (or null: the identity, n <= rows) inside [0, rows); distinct: no value twice (a scatter's rows must not race)
+int screen_rows(const int32_t* idx, int n, long rows, bool distinct) {
+    if (!idx) return n <= rows ? PG_OK : PG_ERR_ARG;
+    std::vector<int32_t> h;
+    if (!to_host(h, idx, n)) return PG_ERR_HIP;
+    std::vector<char> seen(distinct ? (size_t)rows : 0, 0);
+    for (int i = 0; i < n; ++i) {
+        if (h[i] < 0 || h[i] >= rows) return PG_ERR_ARG;
+        if (distinct) { if (seen[h[i]]) return PG_ERR_ARG; seen[h[i]] = 1; }
+    }
+    return PG_OK;
+}
+}  // namespace
+extern "C" {
+
+// The row movers.  n rows are moved; width = H elements (ops 0, 2 - 5), row_bytes (op 1) or L (op 6).  src has src_rows rows and dst dst_rows; an index vector
+// ([n] int32 device, or null = the identity) is copied back and screened against them before anything is launched, a scatter's for duplicates too.
+//   0  launch_embed_gather: src = table fp32 [src_rows = vocab][H], ids [n_ids] (ANY value: the kernel clamps to [0, vocab - 1]), src_idx [n] into ids or null
+//      (then n <= n_ids), dst fp32 [dst_rows >= n][H].  The kernel moves 16-byte vectors: H % 4 != 0 or a table / dst that is not 16-byte aligned is refused.
+//   1  launch_copy_rows: src [src_rows][row_bytes] gathered by src_idx, dst [dst_rows][row_bytes] scattered by dst_idx.  The kernel copies 32-bit words and counts
+//      them in an int: row_bytes % 4 != 0, row_bytes / 4 > INT_MAX or a pointer that is not 4-byte aligned is refused.
+//   2  launch_rows_to_f32: src fp32 / bf16 (src_bf16) [src_rows][H] gathered by src_idx -> dst fp32 [dst_rows >= n][H].
+//   3  launch_f32_to_rows, 4 launch_t_to_rows<float>, 5 launch_t_to_rows<bf16>: src fp32 (5: bf16) [src_rows >= n][H] -> dst fp32 / bf16 (dst_bf16) [dst_rows][H]
+//      scattered by dst_idx.
+//   6  launch_rows_differ: ids [src_rows][L]; dst = flag int32 [1] |= 1 when a row first, first + stride, ... (n rows) differs from row ref in columns [from, L).
+int pg_diag_op_rows(int op, const void* src, void* dst, const int32_t* ids, int n_ids, const int32_t* src_idx, const int32_t* dst_idx, int n, long width,
+                    long src_rows, long dst_rows, int src_bf16, int dst_bf16, int first, int stride, int ref, int from, pg_stream stream) {
+    if (op < 0 || op > 6 || !dst || (op != 6 && !src) || n < 1 || width < 1 || src_rows < 1 || dst_rows < 1) return PG_ERR_ARG;
+    if ((src_bf16 != 0 && src_bf16 != 1) || (dst_bf16 != 0 && dst_bf16 != 1)) return PG_ERR_ARG;
+    if (op != 1 && width > 0x7fffffffL) return PG_ERR_ARG;
+    const int H = (int)(op == 1 ? 0 : width);
+    int rc = PG_OK;
+    switch (op) {
+        case 0:
+            if (!ids || n_ids < 1 || dst_idx || (H & 3) || (((uintptr_t)src | (uintptr_t)dst) & 15) || n > dst_rows || src_rows > 0x7fffffffL) return PG_ERR_ARG;
+            rc = screen_rows(src_idx, n, n_ids, false);
+            break;
+        case 1:
+            if ((width & 3) || width / 4 > 0x7fffffffL || (((uintptr_t)src | (uintptr_t)dst) & 3)) return PG_ERR_ARG;
+            rc = screen_rows(src_idx, n, src_rows, false);
+            if (rc == PG_OK) rc = screen_rows(dst_idx, n, dst_rows, true);
+            break;
+        case 2:
+            if (dst_idx || n > dst_rows || ((uintptr_t)src & (src_bf16 ? 1 : 3)) || ((uintptr_t)dst & 3)) return PG_ERR_ARG;
+            rc = screen_rows(src_idx, n, src_rows, false);
+            break;
+        case 3: case 4: case 5:
+            if (src_idx || n > src_rows || ((uintptr_t)src & (op == 5 ? 1 : 3)) || ((uintptr_t)dst & (dst_bf16 ? 1 : 3))) return PG_ERR_ARG;
+            rc = screen_rows(dst_idx, n, dst_rows, true);
+            break;
+        default:
+            if (!ids || src_idx || dst_idx || first < 0 || stride < 1 || ref < 0 || ref >= src_rows || from < 0 || from > width) return PG_ERR_ARG;
+            if ((long)first + (long)(n - 1) * stride >= src_rows || (((uintptr_t)ids | (uintptr_t)dst) & 3)) return PG_ERR_ARG;
+            break;
+    }
+    if (rc != PG_OK) return rc;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    switch (op) {
+        case 0: launch_embed_gather(s, (const float*)src, ids, src_idx, (float*)dst, n, H, (int)src_rows); break;
+        case 1: launch_copy_rows(s, src, src_idx, dst, dst_idx, n, width); break;
+        case 2: launch_rows_to_f32(s, src, src_bf16, src_idx, (float*)dst, n, H); break;
+        case 3: launch_f32_to_rows(s, (const float*)src, dst, dst_bf16, dst_idx, n, H); break;
+        case 4: launch_t_to_rows<float>(s, (const float*)src, dst, dst_bf16, dst_idx, n, H); break;
+        case 5: launch_t_to_rows<bf16>(s, (const bf16*)src, dst, dst_bf16, dst_idx, n, H); break;
+        default: launch_rows_differ(s, ids, H, first, stride, ref, n, from, (int32_t*)dst); break;
+    }
+    return finish(s);
 }
 
 }  // extern "C"
