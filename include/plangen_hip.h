@@ -98,6 +98,26 @@ const char* pg_last_error(pg_handle h /* may be NULL */);
  * return PG_ERR_NAME so the caller can count what it skipped. */
 int pg_load_tensor(pg_handle h, const char* name, const void* src, int dtype,
                    const int64_t* shape, int ndim);
+/* Merge one LoRA adapter pair into a weight that is already loaded:  W <- W + scale * B A  (peft's get_delta_weight with
+ * scale = lora_alpha / r; dropout is the identity in eval mode), on the device, in the layout the weight already has.
+ * ``weight_name`` is the BASE state_dict name of the weight (a leading "vl_gpt." is accepted); the targets are the seven
+ * projections of every Llama layer: self_attn.{q,k,v,o}_proj.weight and mlp.{gate,up,down}_proj.weight.  ``a_host`` is
+ * lora_A [r, in_features], ``b_host`` is lora_B [out_features, r], HOST memory, each PG_F32 or PG_BF16 (converted to fp32,
+ * which is exact).  Per element, every operation rounded to fp32 on its own (no FMA), k ascending:
+ *     acc = 0;  acc = acc + B[o][k] * A[k][i]  (k = 0 .. r - 1);   W[o][i] = T((float)W[o][i] + scale * acc)
+ * with T the handle's compute type (bf16: round to nearest even).  A bf16 handle loaded from a bf16 checkpoint (what
+ * Janus-Pro is) therefore holds ONE rounding of W + scale B A; a bf16 handle loaded from an fp32 source has rounded W once
+ * before.  Non-finite inputs are not covered.
+ * The weight is updated from its CURRENT contents: a second merge stacks on the first, pg_load_tensor of the base weight
+ * starts it afresh.  There is no un-merge: load the base tensor again.  Synchronous (NULL stream, ends with a device
+ * synchronisation) like pg_load_tensor, and like it the call un-finalizes the handle: call pg_finalize_weights afterwards,
+ * which rebuilds the decode layouts from the merged weights.
+ * PG_ERR_NAME: an unknown name or one that is not among the seven targets.  PG_ERR_STATE: the base weight was never loaded.
+ * PG_ERR_ARG: a null pointer, a dtype other than PG_F32 / PG_BF16, out_features / in_features that are not the weight's
+ * shape, r < 1 or r > 1024, a scale that is not finite.  Nothing is launched on a refusal and the handle stays usable. */
+int pg_merge_lora(pg_handle h, const char* weight_name,
+                  const void* a_host, int a_dtype, const void* b_host, int b_dtype,
+                  int out_features, int in_features, int r, float scale);
 /* After all tensors: build derived tables (gen_embed->gen_aligner table, L2-normalised
  * codebook -> post_quant_conv table, RoPE cos/sin).  ``missing`` (may be NULL) receives the
  * number of required tensors never loaded. */

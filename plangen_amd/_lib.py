@@ -52,6 +52,7 @@ SYMBOLS = [
     ("pg_destroy", C.c_int, [_P]),
     ("pg_last_error", C.c_char_p, [_P]),
     ("pg_load_tensor", C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    ("pg_merge_lora", C.c_int, [_P, C.c_char_p, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
     ("pg_finalize_weights", C.c_int, [_P, C.POINTER(C.c_int), _P]),
     ("pg_prefill", C.c_int, [_P, _P, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
     ("pg_prefill_replicated", C.c_int, [_P, _P, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, _P]),

@@ -2,7 +2,7 @@
 from __future__ import annotations
 
 from dataclasses import asdict, dataclass, field
-from typing import Tuple
+from typing import Optional, Tuple
 
 
 @dataclass
@@ -46,6 +46,8 @@ class PlanGenConfig:
     seed: int = 0
     share_replicas: int = 0        # parallel_size > 1: 1 = prefill every prompt once, its replicas read its K/V (Engine.prefill_replicated); 0 = replicate the ids (extension, off by default)
     kv_dtype: str = "bf16"         # KV cache of the decode loop: 'bf16' (the compute dtype) or 'fp8' (e4m3 codes + power-of-two scales; extension, off by default)
+    lora_alpha: Optional[float] = None   # a LoRA overlay (tuning_mode lora / lora_ranni) is merged with scale lora_alpha / r at load time; None: such an overlay is refused
+    lora_rank: Optional[int] = None      # when given, checked against the rank found in the overlay
 
     @property
     def img_tokens(self) -> int:

@@ -887,6 +887,20 @@ int pg_diag_op_convert(int kind, int src_bf16, int dst_bf16, const void* src, vo
     }
     return finish(s);
 }
+
+// launch_lora_merge<T> (pg_merge_lora's kernel, tests/test_gpu_lora_ops.py) on the caller's device buffers: W fp32 or bf16 (w_bf16), updated in place, [out][in]
+// row-major (layout 0 = K_T) or the gate (2 = K_IL16_G) / up (3 = K_IL16_U) rows of a [2 out][in] interleaved buffer (out % 8 == 0); A fp32 [r][in], B fp32
+// [out][r]; any out, in, r >= 1.  W must be aligned to its element, A and B to 4 bytes.
+int pg_diag_op_lora_merge(int w_bf16, int layout, void* W, int out, int in, const float* A, const float* B, int r, float scale, pg_stream stream) {
+    if (!W || !A || !B || (w_bf16 != 0 && w_bf16 != 1) || out < 1 || in < 1 || r < 1) return PG_ERR_ARG;
+    if (((uintptr_t)W & (w_bf16 ? 1 : 3)) || (((uintptr_t)A | (uintptr_t)B) & 3)) return PG_ERR_ARG;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    const bool ok = w_bf16 ? launch_lora_merge<bf16>(s, (bf16*)W, layout, out, in, A, B, r, scale)
+                           : launch_lora_merge<float>(s, (float*)W, layout, out, in, A, B, r, scale);
+    if (!ok) return PG_ERR_ARG;
+    return finish(s);
+}
 }  // extern "C"
 namespace {
 // idx [n] device (or null: the identity, n <= rows) inside [0, rows); distinct: no value twice (a scatter's rows must not race)

@@ -227,6 +227,7 @@ struct pg_engine {
     template <typename T> void lin(hipStream_t s, const LinW& l, const T* in, void* out, int out_f32, const void* residual, int res_f32, int act, long M);
     template <typename T> int vision_encode(const void* img, int img_dtype, void* out, int out_dtype, int B, hipStream_t s);
     int load_tensor(const char* name, const void* src, int dtype, const int64_t* shape, int ndim);
+    int merge_lora(const char* name, const void* a_host, int a_dtype, const void* b_host, int b_dtype, int out_f, int in_f, int r, float scale);
     int finalize(int* missing, hipStream_t s);
     // pad_len: [R0] rows; replicas > 1 (pg_prefill_replicated): the batch is R0 * replicas virtual rows of which only the R0 distinct ones are packed
     int prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtype, const int32_t* pad_len, int R0, int L_,

@@ -41,6 +41,11 @@ int pg_load_tensor(pg_handle h, const char* name, const void* src, int dtype, co
     if (!h || !name || !src) return PG_ERR_ARG;
     return h->load_tensor(name, src, dtype, shape, ndim);
 }
+int pg_merge_lora(pg_handle h, const char* weight_name, const void* a_host, int a_dtype, const void* b_host, int b_dtype, int out_features,
+                  int in_features, int r, float scale) {
+    if (!h || !weight_name || !a_host || !b_host) return PG_ERR_ARG;
+    return h->merge_lora(weight_name, a_host, a_dtype, b_host, b_dtype, out_features, in_features, r, scale);
+}
 int pg_finalize_weights(pg_handle h, int* missing, pg_stream s) { TuneGuard _tg(h); return h ? h->finalize(missing, (hipStream_t)s) : PG_ERR_ARG; }
 
 int pg_prefill(pg_handle h, const int32_t* ids_dev, const int32_t* pad_len_host, int R, int L, int position_mode,

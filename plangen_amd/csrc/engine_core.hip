@@ -445,6 +445,55 @@ int pg_engine::load_tensor(const char* name_c, const void* src, int dtype, const
     return PG_OK;
 }
 
+// pg_merge_lora: W <- W + scale * B A on the slot's CURRENT contents, in the slot's own layout (lora_merge.hip).  Every refusal comes before the first copy.
+static_assert(LORA_K_T == K_T && LORA_K_IL16_G == K_IL16_G && LORA_K_IL16_U == K_IL16_U, "launch_lora_merge takes SlotKind values");
+int pg_engine::merge_lora(const char* name_c, const void* a_host, int a_dtype, const void* b_host, int b_dtype, int out_f, int in_f, int r, float scale) {
+    std::string name = name_c;
+    if (name.rfind("vl_gpt.", 0) == 0) name = name.substr(7);
+    auto it = slots_map.find(name);
+    if (it == slots_map.end()) FAIL(PG_ERR_NAME, "pg_merge_lora: unknown tensor '%s'", name.c_str());
+    bool target = false;
+    for (const char* suf : {".self_attn.q_proj.weight", ".self_attn.k_proj.weight", ".self_attn.v_proj.weight", ".self_attn.o_proj.weight",
+                            ".mlp.gate_proj.weight", ".mlp.up_proj.weight", ".mlp.down_proj.weight"}) {
+        const size_t n = strlen(suf);
+        target = target || (name.rfind("language_model.model.layers.", 0) == 0 && name.size() > n && name.compare(name.size() - n, n, suf) == 0);
+    }
+    Slot& sl = it->second;
+    if (!target || sl.shape.size() != 2) FAIL(PG_ERR_NAME, "pg_merge_lora: '%s' is not a projection of a Llama layer", name.c_str());
+    if ((a_dtype != PG_F32 && a_dtype != PG_BF16) || (b_dtype != PG_F32 && b_dtype != PG_BF16)) FAIL(PG_ERR_ARG, "pg_merge_lora '%s': A / B dtype must be f32/bf16", name.c_str());
+    if (out_f != sl.shape[0] || in_f != sl.shape[1])
+        FAIL(PG_ERR_ARG, "pg_merge_lora '%s': adapter for [%d,%d], the weight is [%ld,%ld]", name.c_str(), out_f, in_f, (long)sl.shape[0], (long)sl.shape[1]);
+    if (r < 1 || r > 1024) FAIL(PG_ERR_ARG, "pg_merge_lora '%s': rank %d outside [1, 1024]", name.c_str(), r);
+    if (!std::isfinite(scale)) FAIL(PG_ERR_ARG, "pg_merge_lora '%s': scale is not finite", name.c_str());
+    if (!sl.loaded) FAIL(PG_ERR_STATE, "pg_merge_lora '%s': the base weight was never loaded", name.c_str());
+    HIPCHK(hipSetDevice(dev));
+    // staging: [A fp32 | B fp32 | raw A | raw B], each part 256-byte aligned; grown by load_tensor's rule
+    auto up = [](long b) { return (b + 255) & ~255L; };
+    const long na = (long)r * in_f, nb = (long)out_f * r;
+    const long raw_a = a_dtype == PG_BF16 ? up(na * 2) : 0, raw_b = b_dtype == PG_BF16 ? up(nb * 2) : 0;
+    const long nbytes = up(na * 4) + up(nb * 4) + raw_a + raw_b;
+    if (nbytes > stage_bytes) {
+        if (stage_dev) { (void)hipFree(stage_dev); stage_dev = nullptr; bytes -= stage_bytes; stage_bytes = 0; }
+        const long want = nbytes < (64L << 20) ? (64L << 20) : nbytes;
+        HIPCHK(hipMalloc(&stage_dev, want)); stage_bytes = want; bytes += want;
+    }
+    char* base = (char*)stage_dev;
+    float* a_dev = (float*)base; float* b_dev = (float*)(base + up(na * 4));
+    char* ra = base + up(na * 4) + up(nb * 4); char* rb = ra + raw_a;
+    hipStream_t s = nullptr;
+    if (a_dtype == PG_BF16) { HIPCHK(hipMemcpy(ra, a_host, na * 2, hipMemcpyHostToDevice)); launch_to_f32(s, ra, 1, a_dev, na); }
+    else HIPCHK(hipMemcpy(a_dev, a_host, na * 4, hipMemcpyHostToDevice));
+    if (b_dtype == PG_BF16) { HIPCHK(hipMemcpy(rb, b_host, nb * 2, hipMemcpyHostToDevice)); launch_to_f32(s, rb, 1, b_dev, nb); }
+    else HIPCHK(hipMemcpy(b_dev, b_host, nb * 4, hipMemcpyHostToDevice));
+    const bool ok = bf ? launch_lora_merge<bf16>(s, (bf16*)sl.dst, sl.kind, out_f, in_f, a_dev, b_dev, r, scale)
+                       : launch_lora_merge<float>(s, (float*)sl.dst, sl.kind, out_f, in_f, a_dev, b_dev, r, scale);
+    if (!ok) FAIL(PG_ERR_ARG, "pg_merge_lora '%s': launch_lora_merge refused [%d,%d] rank %d", name.c_str(), out_f, in_f, r);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    finalized = false;
+    return PG_OK;
+}
+
 int pg_engine::finalize(int* missing, hipStream_t s) {
     int miss = 0;
     for (auto& kvp : slots_map)

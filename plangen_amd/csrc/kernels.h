@@ -371,5 +371,11 @@ void launch_convert_conv(hipStream_t s, const void* src, int src_bf16, T* dst, i
 template <typename T>
 void launch_convert_interleave16(hipStream_t s, const void* src, int src_bf16, T* dst, int I, int H, int which);
 void launch_to_f32(hipStream_t s, const void* src, int src_bf16, float* dst, long n);
+// LoRA merge in place (lora_merge.hip): W[o][i] <- T((float)W[o][i] + scale * sum_k B[o][k] * A[k][i]), A fp32 [r, in], B fp32 [out, r], every product and sum
+// rounded to fp32 on its own in ascending k (no FMA).  layout: where row o of the [out, in] matrix sits in W -- pg_engine's SlotKind values of the three
+// layouts a projection has: row-major, or the gate / up half of the [8 gate | 8 up] interleave (out % 8 == 0).  false: refused, nothing launched.
+enum { LORA_K_T = 0, LORA_K_IL16_G = 2, LORA_K_IL16_U = 3 };
+template <typename T>
+bool launch_lora_merge(hipStream_t s, T* W, int layout, int out, int in, const float* A, const float* B, int r, float scale);
 void launch_l2norm_rows(hipStream_t s, const float* src, float* dst, int n, int D);
 void launch_fill_zero(hipStream_t s, void* p, long bytes);

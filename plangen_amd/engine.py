@@ -228,6 +228,31 @@ class Engine:
             loaded += 1
         return loaded, skipped
 
+    def merge_lora(self, name: str, A: torch.Tensor, B: torch.Tensor, scale: float) -> None:
+        """``pg_merge_lora``: W <- W + scale * B A on the device, for the loaded projection ``name`` (its base state_dict name).
+        A = lora_A [r, in], B = lora_B [out, r], fp32 or bf16 (other types are converted to fp32).  Un-finalizes the engine:
+        call :meth:`finalize` after the last merge."""
+        if A.dim() != 2 or B.dim() != 2 or B.shape[1] != A.shape[0]:
+            raise PlanGenError(f"merge_lora({name}): lora_A {tuple(A.shape)} / lora_B {tuple(B.shape)} are not [r, in] / [out, r]")
+
+        def host(t):
+            t = t.detach()
+            if t.dtype not in (torch.float32, torch.bfloat16):
+                t = t.float()
+            return t.cpu().contiguous()
+
+        A, B = host(A), host(B)
+        rc = self.lib.pg_merge_lora(self.h, name.encode(), C.c_void_p(A.data_ptr()), _dt(A), C.c_void_p(B.data_ptr()), _dt(B),
+                                    B.shape[0], A.shape[1], A.shape[0], float(scale))
+        self._check(rc, f"pg_merge_lora({name})")
+
+    def load_lora(self, adapters: Dict[str, Tuple[torch.Tensor, torch.Tensor]], alpha: float) -> int:
+        """Merge every (lora_A, lora_B) pair of ``adapters`` (base weight name -> pair) with peft's scale alpha / r, r = A's rows.
+        Returns the number merged; :meth:`finalize` is the caller's."""
+        for name, (A, B) in adapters.items():
+            self.merge_lora(name, A, B, float(alpha) / A.shape[0])
+        return len(adapters)
+
     def finalize(self, strict: bool = True) -> int:
         """``pg_finalize_weights``: derived tables + decode weight layouts, once per checkpoint.  strict: raise when a
         required tensor was never loaded; otherwise the engine is told to run with the missing ones reading as zeros

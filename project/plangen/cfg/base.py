@@ -5,6 +5,8 @@ janus_path = "models/Janus-Pro-1B"     # base.py:8,12  (HF safetensors directory
 system_cls_path = "project.plangen.plangen_base"
 out_path = "out/plangen"
 resume = "latest"                      # base.py:47: newest checkpoint-* under out_path, a path, or None
+lora_alpha = None                      # base.py: lora_alpha of tuning_mode 'lora' (128 there; 'lora_ranni' trains with 16).  A LoRA checkpoint (lora_A / lora_B tensors) is merged into the weights at load time with scale lora_alpha / r; None: such a checkpoint is refused, the value is not in the file
+lora_rank = None                       # base.py: lora_rank (256 there; 'lora_ranni' uses 64).  When set, checked against the rank found in the checkpoint
 test = False
 janus_hw = 384                         # base.py:83
 parallel_size = 1                      # base.py:158

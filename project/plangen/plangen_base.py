@@ -58,6 +58,8 @@ class System(_HotPath):
         cfg.layout_grammar = bool(getattr(args, "layout_grammar", False))
         cfg.kv_dtype = str(getattr(args, "kv_dtype", "bf16"))
         cfg.share_replicas = int(getattr(args, "share_replicas", 0))
+        alpha, rank = getattr(args, "lora_alpha", None), getattr(args, "lora_rank", None)
+        cfg.lora_alpha, cfg.lora_rank = (None if alpha is None else float(alpha)), (None if rank is None else int(rank))
         select_best = bool(getattr(args, "select_best", False))
         layout_best_of = max(1, int(getattr(args, "layout_best_of", 1)))
         bs = int(args.test_batch_size)
@@ -237,7 +239,7 @@ class System(_HotPath):
         if a.resume not in (None, "latest") and not os.path.exists(str(ck)):
             raise FileNotFoundError(f"resume={a.resume!r}: {ck!r} does not exist")
         if a.janus_path and os.path.isdir(str(a.janus_path)):
-            info = load_checkpoint(self.engine, a.janus_path, overlay=ck, strict=True)
+            info = load_checkpoint(self.engine, a.janus_path, overlay=ck, strict=True, lora_alpha=self.cfg.lora_alpha, lora_rank=self.cfg.lora_rank)
             print(f"loaded {info['loaded'][0]} tensors from {a.janus_path}" + (f" + overlay {ck}" if ck else "")
                   + (f"; {len(info['skipped'])} tensors not owned by this engine" if info["skipped"] else ""))
         elif self.synthetic:
