@@ -323,6 +323,41 @@ int pg_generate_text_constrained(pg_handle h, int max_new, int eos_id, float tem
  * B * T / B * max_new, or the "lanes" = 2 decode. */
 int pg_request_token_logprobs(pg_handle h, float* out_dev, int64_t capacity_floats);
 
+/* Per-token uncertainty: what else the model was considering where a decode loop emitted a token.  Rows, y, x = y * (1 / temperature)
+ * (NaN as -inf), tok and the forcing rules are those of pg_request_token_logprobs above; top-k and top-p renormalise nothing, the EOS
+ * ban and the automaton's mask do (a masked entry is -inf in y and is never an alternative).  Per row and step, all fp32 with the
+ * accurate expf / logf, m = max_v x_v, s = sum_v expf(x_v - m), t = sum_v expf(x_v - m) (x_v - m) (an entry -inf adds 0 to both):
+ *   logprob      (x[tok] - m) - logf(s): bit for bit what pg_request_token_logprobs writes for the same call;
+ *   entropy      H = logf(s) - t / s of softmax(x), in nats (>= 0 up to rounding; log V for a flat row);
+ *   rank         #{v : x_v > x[tok]}, exact: 0 says the emitted token was the mode;
+ *   alt_tok      the n_alt largest x_v, descending, the lowest index first among equals, exact;
+ *   alt_logprob  (x_v - m) - logf(s) of each alternative (alt_logprob[0] is the logprob a token alt_tok[0] would have got).
+ * A row without a finite entry: H = 0, rank = V_row (the row's length), logprob -inf.  m = +inf: the mass lies evenly on the k entries
+ * +inf, H = logf(k).  A token outside the row or on a -inf entry: rank = V_row.  Fewer than n_alt entries above -inf: the missing
+ * places hold alt_tok = -1, alt_logprob = -inf.  Text: a row that was finished BEFORE a step gets logprob 0, entropy 0, rank 0,
+ * alt_tok -1, alt_logprob 0 there; columns >= *out_len_host are left untouched.
+ * The arrays are [B, T] (image loop) or [B, max_new] (text loop), the alt_* ones [.., n_alt]; a NULL pointer skips that output. */
+typedef struct pg_token_stats {
+    float*   logprob_dev;
+    float*   entropy_dev;
+    int32_t* rank_dev;
+    int32_t* alt_tok_dev;        /* [.., n_alt] */
+    float*   alt_logprob_dev;    /* [.., n_alt] */
+    int32_t  n_alt;              /* 0..8 */
+    int64_t  capacity;           /* positions (B * T, B * max_new) every non-NULL array can hold */
+} pg_token_stats;
+/* ONE-SHOT like pg_request_token_logprobs and independent of it: the request (copied here) is consumed by the next
+ * pg_decode_image_tokens[_filtered] / pg_generate_text_{greedy,sampled,constrained} on this handle, whether that call succeeds or
+ * not; both requests may be pending for one call, and then their logprob arrays hold the same bits.  The arrays must stay valid
+ * until that call's work on the stream is done.  Inside the loop one more 1024-thread block per row reduces the stored row (the route
+ * pg_request_token_logprobs uses) into a library-owned buffer (allocated by the first request, counted by pg_device_bytes), copied
+ * out at the end; a captured step graph is re-captured when a call's request differs from the capture's.  A call without a request
+ * launches exactly what it launched before this entry point existed.  req == NULL cancels a pending request.
+ * PG_ERR_ARG (nothing launched, the handle still usable): here, n_alt outside 0..8, capacity < 1, n_alt > 0 with exactly one of
+ * the two alt_* pointers, all five pointers NULL; at the consuming call, capacity below B * T / B * max_new, or the "lanes" = 2
+ * decode. */
+int pg_request_token_stats(pg_handle h, const pg_token_stats* req);
+
 /* -- scoring given text ---------------------------------------------------------------------
  * log softmax(lm_head(hidden))[target] for n chosen rows of a hidden-state tensor, logits never materialised: the evaluation half of
  * pg_request_token_logprobs.  hidden_dev [rows, hidden] in the compute dtype (hidden_dtype must say so) -- typically what pg_prefill /
@@ -544,6 +579,13 @@ int pg_op_text_constrain(pg_handle h, const float* logits_dev /*[B,V]*/, int B, 
  * any handle.  PG_ERR_ARG: a null pointer, B < 1, V < 1. */
 int pg_op_token_logprob(pg_handle h, const float* x_dev, int B, int V, const int32_t* tok_dev, float temperature,
                         float* logprob_dev, pg_stream s);
+
+/* The reducer of pg_request_token_stats on caller-given rows (same device code): x_dev fp32 [B, V] (the row y; any B >= 1, V >= 1, any
+ * 4-byte alignment), tok_dev int32 [B], temperature as above -> the arrays of out ([B] and [B, n_alt]; capacity >= B; a NULL pointer
+ * skips that output).  logprob equals pg_op_token_logprob on the same inputs bit for bit.  Works on any handle.  PG_ERR_ARG: a null
+ * x_dev / tok_dev / out, B < 1, V < 1, and what pg_request_token_stats refuses. */
+int pg_op_token_stats(pg_handle h, const float* x_dev, int B, int V, const int32_t* tok_dev, float temperature,
+                      const pg_token_stats* out, pg_stream s);
 
 /* The device code of pg_score_tokens on caller-given weights: x_dev [rows, K], w_dev [V, K] row-major, both in the handle's compute
  * dtype; any n >= 1 and V >= 1, K a positive multiple of 64.  Works on any handle.  PG_ERR_ARG as pg_score_tokens. */

@@ -40,6 +40,11 @@ class pg_text_dfa(C.Structure):
                 ("n_states", C.c_int32), ("n_classes", C.c_int32), ("start_state", C.c_int32)]
 
 
+class pg_token_stats(C.Structure):
+    _fields_ = [("logprob_dev", C.c_void_p), ("entropy_dev", C.c_void_p), ("rank_dev", C.c_void_p), ("alt_tok_dev", C.c_void_p),
+                ("alt_logprob_dev", C.c_void_p), ("n_alt", C.c_int32), ("capacity", C.c_int64)]
+
+
 class pg_timing(C.Structure):
     _fields_ = [("decode_ms", C.c_float), ("attn_ms_sum", C.c_float), ("attn_launches", C.c_int32),
                 ("attn_bytes_sum", C.c_double), ("prefill_ms", C.c_float), ("vq_ms", C.c_float)]
@@ -68,6 +73,7 @@ SYMBOLS = [
     ("pg_set_text_dfa", C.c_int, [_P, C.POINTER(pg_text_dfa), _P]),
     ("pg_generate_text_constrained", C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_int32, C.c_float, C.c_uint64, _P, C.POINTER(C.c_int), _P, _P, _P]),
     ("pg_request_token_logprobs", C.c_int, [_P, _P, C.c_int64]),
+    ("pg_request_token_stats", C.c_int, [_P, C.POINTER(pg_token_stats)]),
     ("pg_score_tokens", C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.c_int64, C.c_float, _P, _P]),
     ("pg_score_image_tokens", C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, _P, C.c_int64, C.c_float, C.c_float, _P, _P]),
     ("pg_vq_decode", C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
@@ -88,6 +94,7 @@ SYMBOLS = [
     ("pg_op_text_constrain", C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int,
                                        _P, _P, _P, _P]),
     ("pg_op_token_logprob", C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_float, _P, _P]),
+    ("pg_op_token_stats", C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_float, C.POINTER(pg_token_stats), _P]),
     ("pg_op_head_logprob", C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.c_int, _P, _P, C.c_int64, C.c_float, _P, _P]),
     ("pg_op_cfg_head_logprob", C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, _P, _P]),
     ("pg_op_kv_quantize", C.c_int, [_P, _P, _P, _P, C.c_int64, _P]),

@@ -117,6 +117,15 @@ struct pg_engine {
     // pg_request_token_logprobs: the caller's destination for the NEXT decode / generate call (one-shot, like uncond_hint) and the library-owned
     // [B, T] / [B, max_new] buffer the loop's kernels write (allocated by the first request, so a captured step keeps a valid address)
     float* lp_req = nullptr; int64_t lp_req_cap = 0; float* d_logprob = nullptr;
+    // pg_request_token_stats: the same one-shot scheme, independent of lp_req.  d_stats (first request) holds P = max_rows * (max_new + 1)
+    // positions of every output at the widest request: [logprob P | entropy P | rank P | alt_tok 8 P | alt_logprob 8 P] (stats_out)
+    pg_token_stats ts_req{}; bool ts_pending = false; float* d_stats = nullptr;
+    const char* check_stats_request(const pg_token_stats* r) const;      // null, or why pg_request_token_stats / pg_op_token_stats refuse it
+    TokenStatsOut stats_out(int n_alt) const {
+        const size_t P = (size_t)cfg.max_rows * (cfg.max_new + 1);
+        return TokenStatsOut{d_stats, d_stats + P, (int32_t*)(d_stats + 2 * P), (int32_t*)(d_stats + 3 * P), d_stats + 11 * P, n_alt};
+    }
+    int stats_copy_out(const pg_token_stats& r, int B, int cols, int pitch_cols, hipStream_t s);   // the first cols columns of [B, pitch_cols]
     int rng_image_offset = 0;                                    // pg_set_option("rng_image_offset", lo): this rank's first image in the global batch
     PgTune tune;                                                 // per-handle tuning knobs (pg_set_option)
     int tune_epoch = 0;                                          // bumped by every option that changes what a captured graph contains
@@ -249,6 +258,7 @@ struct pg_engine {
                       float* logits_out, hipStream_t s, bool constrained = false, int32_t* state_out = nullptr);
     int set_text_dfa(const pg_text_dfa* dfa, hipStream_t s);
     int token_logprob(const float* x, int B, int V, const int32_t* tok, float temp, float* out, hipStream_t s);
+    int token_stats(const float* x, int B, int V, const int32_t* tok, float temp, const pg_token_stats* out, hipStream_t s);
     int head_logprob(const char* who, const void* x, int64_t rows, const void* w, int V, int K, const int32_t* row_idx, const int32_t* target, int64_t n,
                      float temp, float* out, hipStream_t s);
     int sh_reserve(long need);

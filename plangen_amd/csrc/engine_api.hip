@@ -134,6 +134,13 @@ int pg_request_token_logprobs(pg_handle h, float* out_dev, int64_t capacity_floa
     h->lp_req = out_dev; h->lp_req_cap = out_dev ? capacity_floats : 0;
     return PG_OK;
 }
+int pg_request_token_stats(pg_handle h, const pg_token_stats* req) {
+    if (!h) return PG_ERR_ARG;
+    if (!req) { h->ts_pending = false; return PG_OK; }
+    if (const char* why = h->check_stats_request(req)) { h->err = std::string("pg_request_token_stats: ") + why; return PG_ERR_ARG; }
+    h->ts_req = *req; h->ts_pending = true;
+    return PG_OK;
+}
 int pg_vq_decode(pg_handle h, const int32_t* codes_dev, void* img_out_dev, int out_dtype, int B, pg_stream s) { TuneGuard _tg(h);
     if (!h || !codes_dev || !img_out_dev) return PG_ERR_ARG;
     return h->bf ? h->vq_decode<bf16>(codes_dev, img_out_dev, out_dtype, B, (hipStream_t)s)
@@ -326,6 +333,10 @@ int pg_op_text_constrain(pg_handle h, const float* logits_dev, int B, int V, con
 int pg_op_token_logprob(pg_handle h, const float* x_dev, int B, int V, const int32_t* tok_dev, float temperature, float* logprob_dev, pg_stream s) {
     if (!h || !x_dev || !tok_dev || !logprob_dev) return PG_ERR_ARG;
     return h->token_logprob(x_dev, B, V, tok_dev, temperature, logprob_dev, (hipStream_t)s);
+}
+int pg_op_token_stats(pg_handle h, const float* x_dev, int B, int V, const int32_t* tok_dev, float temperature, const pg_token_stats* out, pg_stream s) {
+    if (!h || !x_dev || !tok_dev || !out) return PG_ERR_ARG;
+    return h->token_stats(x_dev, B, V, tok_dev, temperature, out, (hipStream_t)s);
 }
 int pg_score_tokens(pg_handle h, const void* hidden_dev, int hidden_dtype, int64_t rows, const int32_t* row_idx_dev, const int32_t* target_dev, int64_t n,
                     float temperature, float* logprob_dev, pg_stream s) { TuneGuard _tg(h);

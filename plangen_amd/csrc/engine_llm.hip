@@ -308,6 +308,8 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
                             const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s) {
     float* const lp_out = lp_req; const int64_t lp_cap = lp_req_cap;      // the one-shot log-prob request: consumed whatever this call answers
     lp_req = nullptr; lp_req_cap = 0;
+    const pg_token_stats ts = ts_req; const bool stats = ts_pending;      // the one-shot stats request: the same
+    ts_pending = false;
     if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(PG_ERR_ARG, "top_k=%d must be >= 0 and top_p=%g in (0, 1]", top_k, (double)top_p);
     if (!prefilled) FAIL(PG_ERR_STATE, "pg_decode_image_tokens before pg_prefill");
     if (kv8 && !fuse_rope) FAIL(PG_ERR_ARG, "the FP8 KV cache needs the fused decode attention (fuse_rope)");
@@ -319,10 +321,14 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     if (T < 1 || T - 1 > cfg.max_new) FAIL(PG_ERR_CAPACITY, "T=%d exceeds max_new=%d", T, cfg.max_new);
     if (lp_out && lp_cap < (int64_t)(R / 2) * T) FAIL(PG_ERR_ARG, "token log-probs: capacity %lld floats is below B * T = %lld", (long long)lp_cap, (long long)(R / 2) * T);
     if (lp_out && lanes_opt == 2) FAIL(PG_ERR_ARG, "token log-probs do not support lanes = 2");
+    if (stats && ts.capacity < (int64_t)(R / 2) * T) FAIL(PG_ERR_ARG, "token stats: capacity %lld positions is below B * T = %lld", (long long)ts.capacity, (long long)(R / 2) * T);
+    if (stats && lanes_opt == 2) FAIL(PG_ERR_ARG, "token stats do not support lanes = 2");
     HIPCHK(hipSetDevice(dev));
     const int Rtot = R, B = R / 2;
     const bool score = lp_out != nullptr;
     if (score && !d_logprob) TRY(dalloc(&d_logprob, (size_t)cfg.max_rows * (cfg.max_new + 1) * 4, false));
+    if (stats && !d_stats) TRY(dalloc(&d_stats, (size_t)cfg.max_rows * (cfg.max_new + 1) * 19 * 4, false));
+    const bool stored = score || stats;                                   // the step also leaves the row the draw is made from in the row workspace
     // Lanes: at large batch the rows are split into two independent chains on two streams so one
     // half's latency-bound GEMM / norm kernels overlap the other half's bandwidth-bound attention.
     // CFG pairs never straddle lanes; results are lane-independent (global image index in the RNG).
@@ -336,7 +342,7 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     if (filtered) {
         if (cfg.img_vocab > SEL_MAXV) FAIL(PG_ERR_CAPACITY, "top-k / top-p sampler supports img_vocab <= %d (got %d)", SEL_MAXV, cfg.img_vocab);
     }
-    if ((filtered || score) && !cfg_mix) TRY(dalloc(&cfg_mix, (size_t)(cfg.max_rows / 2) * cfg.img_vocab * 4, false));
+    if ((filtered || stored) && !cfg_mix) TRY(dalloc(&cfg_mix, (size_t)(cfg.max_rows / 2) * cfg.img_vocab * 4, false));
     struct LaneDef { int r0, nrows; float* part; int32_t* ndec; };
     LaneDef ld[2];
     ld[0] = {0, nl == 2 ? Rtot / 2 : Rtot, part, d_ndec};
@@ -372,10 +378,11 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
         tic(st);
         if (filtered) launch_cfg_sample_filtered(st, sa, R / 2, cfg_pv, cfg_pi, cfg_mix);
         else {
-            if (score) launch_cfg_store(st, sa, R / 2, cfg_mix);     // the filtered route already leaves the mixed rows in cfg_mix
+            if (stored) launch_cfg_store(st, sa, R / 2, cfg_mix);    // the filtered route already leaves the mixed rows in cfg_mix
             launch_cfg_sample(st, sa, R / 2, cfg_pv, cfg_pi);
         }
         if (score) launch_token_logprob_image(st, sa, R / 2, cfg_mix, d_logprob);
+        if (stats) launch_token_stats_image(st, sa, R / 2, cfg_mix, stats_out(ts.n_alt));
         toc(st, TC_SAMPLE, (double)S_last * R * cfg.img_vocab * 4.0);
         tc_on = false;
     };
@@ -420,7 +427,8 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
         std::vector<int64_t> key = {Rtot, (int64_t)bf, (int64_t)logits_out, (int64_t)shared_len, (int64_t)fuse_rope, (int64_t)nl,
                                     (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch, (int64_t)skip_attn, (int64_t)filtered,
                                     (int64_t)group_rows,         // replica geometry: never replay a graph across different aliasing
-                                    (int64_t)score};             // the scored step holds two more launches
+                                    (int64_t)score,              // the scored step holds two more launches
+                                    (int64_t)(stats ? 1 + ts.n_alt : 0)};        // the stats step one more (and the store, if score did not bring it)
         if (!gexec || key != gkey) {
             if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
             hipGraph_t g = nullptr;
@@ -440,6 +448,7 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     if (T > 1) TRY(iteration(false));
     HIPCHK(hipMemcpyAsync(out_tok, d_out_tok, (size_t)B * T * 4, hipMemcpyDeviceToDevice, ws));
     if (score) HIPCHK(hipMemcpyAsync(lp_out, d_logprob, (size_t)B * T * 4, hipMemcpyDeviceToDevice, ws));
+    if (stats) TRY(stats_copy_out(ts, B, T, T, ws));
     HIPCHK(hipEventRecord(ev_t1, ws));
     if (ws != s) {
         HIPCHK(hipEventRecord(ev_out, ws));
@@ -580,6 +589,48 @@ int pg_engine::token_logprob(const float* x, int B, int V, const int32_t* tok, f
     return PG_OK;
 }
 
+// pg_request_token_stats / pg_op_token_stats: what both refuse
+const char* pg_engine::check_stats_request(const pg_token_stats* r) const {
+    if (r->n_alt < 0 || r->n_alt > 8) return "n_alt must be in 0..8";
+    if (r->capacity < 1) return "capacity must be >= 1";
+    if (r->n_alt > 0 && (r->alt_tok_dev == nullptr) != (r->alt_logprob_dev == nullptr)) return "n_alt > 0 needs both alt_tok_dev and alt_logprob_dev, or neither";
+    const bool alts = r->n_alt > 0 && r->alt_tok_dev;
+    if (!r->logprob_dev && !r->entropy_dev && !r->rank_dev && !alts) return "no output requested";
+    if (((uintptr_t)r->logprob_dev | (uintptr_t)r->entropy_dev | (uintptr_t)r->rank_dev | (uintptr_t)r->alt_tok_dev | (uintptr_t)r->alt_logprob_dev) & 3)
+        return "pointers must be 4-byte aligned";
+    return nullptr;
+}
+
+// the loop's library-owned results -> the caller's arrays: the first cols columns of every [B, pitch_cols] array (alternatives: x n_alt)
+int pg_engine::stats_copy_out(const pg_token_stats& r, int B, int cols, int pitch_cols, hipStream_t s) {
+    const TokenStatsOut o = stats_out(r.n_alt);
+    auto copy = [&](void* dst, const void* src, size_t per) -> hipError_t {
+        return hipMemcpy2DAsync(dst, (size_t)pitch_cols * per, src, (size_t)pitch_cols * per, (size_t)cols * per, B, hipMemcpyDeviceToDevice, s);
+    };
+    if (cols < 1) return PG_OK;
+    if (r.logprob_dev) HIPCHK(copy(r.logprob_dev, o.logprob, 4));
+    if (r.entropy_dev) HIPCHK(copy(r.entropy_dev, o.entropy, 4));
+    if (r.rank_dev) HIPCHK(copy(r.rank_dev, o.rank, 4));
+    if (r.n_alt > 0 && r.alt_tok_dev) {
+        HIPCHK(copy(r.alt_tok_dev, o.alt_tok, (size_t)r.n_alt * 4));
+        HIPCHK(copy(r.alt_logprob_dev, o.alt_logprob, (size_t)r.n_alt * 4));
+    }
+    return PG_OK;
+}
+
+// pg_op_token_stats: the loops' second reducer on caller-given rows and tokens
+int pg_engine::token_stats(const float* x, int B, int V, const int32_t* tok, float temp, const pg_token_stats* out, hipStream_t s) {
+    if (B < 1 || V < 1) FAIL(PG_ERR_ARG, "pg_op_token_stats: needs B >= 1 and V >= 1 (got %d, %d)", B, V);
+    if (((uintptr_t)x & 3) || ((uintptr_t)tok & 3)) FAIL(PG_ERR_ARG, "pg_op_token_stats: pointers must be 4-byte aligned");
+    if (const char* why = check_stats_request(out)) FAIL(PG_ERR_ARG, "pg_op_token_stats: %s", why);
+    if (out->capacity < B) FAIL(PG_ERR_ARG, "pg_op_token_stats: capacity %lld is below B = %d", (long long)out->capacity, B);
+    HIPCHK(hipSetDevice(dev));
+    const bool alts = out->n_alt > 0 && out->alt_tok_dev;
+    launch_token_stats_op(s, x, B, V, tok, temp, TokenStatsOut{out->logprob_dev, out->entropy_dev, out->rank_dev, out->alt_tok_dev, out->alt_logprob_dev, alts ? out->n_alt : 0});
+    HIPCHK(hipGetLastError());
+    return PG_OK;
+}
+
 // pg_score_tokens / pg_op_head_logprob: log softmax(x . w^T)[target] for n chosen rows.  bf16: the fused head (score_head.hip), only its
 // (max, sum) partials touch HBM.  f32 (parity mode): the f32 GEMM + token_logprob_kernel over row chunks whose logits stay <= 64 MB.
 int pg_engine::head_logprob(const char* who, const void* x, int64_t rows, const void* w, int V, int K, const int32_t* row_idx, const int32_t* target,
@@ -698,6 +749,8 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
                              float* logits_out, hipStream_t s, bool constrained, int32_t* state_out) {
     float* const lp_out = lp_req; const int64_t lp_cap = lp_req_cap;      // the one-shot log-prob request: consumed whatever this call answers
     lp_req = nullptr; lp_req_cap = 0;
+    const pg_token_stats ts = ts_req; const bool stats = ts_pending;      // the one-shot stats request: the same
+    ts_pending = false;
     if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(PG_ERR_ARG, "top_k=%d must be >= 0 and top_p=%g in (0, 1]", top_k, (double)top_p);
     if (!prefilled) FAIL(PG_ERR_STATE, "text decode before pg_prefill");
     if (replicas_n > 1) FAIL(PG_ERR_STATE, "text decode after pg_prefill_replicated (position_mode 0, image sampling only)");
@@ -710,14 +763,17 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
         if (dfa_dist_start > max_new) FAIL(PG_ERR_ARG, "max_new=%d is below dist[start_state]=%d: no row could finish", max_new, dfa_dist_start);
     }
     if (lp_out && lp_cap < (int64_t)R * max_new) FAIL(PG_ERR_ARG, "token log-probs: capacity %lld floats is below B * max_new = %lld", (long long)lp_cap, (long long)R * max_new);
+    if (stats && ts.capacity < (int64_t)R * max_new) FAIL(PG_ERR_ARG, "token stats: capacity %lld positions is below B * max_new = %lld", (long long)ts.capacity, (long long)R * max_new);
     HIPCHK(hipSetDevice(dev));
     const int B = R;
     const bool score = lp_out != nullptr;
     if (score && !d_logprob) TRY(dalloc(&d_logprob, (size_t)cfg.max_rows * (cfg.max_new + 1) * 4, false));
+    if (stats && !d_stats) TRY(dalloc(&d_stats, (size_t)cfg.max_rows * (cfg.max_new + 1) * 19 * 4, false));
+    const bool stored = score || stats;                                   // the step also leaves the row the draw is made from in the row workspace
     // launch structure: greedy argmax (temperature <= 0 ignores the filters, as HF's warpers do) / Gumbel-max folded into the scan /
     // scan -> workspace -> select.  Everything else about sampling is a value in TextParams.
     const int mode = !(temp > 0.f) ? 0 : ((top_k > 0 || top_p < 1.f) ? 2 : 1);
-    if ((mode == 2 || score) && !txt_mix) TRY(dalloc(&txt_mix, (size_t)cfg.max_rows * cfg.vocab * 4, false));
+    if ((mode == 2 || stored) && !txt_mix) TRY(dalloc(&txt_mix, (size_t)cfg.max_rows * cfg.vocab * 4, false));
     std::vector<int32_t> ones(B, 1);
     HIPCHK(hipMemcpyAsync(d_unf, ones.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(d_anyunf, 0, 1024 * 4, s));
@@ -752,12 +808,13 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
         else gemm_llm<float>(ws, (const float*)hfin, (const float*)lm_head, B, cfg.vocab, H(), true);
         ta.logits_partial = part; ta.S = S_last; ta.slab = slab_last;
         // scored greedy / Gumbel-in-the-scan steps: the row goes to txt_mix first (mode 2 leaves it there anyway); the step's own scan follows
-        if (score && mode != 2) launch_text_store(ws, ta, constrained ? &da : nullptr, B, cfg_pv, cfg_pi, txt_mix);
+        if (stored && mode != 2) launch_text_store(ws, ta, constrained ? &da : nullptr, B, cfg_pv, cfg_pi, txt_mix);
         if (constrained) launch_text_constrained(ws, ta, da, B, mode, cfg_pv, cfg_pi, txt_mix);
         else if (mode == 2) launch_text_sample_filtered(ws, ta, B, cfg_pv, cfg_pi, txt_mix);
         else if (mode == 1) launch_text_sample(ws, ta, B, cfg_pv, cfg_pi);
         else launch_text_argmax(ws, ta, B, cfg_pv, cfg_pi);
         if (score) launch_token_logprob_text(ws, ta, B, txt_mix, d_logprob);
+        if (stats) launch_token_stats_text(ws, ta, B, txt_mix, stats_out(ts.n_alt));
         if (with_forward) forward_decode(ws);
     };
     for (int step_i = 0; step_i < max_new; ++step_i) {
@@ -765,7 +822,7 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
         if (use_graph && !last && step_i > 0) {
             // shapes and kernel selection only: temperature, top_k, top_p, seed and the row offset reach the kernels through TextParams
             std::vector<int64_t> key = {R, (int64_t)bf, (int64_t)fuse_rope, (int64_t)shared_len, (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch,
-                                        (int64_t)mode, (int64_t)logits_out, (int64_t)constrained, (int64_t)score};
+                                        (int64_t)mode, (int64_t)logits_out, (int64_t)constrained, (int64_t)score, (int64_t)(stats ? 1 + ts.n_alt : 0)};
             if (!gexec_txt || key != gkey_txt) {
                 if (gexec_txt) { (void)hipGraphExecDestroy(gexec_txt); gexec_txt = nullptr; }
                 hipGraph_t g = nullptr;
@@ -793,6 +850,7 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
     // only the columns this call produced; the caller's buffer keeps its own fill beyond them
     HIPCHK(hipMemcpy2DAsync(out, (size_t)max_new * 8, d_text_out, (size_t)max_new * 8, (size_t)done_len * 8, B, hipMemcpyDeviceToDevice, ws));
     if (score) HIPCHK(hipMemcpy2DAsync(lp_out, (size_t)max_new * 4, d_logprob, (size_t)max_new * 4, (size_t)done_len * 4, B, hipMemcpyDeviceToDevice, ws));
+    if (stats) TRY(stats_copy_out(ts, B, done_len, max_new, ws));
     if (constrained && state_out) HIPCHK(hipMemcpyAsync(state_out, d_dfa_state, (size_t)B * 4, hipMemcpyDeviceToDevice, ws));
     if (ws != s) {
         HIPCHK(hipEventRecord(ev_out, ws));

@@ -302,6 +302,22 @@ void launch_token_logprob_image(hipStream_t s, const SampleArgs& a, int B, const
 // also leaves chunk maxima in scratch_v / scratch_i: launch it BEFORE the step's own scan, which overwrites them with its winners.
 void launch_text_store(hipStream_t s, const TextArgs& a, const TextDfaArgs* d, int B, float* scratch_v, int* scratch_i, float* mix);
 void launch_token_logprob_text(hipStream_t s, const TextArgs& a, int B, const float* mix, float* out);
+// Per-token uncertainty (pg_request_token_stats / pg_op_token_stats; definition: include/plangen_hip.h; kernel: token_stats.hip).  The second
+// reducer on the stored-row route: the same rows, x, token, step and destination index as LogprobArgs, and per position the log-probability
+// (the bits of token_logprob_kernel), the entropy of softmax(x), the emitted token's rank and the n_alt <= 8 largest entries (ids,
+// log-probabilities).  Any output pointer may be null (skipped).  The loops' forms index every array as the log-prob buffer is indexed
+// ([B, T] / [B, max_new], alternatives [.., n_alt]); a finished text row gets logprob 0, entropy 0, rank 0, alt_tok -1, alt_logprob 0.
+struct TokenStatsOut { float* logprob; float* entropy; int32_t* rank; int32_t* alt_tok; float* alt_logprob; int n_alt; };
+struct StatsArgs {
+    const float* rows; int V;                                     // [gridDim, V] fp32
+    const SampleParams* sp; const TextParams* tp; float temperature;      // as LogprobArgs
+    const int32_t* tok32; const int64_t* tok64;
+    const int32_t* n_dec; int b_off;
+    TokenStatsOut o;
+};
+void launch_token_stats_op(hipStream_t s, const float* rows, int B, int V, const int32_t* tok, float temperature, const TokenStatsOut& o);
+void launch_token_stats_image(hipStream_t s, const SampleArgs& a, int B, const float* mix, const TokenStatsOut& o);
+void launch_token_stats_text(hipStream_t s, const TextArgs& a, int B, const float* mix, const TokenStatsOut& o);
 // Fused lm_head + log-softmax at a target (score_head.hip; contract and geometry in its header): X bf16 [rows, K], W bf16 [V, K] row-major,
 // row_idx int32 [n] or null (identity), target int32 [n] -> out fp32 [n].  part: >= head_logprob_ws_bytes(n, V, K) bytes of workspace
 // ([G][n] (max, sum) pairs).  K % 64 == 0 (the kernel's K step).  False (nothing launched) on a shape it does not take.

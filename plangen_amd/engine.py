@@ -31,6 +31,15 @@ def _torch_dt(code: int):
     return torch.bfloat16 if code == PG_BF16 else torch.float32
 
 
+def _wants_stats(return_stats) -> bool:
+    """``return_stats``: False / None is off; True is n_alt = 0; an int is n_alt (0 is still a request)."""
+    return return_stats is not None and return_stats is not False
+
+
+def _n_alt(return_stats) -> int:
+    return 0 if return_stats is True else int(return_stats)
+
+
 def replica_owner(row: int, R0: int, shared: bool) -> int:
     """Owner rule of ``pg_prefill_replicated``: the row whose cache holds the prompt K/V that ``row`` of a batch of ``replicas`` copies of ``R0``
     CFG-interleaved rows (row t * R0 + r = replica t of row r) reads.  ``shared``: the negative prompt is batch-constant and shared, so every odd
@@ -495,15 +504,18 @@ class Engine:
     def decode_image_tokens(self, T: Optional[int] = None, cfg_weight: float = 5.0, temperature: float = 0.0,
                             seed: int = 0, force_tokens: Optional[torch.Tensor] = None,
                             force_mask: Optional[torch.Tensor] = None, return_logits: bool = False,
-                            top_k: int = 0, top_p: float = 1.0, return_logprobs: bool = False):
+                            top_k: int = 0, top_p: float = 1.0, return_logprobs: bool = False, return_stats=False):
         """The fused CFG decode loop.  top_k / top_p filter the sampled draws (temperature > 0; HF order temperature ->
         top-k -> top-p); (0, 1.0) is the unfiltered sampler.  return_logprobs: also fp32 [B, T], the log-probability of every emitted
         token under softmax(mixed / temperature) before the filters (``pg_request_token_logprobs``); with ``force_mask = zeros`` it is the
-        log-likelihood of ``force_tokens``.  Semantics: include/plangen_hip.h."""
+        log-likelihood of ``force_tokens``.  return_stats (True, or an int n_alt in 1..8): also (last) the dict of ``_request_stats``
+        over [B, T]: the emitted tokens' entropy, rank and top-n_alt alternatives (``pg_request_token_stats``).  Semantics:
+        include/plangen_hip.h."""
         T = self.cfg.img_tokens if T is None else T
         B = self.R // 2
         out = torch.zeros((B, T), dtype=torch.int32, device=self.device)
         lp = self._request_logprobs((B, T)) if return_logprobs else None
+        stt = self._request_stats((B, T), return_stats) if _wants_stats(return_stats) else None
         ft = self._dev(force_tokens, torch.int32) if force_tokens is not None else None
         fm = self._dev(force_mask, torch.uint8) if force_mask is not None else None
         lg = torch.zeros((T, B, self.cfg.img_vocab), dtype=torch.float32, device=self.device) if return_logits else None
@@ -515,8 +527,8 @@ class Engine:
             self._check(self.lib.pg_decode_image_tokens_filtered(self.h, T, float(cfg_weight), float(temperature), int(top_k),
                                                                  float(top_p), int(seed), self._p(ft), self._p(fm), self._p(out),
                                                                  self._p(lg), self.stream), "pg_decode_image_tokens_filtered")
-        self._keep = [ft, fm, out, lg, lp]
-        res = (out,) + ((lg,) if return_logits else ()) + ((lp,) if return_logprobs else ())
+        self._keep = [ft, fm, out, lg, lp, stt]
+        res = (out,) + ((lg,) if return_logits else ()) + ((lp,) if return_logprobs else ()) + ((stt,) if stt is not None else ())
         return res if len(res) > 1 else res[0]
 
     def _request_logprobs(self, shape) -> torch.Tensor:
@@ -524,6 +536,41 @@ class Engine:
         lp = torch.full(shape, float("nan"), dtype=torch.float32, device=self.device)
         self._check(self.lib.pg_request_token_logprobs(self.h, self._p(lp), lp.numel()), "pg_request_token_logprobs")
         return lp
+
+    def _stats_buffers(self, shape, n_alt: int):
+        """(dict of result tensors, the pg_token_stats naming them): fp32 NaN / int32 -2 where a call writes nothing."""
+        shape = tuple(shape)
+        d = {"logprob": torch.full(shape, float("nan"), dtype=torch.float32, device=self.device),
+             "entropy": torch.full(shape, float("nan"), dtype=torch.float32, device=self.device),
+             "rank": torch.full(shape, -2, dtype=torch.int32, device=self.device)}
+        if n_alt > 0:
+            d["alt_tok"] = torch.full(shape + (n_alt,), -2, dtype=torch.int32, device=self.device)
+            d["alt_logprob"] = torch.full(shape + (n_alt,), float("nan"), dtype=torch.float32, device=self.device)
+        req = _lib.pg_token_stats(self._p(d["logprob"]), self._p(d["entropy"]), self._p(d["rank"]), self._p(d.get("alt_tok")),
+                                  self._p(d.get("alt_logprob")), n_alt, d["rank"].numel())
+        return d, req
+
+    def _request_stats(self, shape, return_stats) -> dict:
+        """``pg_request_token_stats`` for the next decode / generate call: the dict that call fills -- ``logprob`` fp32, ``entropy`` fp32
+        (nats), ``rank`` int32 (0: the emitted token was the mode) over ``shape``, and with n_alt > 0 ``alt_tok`` int32 / ``alt_logprob``
+        fp32 over ``shape + (n_alt,)`` (-1 / -inf where a row has fewer alternatives)."""
+        d, req = self._stats_buffers(shape, _n_alt(return_stats))
+        self._check(self.lib.pg_request_token_stats(self.h, C.byref(req)), "pg_request_token_stats")
+        return d
+
+    def token_stats(self, x: torch.Tensor, tok: torch.Tensor, temperature: float = 0.0, n_alt: int = 0) -> dict:
+        """``pg_op_token_stats``: the loops' uncertainty reducer over fp32 rows ``x`` [B, V] and tokens ``tok`` [B] -> the dict of
+        ``_request_stats`` over [B]; ``logprob`` has the bits of ``token_logprob``."""
+        x = self._dev(x, torch.float32).reshape(-1, x.shape[-1]).contiguous()
+        B, V = x.shape
+        t = self._dev(torch.as_tensor(tok), torch.int32).reshape(-1).contiguous()
+        if t.numel() != B:
+            raise PlanGenError(f"token_stats: {t.numel()} tokens for {B} rows")
+        d, req = self._stats_buffers((B,), int(n_alt))
+        self._check(self.lib.pg_op_token_stats(self.h, self._p(x), B, V, self._p(t), float(temperature), C.byref(req), self.stream),
+                    "pg_op_token_stats")
+        self._keep = [x, t, d]
+        return d
 
     def token_logprob(self, x: torch.Tensor, tok: torch.Tensor, temperature: float = 0.0) -> torch.Tensor:
         """``pg_op_token_logprob``: the loops' scoring kernel over fp32 rows ``x`` [B, V] and tokens ``tok`` [B] -> fp32 [B],
@@ -686,23 +733,25 @@ class Engine:
         return self.score_image_tokens(hid, codes.reshape(-1), cond, uncond, cfg_weight, temperature).view(B, T)
 
     def generate_text(self, max_new_tokens: int, eos_id: int, min_new_tokens: int = 0, temperature: float = 0.0, top_k: int = 0,
-                      top_p: float = 1.0, seed: int = 0, return_logits: bool = False, return_logprobs: bool = False):
+                      top_p: float = 1.0, seed: int = 0, return_logits: bool = False, return_logprobs: bool = False, return_stats=False):
         """The text decode loop after a ``prefill*(position_mode=1)``: new tokens only, int64 [R, n <= max_new_tokens], finished rows
         padded with eos.  temperature <= 0: greedy (``generate_text_greedy``, bit for bit).  temperature > 0: sampled in HF's order
         (min_new EOS suppression -> temperature -> top-k -> top-p -> draw), keyed on (seed, row + the ``rng_image_offset`` option, step):
         a row's tokens do not depend on the other rows, and two rows that carry the same prompt draw different texts.
         return_logits: also fp32 [n, R, vocab], the logits every emitted token was drawn from.  return_logprobs: also fp32 [R, n], every
-        emitted token's log-probability (0.0 once a row has finished, so a row's sum is its sequence log-probability).  Semantics:
-        include/plangen_hip.h."""
+        emitted token's log-probability (0.0 once a row has finished, so a row's sum is its sequence log-probability).  return_stats
+        (True, or an int n_alt): also (last) the ``_request_stats`` dict over [R, n].  Semantics: include/plangen_hip.h."""
         out = torch.full((self.R, max_new_tokens), eos_id, dtype=torch.int64, device=self.device)
         lg = torch.zeros((max_new_tokens, self.R, self.cfg.vocab), dtype=torch.float32, device=self.device) if return_logits else None
         lp = self._request_logprobs((self.R, max_new_tokens)) if return_logprobs else None
+        stt = self._request_stats((self.R, max_new_tokens), return_stats) if _wants_stats(return_stats) else None
         n = C.c_int(0)
         self._check(self.lib.pg_generate_text_sampled(self.h, max_new_tokens, min_new_tokens, eos_id, float(temperature), int(top_k),
                                                       float(top_p), int(seed), self._p(out), C.byref(n), self._p(lg), self.stream),
                     "pg_generate_text_sampled")
-        self._keep = [out, lg, lp]
-        res = (out[:, :n.value],) + ((lg[:n.value],) if return_logits else ()) + ((lp[:, :n.value],) if return_logprobs else ())
+        self._keep = [out, lg, lp, stt]
+        res = (out[:, :n.value],) + ((lg[:n.value],) if return_logits else ()) + ((lp[:, :n.value],) if return_logprobs else ()) \
+            + (({k: v[:, :n.value] for k, v in stt.items()},) if stt is not None else ())
         return res if len(res) > 1 else res[0]
 
     def set_text_dfa(self, dfa) -> None:
@@ -726,23 +775,26 @@ class Engine:
         self.uploaded_dfa = dfa
 
     def generate_text_constrained(self, max_new_tokens: int, eos_id: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
-                                  seed: int = 0, return_logits: bool = False, return_state: bool = False, return_logprobs: bool = False):
+                                  seed: int = 0, return_logits: bool = False, return_state: bool = False, return_logprobs: bool = False,
+                                  return_stats=False):
         """``generate_text`` under the automaton of ``set_text_dfa``: disallowed tokens are -inf before temperature / top-k / top-p, a row
         only moves to states it can still finish from, so every row ends with eos inside ``max_new_tokens`` (needs dist[start] <=
         max_new_tokens).  return_logits: also the masked rows fp32 [n, R, vocab]; return_state: also the final states int32 [R];
         return_logprobs: also (last) fp32 [R, n], every emitted token's log-probability over the ALLOWED tokens (0.0 once a row has
-        finished).  Semantics: include/plangen_hip.h."""
+        finished); return_stats (True, or an int n_alt): also (after it) the ``_request_stats`` dict over [R, n], masked tokens never
+        among the alternatives.  Semantics: include/plangen_hip.h."""
         out = torch.full((self.R, max_new_tokens), eos_id, dtype=torch.int64, device=self.device)
         lg = torch.zeros((max_new_tokens, self.R, self.cfg.vocab), dtype=torch.float32, device=self.device) if return_logits else None
         st = torch.full((self.R,), -1, dtype=torch.int32, device=self.device) if return_state else None
         lp = self._request_logprobs((self.R, max_new_tokens)) if return_logprobs else None
+        stt = self._request_stats((self.R, max_new_tokens), return_stats) if _wants_stats(return_stats) else None
         n = C.c_int(0)
         self._check(self.lib.pg_generate_text_constrained(self.h, max_new_tokens, eos_id, float(temperature), int(top_k), float(top_p),
                                                           int(seed), self._p(out), C.byref(n), self._p(st), self._p(lg), self.stream),
                     "pg_generate_text_constrained")
-        self._keep = [out, lg, st, lp]
+        self._keep = [out, lg, st, lp, stt]
         res = (out[:, :n.value],) + ((lg[:n.value],) if return_logits else ()) + ((st,) if return_state else ()) \
-            + ((lp[:, :n.value],) if return_logprobs else ())
+            + ((lp[:, :n.value],) if return_logprobs else ()) + (({k: v[:, :n.value] for k, v in stt.items()},) if stt is not None else ())
         return res if len(res) > 1 else res[0]
 
     def generate_text_greedy(self, max_new_tokens: int, eos_id: int, min_new_tokens: int = 0) -> torch.Tensor:

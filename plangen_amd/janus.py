@@ -106,14 +106,16 @@ class _LanguageModel:
                  pad_token_id: Optional[int] = None, bos_token_id: Optional[int] = None,
                  eos_token_id: Optional[int] = None, max_new_tokens: int = 512, do_sample: bool = False,
                  use_cache: bool = True, min_new_tokens: int = 0, temperature: float = 1.0, top_k: int = 0,
-                 top_p: float = 1.0, seed: int = 0, dfa=None, return_logprobs: bool = False, **kw) -> torch.Tensor:
+                 top_p: float = 1.0, seed: int = 0, dfa=None, return_logprobs: bool = False, return_stats=False, **kw) -> torch.Tensor:
         """HF GenerationMixin.generate (System.x2t, plangen_base.py:513-523): returns the NEW tokens only, int64
         [B, n<=max_new_tokens], finished rows padded with eos.  do_sample=False (the reference's call) is greedy and
         ignores temperature / top_k / top_p like HF; do_sample=True draws with them (temperature -> top-k -> top-p,
         0 / 1.0 = filter off) from the engine's counter RNG keyed on (``seed``, row, step) -- not torch's generator.
         ``dfa`` (a ``grammar.TokenDFA``): the same decode with every step's logits masked by the automaton (HF's logits-processor slot);
         min_new_tokens does not apply there, the automaton says where EOS may stand.
-        ``return_logprobs`` (HF's output_scores + compute_transition_scores): returns (tokens, fp32 [B, n] log-probabilities of the emitted tokens)."""
+        ``return_logprobs`` (HF's output_scores + compute_transition_scores): returns (tokens, fp32 [B, n] log-probabilities of the emitted tokens).
+        ``return_stats`` (True, or an int n_alt; HF's output_scores reduced on the device): also (last) the dict of
+        ``Engine._request_stats`` over [B, n]: entropy, rank and the top-n_alt alternatives of every emitted token."""
         if do_sample and not temperature > 0:
             raise PlanGenError(f"do_sample=True needs temperature > 0 (got {temperature})")
         if do_sample and top_k is None:
@@ -127,14 +129,16 @@ class _LanguageModel:
         self.eng.prefill_embeds(inputs_embeds, pad, position_mode=1)
         self.model.epoch += 1          # invalidates any sample_image cache token
         lpkw = {"return_logprobs": True} if return_logprobs else {}       # without it: exactly the calls made before scores existed
+        if return_stats is not False and return_stats is not None:
+            lpkw["return_stats"] = return_stats
         if dfa is not None:
             if getattr(self.eng, "uploaded_dfa", None) is not dfa:         # the cached automaton of layout_token_dfa: uploaded once
                 self.eng.set_text_dfa(dfa)
             return self.eng.generate_text_constrained(max_new_tokens, int(eos_token_id), temperature=float(temperature) if do_sample else 0.0,
                                                       top_k=int(top_k or 0), top_p=float(1.0 if top_p is None else top_p), seed=int(seed), **lpkw)
         if not do_sample:
-            if return_logprobs:
-                return self.eng.generate_text(max_new_tokens, int(eos_token_id), min_new_tokens, temperature=0.0, return_logprobs=True)
+            if lpkw:
+                return self.eng.generate_text(max_new_tokens, int(eos_token_id), min_new_tokens, temperature=0.0, **lpkw)
             return self.eng.generate_text_greedy(max_new_tokens, int(eos_token_id), min_new_tokens)
         return self.eng.generate_text(max_new_tokens, int(eos_token_id), min_new_tokens, temperature=float(temperature),
                                       top_k=int(top_k), top_p=float(top_p), seed=int(seed), **lpkw)

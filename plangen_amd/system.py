@@ -62,6 +62,11 @@ def t2i_infer_collate_batch(cond_ids: Sequence[Sequence[int]], neg_ids, pad_id: 
     return ids.int(), mask.int()
 
 
+def _stats_on(v) -> bool:
+    """The ``token_stats`` key / ``return_stats`` argument: False (or None) is off, True is n_alt = 0, an int is n_alt."""
+    return v is not None and v is not False
+
+
 def denorm_pt(pt: torch.Tensor) -> torch.Tensor:
     """src/utils/funcs.py:511."""
     return (pt.clamp(-1, 1) + 1) / 2
@@ -84,6 +89,7 @@ class System:
         self.engine = engine
         self.codec = codec                # tokenizer (plangen_amd.textproc.HFCodec / TagWordCodec); None: ids only
         self.last_generated_tokens = None
+        self.last_token_stats = None      # args.token_stats: the stats dict [B, T] of the last t2i (+ "summary": image_token_stats_summary)
         self.last_selection = None        # select_best: dict(replica int64 [B0], score fp32 [B0], scores fp32 [p, B0]) of the last t2i
         self.vl_gpt = MultiModalityCausalLM(engine)
         self.args = args or SimpleNamespace(seed=cfg.seed, parallel_size=1, cfg_weight=cfg.cfg_weight,
@@ -106,13 +112,15 @@ class System:
                      seed: int = 0, edit_region: Optional[torch.Tensor] = None,
                      gt_labels: Optional[torch.Tensor] = None, force_tokens: Optional[torch.Tensor] = None,
                      n_tokens: Optional[int] = None, return_logits: bool = False, top_k: Optional[int] = None,
-                     top_p: Optional[float] = None, replicas: int = 1, alias: bool = True, return_logprobs: bool = False):
+                     top_p: Optional[float] = None, replicas: int = 1, alias: bool = True, return_logprobs: bool = False,
+                     return_stats=False):
         """The 576-step CFG loop, fused on device (one pg_prefill + one pg_decode_image_tokens).
         tokens int32 [2B, L] CFG-interleaved ids, mask [2B, L+T].  temperature<=0 -> greedy.
         top_k / top_p (default: self.args, else off) filter the sampled draws.
         replicas > 1: ``tokens`` is the UN-replicated batch [2B0, L] and the loop runs on replicas * 2B0 rows (row t * 2B0 + r = replica t of
         row r) with every prompt prefilled once (Engine.prefill_replicated); mask / edit_region / gt_labels / force_tokens are the replicated ones.
-        return_logprobs: the emitted tokens' log-probabilities fp32 [B, T] are appended to what is returned."""
+        return_logprobs: the emitted tokens' log-probabilities fp32 [B, T] are appended to what is returned.
+        return_stats (True, or an int n_alt): the ``Engine._request_stats`` dict over [B, T] is appended (last)."""
         top_k = getattr(self.args, "top_k", 0) if top_k is None else top_k
         top_p = getattr(self.args, "top_p", 1.0) if top_p is None else top_p
         L = tokens.shape[1]
@@ -128,7 +136,25 @@ class System:
         elif force_tokens is not None:
             ft = force_tokens
         lpkw = {"return_logprobs": True} if return_logprobs else {}        # without it: exactly the call made before scores existed
+        if _stats_on(return_stats):
+            lpkw["return_stats"] = return_stats
         return self.engine.decode_image_tokens(n_tokens, cfg_weight, temperature, seed, ft, fm, return_logits, top_k=top_k, top_p=top_p, **lpkw)
+
+    @staticmethod
+    def image_token_stats_summary(stats: dict, forced: Optional[torch.Tensor] = None) -> dict:
+        """Per image, from the [B, T] arrays of a stats request: mean entropy (nats), mean rank of the emitted token and the share of
+        positions where it was the mode.  forced bool [B, T] (teacher forcing: the positions that carry the given image's token): also
+        top1 / top5, the share of the forced positions whose given token ranked 0 / below 5 (null for an image without forced positions)."""
+        ent, rank = stats["entropy"].float(), stats["rank"]
+        s = dict(mean_entropy=ent.mean(1).cpu().tolist(), mean_rank=rank.float().mean(1).cpu().tolist(),
+                 rank0_share=(rank == 0).float().mean(1).cpu().tolist())
+        if forced is not None:
+            f = forced.to(rank.device)
+            n = f.sum(1)
+            for name, k in (("top1", 1), ("top5", 5)):
+                hit = ((rank < k) & f).sum(1)
+                s[name] = [h / c if c else None for h, c in zip(hit.cpu().tolist(), n.cpu().tolist())]
+        return s
 
     @staticmethod
     def select_best_replicas(logprobs: torch.Tensor, p: int, scored: Optional[torch.Tensor] = None):
@@ -207,6 +233,9 @@ class System:
         num_gen = B0 * p
         select = p > 1 and bool(getattr(a, "select_best", False))
         self.last_selection = None
+        want_stats = getattr(a, "token_stats", False)
+        stats_on = _stats_on(want_stats)
+        self.last_token_stats = None
         if p > 1:
             if not share:
                 tokens = torch.cat([tokens] * p)
@@ -219,17 +248,29 @@ class System:
                 force_region = torch.cat([edit_region] + [torch.ones_like(edit_region)] * (p - 1))
         toks = self.sample_image(tokens, mask, cfg_weight, temperature, a.seed,
                                  force_region if gt_labels is not None else None, gt_labels, top_k=top_k, top_p=top_p,
-                                 replicas=p if share else 1, **({"return_logprobs": True} if select else {}))
+                                 replicas=p if share else 1, **({"return_logprobs": True} if select else {}),
+                                 **({"return_stats": want_stats} if stats_on else {}))
+        if stats_on:
+            toks, stats = toks[:-1], toks[-1]
+            toks = toks if select else toks[0]
         if select:
             toks, lp = toks
             scored = (edit_region != 0).reshape(B0, -1) if gt_labels is not None else None
             rows, replica, scores = self.select_best_replicas(lp, p, scored)
             toks = toks.index_select(0, rows)
+            if stats_on:
+                stats = {k: v.index_select(0, rows) for k, v in stats.items()}
             num_gen = B0
             self.last_selection = dict(replica=replica, score=scores.gather(0, replica.view(1, B0))[0], scores=scores)
         dec = self.vl_gpt.gen_vision_model.decode_code(toks.to(dtype=torch.int),
                                                        shape=[num_gen, self.cfg.img_dim, self.cfg.grid, self.cfg.grid])
         self.last_generated_tokens = toks
+        if stats_on:
+            # under teacher forcing the rank at the forced positions (edit_region == 0) of the first replica is the model's accuracy there
+            forced = None
+            if gt_labels is not None and not select:
+                forced = torch.cat([(edit_region == 0).reshape(B0, -1)] + [torch.zeros((B0 * (p - 1), toks.shape[1]), dtype=torch.bool, device=edit_region.device)] * (p > 1))
+            self.last_token_stats = dict(stats, summary=self.image_token_stats_summary(stats, forced))
         mask_image = None
         if a.use_teacher_forcing and edit_region is not None:
             er = edit_region.to(dec.device)
@@ -319,13 +360,22 @@ class System:
                     raise PlanGenError(f"layout_best_of={best_of} x {nb} stage-1 rows = {best_of * nb} rows exceed the engine's max_rows={self.engine.max_rows}")
                 emb = torch.cat([emb] * best_of)
                 attention_mask = torch.cat([attention_mask] * best_of)
+            want_stats = getattr(self.args, "token_stats", False)
             outputs = self.x2t(emb, attention_mask.to(dev), max_new_tokens=max_new_tokens, min_new_tokens=min_new_tokens,
-                               **({} if dfa is None else {"dfa": dfa}), **({} if best_of == 1 else {"return_logprobs": True}))
+                               **({} if dfa is None else {"dfa": dfa}), **({} if best_of == 1 else {"return_logprobs": True}),
+                               **({"return_stats": want_stats} if _stats_on(want_stats) else {}))
+            tstats = None
+            if _stats_on(want_stats):
+                tstats, outputs = outputs[-1], (outputs[:-1] if best_of > 1 else outputs[0])
             if best_of > 1:
                 outputs, lp = outputs
                 rows_best, replica, score = self.select_best_layouts(outputs, lp, best_of, self.cfg.eos_id)
                 outputs = outputs.index_select(0, rows_best)
                 out["pr_layout_replica"], out["pr_layout_score"] = replica, score
+                if tstats is not None:
+                    tstats = {k: v.index_select(0, rows_best) for k, v in tstats.items()}
+            if tstats is not None:
+                out["text_token_stats"] = self.text_token_stats_summary(outputs, tstats, self.cfg.eos_id)
             out["pr_text_ids" if is_mmu else "pr_layout_ids"] = outputs
             rows = outputs.cpu().tolist()
             if self.codec is not None:
@@ -349,6 +399,9 @@ class System:
             cfg_ids, cfg_mask = self._cfg_prompt(batch)
             dec, edit_mask = self.t2i(cfg_ids, cfg_mask, gt_image=batch.get("image"), edit_region=batch.get("edit_region"))
             out["pr_tokens"] = self.last_generated_tokens
+            if self.last_token_stats is not None:
+                out["image_token_stats"] = self.last_token_stats["summary"]
+                out["image_entropy"] = self.last_token_stats["entropy"].view(-1, self.cfg.grid, self.cfg.grid)
             if self.last_selection is not None:
                 out["pr_replica"], out["pr_score"] = self.last_selection["replica"], self.last_selection["score"]
             out["pr_image"] = dec.float()
@@ -376,6 +429,12 @@ class System:
                     extra["gt_layout_logprob"] = out["gt_layout_logprob"]
                 if "gt_image_logprob" in out:
                     extra["gt_image_logprob"] = out["gt_image_logprob"]
+                for k in ("image_token_stats", "text_token_stats"):
+                    if k in out:
+                        extra[k] = out[k]
+                if "image_entropy" in out:
+                    import numpy as np
+                    np.save(os.path.join(gen_path, f"{batch_idx}_entropy.npy"), out["image_entropy"].float().cpu().numpy())
                 json.dump(dict(base_caption=base_caption, gt_grounding=batch.get("gt_grounding"),
                                pr_grounding=pr_grounding if pred_layout else "", **extra), f)
         return out
@@ -491,6 +550,19 @@ class System:
         return dict(sum=sums, mean=[s / n for s, n in zip(sums, n_tok)], n_tokens=n_tok, logprobs=lp)
 
     @staticmethod
+    def text_token_stats_summary(tokens: torch.Tensor, stats: dict, eos_id: int) -> dict:
+        """Per row of a text decode with a stats request: the mean entropy over the row's own tokens (up to and including its EOS) and, with
+        n_alt > 0, the alternatives' ids at each of them."""
+        toks = tokens.cpu()
+        count = [row.index(eos_id) + 1 if eos_id in row else len(row) for row in toks.tolist()]
+        ent = stats["entropy"].float().cpu()
+        s = dict(mean_entropy=[float(ent[i, :c].mean()) if c else 0.0 for i, c in enumerate(count)], n_tokens=count)
+        if "alt_tok" in stats:
+            alt = stats["alt_tok"].cpu()
+            s["alt_tok"] = [alt[i, :c].tolist() for i, c in enumerate(count)]
+        return s
+
+    @staticmethod
     def select_best_layouts(tokens: torch.Tensor, logprobs: torch.Tensor, n: int, eos_id: int):
         """The layout_best_of rule.  tokens int64 [n * B, L] and logprobs fp32 [n * B, L] of one replicated stage-1 batch (row t * B + i =
         draw t of row i).  A row's score = sum of its log-probs (finished columns are 0.0) / the number of scored columns = up to and
@@ -508,7 +580,8 @@ class System:
     @torch.no_grad()
     def x2t(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
             max_new_tokens: int = 512, min_new_tokens: int = 0, temperature: Optional[float] = None,
-            top_k: Optional[int] = None, top_p: Optional[float] = None, dfa=None, return_logprobs: bool = False) -> torch.Tensor:
+            top_k: Optional[int] = None, top_p: Optional[float] = None, dfa=None, return_logprobs: bool = False,
+            return_stats=False) -> torch.Tensor:
         """System.x2t (:513-523): text / layout-token decode.  Greedy like the reference unless ``text_temperature`` > 0 (argument,
         else self.args, else 0): then every row is sampled with ``text_top_k`` / ``text_top_p`` (HF order temperature -> top-k -> top-p)
         from seed = args.seed, the seed t2i uses.  The draw is keyed on the row's index in the batch, so two rows that carry the same
@@ -526,6 +599,8 @@ class System:
             kw["dfa"] = dfa
         if return_logprobs:
             kw["return_logprobs"] = True
+        if _stats_on(return_stats):                        # the stats dict over [B, n] comes back last
+            kw["return_stats"] = return_stats
         return self.vl_gpt.language_model.generate(inputs_embeds=inputs_embeds, attention_mask=attention_mask,
                                                    pad_token_id=self.cfg.eos_id, bos_token_id=None,
                                                    eos_token_id=self.cfg.eos_id, max_new_tokens=max_new_tokens,

@@ -90,6 +90,7 @@ class System(_HotPath):
                                                    layout_grammar=cfg.layout_grammar, select_best=select_best, layout_best_of=layout_best_of,
                                                    score_gt_layout=bool(getattr(args, "score_gt_layout", False)),
                                                    score_gt_image=bool(getattr(args, "score_gt_image", False)),
+                                                   token_stats=getattr(args, "token_stats", False),
                                                    use_teacher_forcing=args.use_teacher_forcing, share_replicas=cfg.share_replicas,
                                                    debug_max_seq_len=args.debug_max_seq_len, janus_hw=args.janus_hw,
                                                    neg_prompt=getattr(args, "neg_prompt", ""),
