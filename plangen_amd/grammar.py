@@ -10,7 +10,9 @@ carries), as ``cut_plan_text`` / ``trans_gr_to_creati`` read it back::
     text   := 1..64 characters, none of "<" ">" or newline
     int    := 1..4 digits
 
-Tags and EOS are atomic symbols: a token spells a tag only if its string IS the tag.  Pure numpy; no GPU.
+Tags and EOS are atomic symbols: a token spells a tag only if its string IS the tag, and a vocabulary in which some tag is no single
+token (tokenizer files the reference's ``add_tokens`` was never applied to: ``HFCodec(special_tokens=True)``) is refused by name.
+Pure numpy; no GPU.
 
 Known limit: the automaton reads each token's OWN string (``codec.token_strings``).  A byte-level piece that is not valid UTF-8 alone
 has no string of its own (HFCodec maps it to None: allowed nowhere), so descriptions that need such pieces (characters split over
@@ -183,6 +185,13 @@ def token_dist(next_state: np.ndarray, accept: Sequence[int], used: np.ndarray) 
 def compile_token_dfa(char_dfa: CharDFA, token_strings: Sequence[Optional[str]], eos_id: int) -> TokenDFA:
     """Run every token's string through ``char_dfa`` from every state; tokens with the same transition column share a class."""
     n, table = char_dfa.n_states, char_dfa.table
+    # a tag is a symbol only as a whole token: over a vocabulary that spells one in pieces (a tokenizer the tags were never added to) every
+    # state behind it is unreachable, and what would come out is an automaton that can never write or close an item
+    have = set(s for i, s in enumerate(token_strings) if i != eos_id)
+    missing = [a for a in char_dfa.atoms if a != EOS and a not in have]
+    if missing:
+        raise ValueError(f"compile_token_dfa: no single token of this vocabulary spells {', '.join(missing)}: add the tags to the tokenizer "
+                         "(HFCodec(special_tokens=True), cfg key use_special_tokens)")
     ident = np.arange(n + 1, dtype=np.int32)
     dead_col = np.full(n + 1, n, np.int32)
     by_string: Dict[Optional[str], bytes] = {}

@@ -67,6 +67,15 @@ def _stats_on(v) -> bool:
     return v is not None and v is not False
 
 
+def check_codec_capacity(codec, vocab: int) -> None:
+    """A tokenizer that knows its length (HFCodec: the files' vocabulary + the added tokens) must fit the embedding table: an id at or
+    past ``vocab`` has no row there.  Refused where the tokenizer meets the model, before any id is embedded."""
+    n = len(codec) if hasattr(codec, "__len__") else None
+    if n is not None and n > int(vocab):
+        raise PlanGenError(f"the tokenizer holds {n} tokens ({getattr(codec, 'n_added', 0)} of them added by use_special_tokens / "
+                           f"use_numhw_tokens) but the model's embedding table has vocab={int(vocab)} rows: ids {int(vocab)}..{n - 1} cannot be embedded")
+
+
 def denorm_pt(pt: torch.Tensor) -> torch.Tensor:
     """src/utils/funcs.py:511."""
     return (pt.clamp(-1, 1) + 1) / 2
@@ -85,6 +94,7 @@ class System:
     """
 
     def __init__(self, cfg: PlanGenConfig, engine: Engine, args: Optional[SimpleNamespace] = None, codec=None):
+        check_codec_capacity(codec, cfg.vocab)
         self.cfg = cfg
         self.engine = engine
         self.codec = codec                # tokenizer (plangen_amd.textproc.HFCodec / TagWordCodec); None: ids only

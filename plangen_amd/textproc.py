@@ -32,6 +32,8 @@ MMU_SYSTEM_PROMPT = ("You are a helpful language and vision assistant. "
                      "and assist the user with a variety of tasks using natural language.")
 PAD_TAG = "<｜▁pad▁｜>"                                # processing_vlm.py:91
 GROUNDING_OPEN, GROUNDING_CLOSE = "<grounding>", "</grounding>"
+LAYOUT_TAGS = (GROUNDING_OPEN, GROUNDING_CLOSE, "<box>", "</box>", "<ref>", "</ref>")            # use_special_tokens, plangen_base.py:110-118, in this order
+NUMHW_TAGS = tuple(f"<{a}{i}>" for i in range(100) for a in "hw")                                # use_numhw_tokens, plangen_base.py:120-127: <h0> <w0> <h1> <w1> ...
 
 
 # ------------------------------------------------------------------------------------------ chat template
@@ -136,15 +138,28 @@ def trans_gr_to_creati(prompt: str) -> Tuple[List[List[float]], List[str]]:
 # ------------------------------------------------------------------------------------------ tokenizers
 class HFCodec:
     """The Janus-Pro tokenizer files (tokenizer.json / tokenizer_config.json / special_tokens_map.json) through
-    ``transformers.AutoTokenizer`` -- the object ``VLChatProcessor.tokenizer`` is (processing_vlm.py:97-125)."""
+    ``transformers.AutoTokenizer`` -- the object ``VLChatProcessor.tokenizer`` is (processing_vlm.py:97-125) -- extended the way
+    ``System.__init__`` extends it before anything is encoded (plangen_base.py:110-127): ``special_tokens`` (cfg key
+    ``use_special_tokens``) appends LAYOUT_TAGS, ``numhw_tokens`` (``use_numhw_tokens``) then NUMHW_TAGS, each as
+    ``AddedToken(special=True)``.  A token the files already hold keeps its id (``add_tokens`` skips it); ``n_added`` is what the two
+    calls returned, the number the reference prints."""
 
-    def __init__(self, path: str):
+    def __init__(self, path: str, special_tokens: bool = False, numhw_tokens: bool = False):
+        from tokenizers import AddedToken
         from transformers import AutoTokenizer
         self.tok = AutoTokenizer.from_pretrained(path)
+        self.n_added = 0
+        if special_tokens:
+            self.n_added += self.tok.add_tokens([AddedToken(t, special=True) for t in LAYOUT_TAGS])
+        if numhw_tokens:
+            self.n_added += self.tok.add_tokens([AddedToken(t, special=True) for t in NUMHW_TAGS])
         self.eos_token_id = self.tok.eos_token_id
         self.bos_token_id = self.tok.bos_token_id
         pad = self.tok.convert_tokens_to_ids(PAD_TAG)
         self.pad_id = pad if pad is not None and pad >= 0 else self.tok.pad_token_id
+
+    def __len__(self) -> int:
+        return len(self.tok)                              # base vocabulary + every added token: one more than the largest id
 
     def encode(self, text: str) -> List[int]:
         return self.tok.encode(text)                      # adds BOS like the reference's tokenizer.encode(prompt)

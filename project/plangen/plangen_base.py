@@ -21,7 +21,7 @@ import torch
 from plangen_amd.config import PlanGenConfig
 from plangen_amd.dist import shard_range, world
 from plangen_amd.engine import Engine, PlanGenError
-from plangen_amd.system import System as _HotPath, denorm_pt
+from plangen_amd.system import System as _HotPath, check_codec_capacity, denorm_pt
 from plangen_amd.textproc import HFCodec, TagWordCodec
 from plangen_amd.weights import latest_checkpoint, load_checkpoint
 
@@ -67,7 +67,11 @@ class System(_HotPath):
         self.synthetic = td.get("data_name") == "synthetic" or bool(getattr(args, "synthetic", False))
         tok_dir = str(args.janus_path) if args.janus_path else ""
         if os.path.exists(os.path.join(tok_dir, "tokenizer.json")) or os.path.exists(os.path.join(tok_dir, "tokenizer.model")):
-            codec = HFCodec(tok_dir)
+            # plangen_base.py:110-127: the tokenizer is extended before anything is encoded
+            codec = HFCodec(tok_dir, special_tokens=bool(getattr(args, "use_special_tokens", False)),
+                            numhw_tokens=bool(getattr(args, "use_numhw_tokens", False)))
+            print(f"\nadd special / hw_num tokens {codec.n_added}")
+            check_codec_capacity(codec, cfg.vocab)          # before the engine exists: no id past the embedding table is ever embedded
             cfg.eos_id, cfg.pad_id = codec.eos_token_id, codec.pad_id
         elif self.synthetic:
             codec = TagWordCodec(cfg.vocab, eos_id=cfg.eos_id, pad_id=cfg.pad_id)

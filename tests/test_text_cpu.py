@@ -194,3 +194,200 @@ def test_hf_codec_on_tokenizer_files(tmp_path):
     ans = c.encode("<ref>a cat</ref><box>[12,40,500,620]</box>")[1:] + [c.eos_token_id] + c.encode("junk")[1:]
     text = c.decode(T.cut_at_eos(ans, c.eos_token_id))
     assert T.trans_gr_to_creati(text) == ([[0.012, 0.04, 0.5, 0.62]], ["a cat"])
+
+
+# ------------------------------------------------------------------------------------------ the reference's tokenizer extension
+# System.__init__ (plangen_base.py:110-127) adds the six layout tags -- and with use_numhw_tokens 200 size tokens -- to the tokenizer before
+# anything is encoded.  The directory of _tiny_hf_tokenizer_dir above already holds the tags (somebody extended it: the idempotence case);
+# the one of tok_fixtures.plain_hf_tokenizer_dir does not, like the files of a checkpoint.  Every comparison below is integer equality with
+# a tokenizer prepared by tok_fixtures.reference_prepared.
+import re
+
+from tok_fixtures import NUMHW_ORDER, SPECIAL_ORDER
+from tok_fixtures import plain_hf_tokenizer_dir as _plain_hf_tokenizer_dir
+from tok_fixtures import reference_prepared as _reference_prepared
+
+GROUNDING = "<grounding><ref>a cat</ref><box>[12,40,500,620]</box><ref>a red dog</ref><box>[0, 7, 999, 1000]</box></grounding>"
+ANSWER = "<ref>a cat</ref><box>[12,40,500,620]</box><ref>the table</ref><box>[1,2,300,400]</box>"
+CAPTIONS = ["a red cat on the table",
+            "look at <ref>the cat</ref> here",                          # a tag directly after a space
+            "line one\n<box>[1,2,3,4]</box>\n</grounding>tail",         # ... after a newline
+            "room 5<ref>x</ref>7</box>8",                               # ... after a digit
+            "<ref></ref><box></box><grounding></grounding>",            # tags back to back
+            "a <reflex> and </boxes> and <refs> stay text, <ref >too",  # a tag's prefix is not the tag
+            "sizes <h3><w12><h99> and <h100>"]                          # numhw tokens, and one past the last
+
+
+@pytest.fixture(scope="module")
+def plain_dir(tmp_path_factory):
+    return _plain_hf_tokenizer_dir(tmp_path_factory.mktemp("plain"))
+
+
+def _prompts(codec):
+    """(prompt, ids as the project builds them, how the reference gets them from ITS tokenizer's encode(prompt))"""
+    out = []
+    for cap in CAPTIONS:
+        p, ids = T.wrap_uni_prompt_ids(codec, cap, GROUNDING)
+        out.append((p, ids, lambda e: e))
+        p, ids = T.wrap_uni_prompt_ids(codec, cap, "<grounding>", in_stage1=True)
+        out.append((p, ids, lambda e: e[:-1]))                                     # plangen_base.py:259-260
+    img = codec.token_id(T.IMAGE_TAG)
+    slots = [codec.token_id(T.IMAGE_START_TAG)] + [img] * 5 + [codec.token_id(T.IMAGE_END_TAG)]
+    for q, a in (("what is on the table?", ""), (CAPTIONS[1], ANSWER)):
+        p, ids, mask = T.wrap_mmu_prompt_ids(codec, q, 5, a)
+        assert sum(mask) == 5
+        out.append((p, ids, lambda e, s=slots, i=img: [t for v in e for t in (s if v == i else [v])]))      # add_image_token, processing_vlm.py:243-248
+    for text in (ANSWER, GROUNDING, ANSWER + "</grounding>"):
+        out.append((text, codec.encode(text), lambda e: e))
+    return out
+
+
+@pytest.mark.parametrize("numhw", [False, True])
+def test_hf_codec_adds_the_tags_at_the_reference_ids(plain_dir, numhw):
+    n = len(_reference_prepared(plain_dir, False, False))
+    o = _reference_prepared(plain_dir, True, numhw)
+    c = T.HFCodec(plain_dir, special_tokens=True, numhw_tokens=numhw)
+    assert [c.token_id(t) for t in SPECIAL_ORDER] == list(range(n, n + 6)) == o.convert_tokens_to_ids(SPECIAL_ORDER)
+    assert len(c.tok) == len(c) == len(o) == n + 6 + 200 * numhw and c.n_added == 6 + 200 * numhw
+    if numhw:
+        assert [c.token_id(t) for t in NUMHW_ORDER] == list(range(n + 6, n + 206)) == o.convert_tokens_to_ids(NUMHW_ORDER)
+        assert (c.token_id("<h0>"), c.token_id("<w0>"), c.token_id("<h1>"), c.token_id("<w99>")) == (n + 6, n + 7, n + 8, n + 205)
+    else:
+        with pytest.raises(KeyError):
+            c.token_id("<h0>")
+    assert (c.eos_token_id, c.bos_token_id, c.pad_id) == (o.eos_token_id, o.bos_token_id, o.convert_tokens_to_ids(T.PAD_TAG))
+    assert c.eos_token_id == c.token_id(T.SEP2) < n and c.pad_id == c.token_id(T.PAD_TAG) < n
+    only = T.HFCodec(plain_dir, numhw_tokens=True)                                   # the second switch alone: the same 200 names right after the files' ids
+    assert [only.token_id(t) for t in NUMHW_ORDER] == list(range(n, n + 200)) and only.n_added == 200
+    assert only.encode(GROUNDING) == _reference_prepared(plain_dir, False, True).encode(GROUNDING)
+
+
+@pytest.mark.parametrize("numhw", [False, True])
+def test_hf_codec_prompt_ids_equal_the_reference_tokenizers(plain_dir, numhw):
+    o = _reference_prepared(plain_dir, True, numhw)
+    c = T.HFCodec(plain_dir, special_tokens=True, numhw_tokens=numhw)
+    tags = SPECIAL_ORDER + (NUMHW_ORDER if numhw else [])
+    seen = 0
+    for prompt, ids, ref in _prompts(c):
+        assert list(ids) == ref(o.encode(prompt)), prompt
+        for t in tags:
+            assert list(ids).count(c.token_id(t)) == prompt.count(t), (prompt, t)              # one id per occurrence, none for <reflex> / </boxes>
+            seen += prompt.count(t)
+    assert seen > 100
+    body = c.encode(CAPTIONS[5])[1:]
+    assert not set(body) & set(c.token_id(t) for t in tags) and c.decode(body) == CAPTIONS[5]
+    assert c.encode(CAPTIONS[6]).count(o.convert_tokens_to_ids("<h3>") if numhw else -1) == int(numhw)
+
+
+def test_hf_codec_round_trip_through_the_added_tokens(plain_dir):
+    c = T.HFCodec(plain_dir, special_tokens=True)
+    for cap in CAPTIONS:
+        p, ids = T.wrap_uni_prompt_ids(c, cap, GROUNDING)
+        assert ids[0] == c.bos_token_id and c.decode(ids[1:]) == p, cap
+        p, ids = T.wrap_uni_prompt_ids(c, cap, "<grounding>", in_stage1=True)
+        assert p.endswith("<grounding>" + T.SEP2) and c.decode(ids[1:]) == p[:-len(T.SEP2)], cap           # stage 1: the EOS tag was dropped
+    for text in (ANSWER, GROUNDING, T.wrap_mmu_prompt_text(CAPTIONS[1], ANSWER)):
+        assert c.decode(c.encode(text)[1:]) == text
+    ans = c.encode(ANSWER)[1:] + [c.eos_token_id] + c.encode("junk <ref>x</ref>")[1:]
+    text = c.decode(T.cut_at_eos(ans, c.eos_token_id))
+    assert text == ANSWER and T.trans_gr_to_creati(text) == ([[0.012, 0.04, 0.5, 0.62], [0.001, 0.002, 0.3, 0.4]], ["a cat", "the table"])
+    lay = c.encode(ANSWER + "</grounding> and more")[1:]
+    assert T.cut_plan_text(c.decode(lay)) == "<grounding>" + ANSWER + "</grounding>"
+
+
+def test_hf_codec_extension_is_idempotent_on_extended_files(tmp_path):
+    d = _tiny_hf_tokenizer_dir(tmp_path)
+    before, c = T.HFCodec(d), T.HFCodec(d, special_tokens=True)
+    n = len(before.tok)
+    assert c.n_added == 0 and len(c.tok) == n == len(_reference_prepared(d, True, False))
+    assert c.tok.convert_ids_to_tokens(list(range(n))) == before.tok.convert_ids_to_tokens(list(range(n)))
+    assert [c.token_id(t) for t in SPECIAL_ORDER] == [before.token_id(t) for t in SPECIAL_ORDER] and max(c.token_id(t) for t in SPECIAL_ORDER) < n
+    o = _reference_prepared(d, True, False)
+    for prompt, ids, ref in _prompts(c):
+        assert list(ids) == ref(before.encode(prompt)) == ref(o.encode(prompt)), prompt
+    both = T.HFCodec(d, special_tokens=True, numhw_tokens=True)                      # the tags stay where they were, the size tokens follow the files' ids
+    assert both.n_added == 200 and [both.token_id(t) for t in NUMHW_ORDER] == list(range(n, n + 200))
+    assert [both.token_id(t) for t in SPECIAL_ORDER] == [before.token_id(t) for t in SPECIAL_ORDER]
+
+
+def test_hf_codec_switches_off_is_the_tokenizer_of_the_files(plain_dir):
+    """The reference with use_special_tokens=False (cfg/base.py:69): nothing is added, the tags are ordinary text."""
+    o = _reference_prepared(plain_dir, False, False)
+    for c in (T.HFCodec(plain_dir), T.HFCodec(plain_dir, special_tokens=False, numhw_tokens=False)):
+        assert c.n_added == 0 and len(c.tok) == len(o)
+        for t in SPECIAL_ORDER + ["<h0>"]:
+            with pytest.raises(KeyError):
+                c.token_id(t)
+            assert len(c.encode(t)) > 2                                               # BOS + several pieces
+        for cap in CAPTIONS:
+            p, ids = T.wrap_uni_prompt_ids(c, cap, GROUNDING)
+            assert ids == o.encode(p) and c.decode(ids[1:]) == p
+        assert len(c.encode(GROUNDING)) > len(T.HFCodec(plain_dir, special_tokens=True).encode(GROUNDING)) + 10
+
+
+def _symbols(text):
+    from plangen_amd import grammar as G
+    return re.findall("|".join(re.escape(t) for t in G.TAGS) + "|.", text, re.S)
+
+
+def test_layout_grammar_over_the_extended_hf_codec(plain_dir):
+    from plangen_amd import grammar as G
+    from text_dfa_ref import accepts_layout
+    vocab = 512
+    o, plain = _reference_prepared(plain_dir, True, False), _reference_prepared(plain_dir, False, False)
+    c = T.HFCodec(plain_dir, special_tokens=True)
+    dfa = G.compile_token_dfa(G.layout_char_dfa(), c.token_strings(vocab), c.eos_token_id)
+    assert dfa.token_class.shape == (vocab,) and (dfa.token_class[len(c):] == 0).all()
+    for tag in G.TAGS:                                                    # every tag: a class of its own that holds this one token
+        k = dfa.token_class[o.convert_tokens_to_ids(tag)]
+        assert k != 0 and (dfa.token_class == k).sum() == 1, tag
+    assert dfa.token_class[c.token_id("<grounding>")] == 0               # the prompt carries it; the layout never repeats it
+    chars = G.layout_char_dfa()
+    for text in (ANSWER + "</grounding>", "</grounding>", GROUNDING[len("<grounding>"):]):
+        assert accepts_layout(text)
+        st = dfa.start_state
+        for t in o.encode(text)[1:] + [o.eos_token_id]:
+            st = dfa.step(st, t)
+            assert st >= 0, (text, t)
+        assert dfa.dist[st] == 0                                          # the accepting state
+        # the files' own tokenizer spells the tags in pieces: the same string, judged by the character-level rules
+        split = plain.encode(text)[1:]
+        assert len(split) > len(o.encode(text)[1:]) and plain.decode(split) == text
+        assert chars.accepts(_symbols(plain.decode(split)) + [G.EOS])
+        assert not chars.accepts(_symbols(plain.decode(split)[:-1]) + [G.EOS])
+    assert G.layout_token_dfa(c, vocab) is G.layout_token_dfa(c, vocab)
+
+
+def test_layout_grammar_refuses_a_vocabulary_without_the_tags(plain_dir):
+    """A tag that is not a single token: an error that names it, not an automaton that can only write the empty layout."""
+    from plangen_amd import grammar as G
+    plain = T.HFCodec(plain_dir)
+    with pytest.raises(ValueError, match=re.escape("<ref>")) as ei:
+        G.layout_token_dfa(plain, 512)
+    assert all(t in str(ei.value) for t in G.TAGS)
+    c = T.HFCodec(plain_dir, special_tokens=True)
+    strings = c.token_strings(512)
+    for tag in G.TAGS:
+        with pytest.raises(ValueError, match=re.escape(tag)) as ei:
+            G.compile_token_dfa(G.layout_char_dfa(), [None if s == tag else s for s in strings], c.eos_token_id)
+        assert [t for t in G.TAGS if t in str(ei.value)] == [tag]
+    with pytest.raises(ValueError, match=re.escape("</box>")):             # the tag's characters in one token's string do not make it the tag
+        G.compile_token_dfa(G.layout_char_dfa(), [s + " " if s == "</box>" else s for s in strings], c.eos_token_id)
+
+
+def test_tokenizer_longer_than_the_embedding_table_is_refused(plain_dir, tiny_cfg):
+    from plangen_amd.engine import PlanGenError
+    from plangen_amd.system import System, check_codec_capacity
+    from project.plangen.plangen_base import System as CliSystem
+    fits, over = T.HFCodec(plain_dir, special_tokens=True), T.HFCodec(plain_dir, special_tokens=True, numhw_tokens=True)
+    assert len(fits) <= tiny_cfg.vocab < len(over)
+    check_codec_capacity(fits, tiny_cfg.vocab)
+    check_codec_capacity(fits, len(fits))                                   # the largest id is len - 1: a table of exactly len rows holds it
+    with pytest.raises(PlanGenError, match=f"{len(fits)}.*vocab={len(fits) - 1}"):
+        check_codec_capacity(fits, len(fits) - 1)
+    with pytest.raises(PlanGenError, match=f"{len(over)}.*vocab={tiny_cfg.vocab}"):
+        System(tiny_cfg, None, codec=over)                                  # refused before the engine is touched
+    a = _cli(janus_path=plain_dir, use_numhw_tokens=True)
+    assert a.use_special_tokens is True                                     # the README configuration's key (h_text_ump+oimsam.py:11)
+    with pytest.raises(PlanGenError, match=f"{len(over)}.*vocab={tiny_cfg.vocab}"):
+        CliSystem(a, None)                                                  # ... and before one is created
