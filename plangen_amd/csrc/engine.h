@@ -93,7 +93,7 @@ struct pg_engine {
     bool allow_partial = false;       // pg_set_option("allow_partial_weights", 1): run with missing tensors (they read as zeros)
 
     // ---- sequence state
-    int R = 0, L = 0, Ntok = 0, slots = 0; bool prefilled = false; int pos_mode = 0;
+    int R = 0, L = 0, slots = 0; bool prefilled = false;
     int n_dec_host = 0;
     std::vector<int> h_len;
     int32_t *d_len = nullptr, *d_pos_off = nullptr, *d_ndec = nullptr, *d_tok_row = nullptr, *d_tok_j = nullptr,

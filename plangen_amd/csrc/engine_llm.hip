@@ -241,7 +241,7 @@ int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtyp
         for (int j = 0; j < len; ++j) { s_row[ntok] = r; s_j[ntok] = j; s_src[ntok] = r * L_ + pad + j; ++ntok; }
         s_last[r] = ntok - 1;
     }
-    R = R_; L = L_; Ntok = ntok; pos_mode = pmode; n_dec_host = 0;
+    R = R_; L = L_; n_dec_host = 0;
     replicas_n = replicas; group_rows = (replicas > 1 && alias == 1) ? R0 : 0;
     {   // longest-first row order for the decode attention launch (private keys per row)
         for (int r = 0; r < R_; ++r) s_ord[r] = r;
