@@ -58,6 +58,20 @@ struct LinW { void* w = nullptr; float* b = nullptr; int out = 0, in = 0; };
 struct VitBlockW { NormW n1, n2; LinW qkv, proj, fc1, fc2; };
 struct VqNet { ConvW conv_in; ResBlockW mid0, mid2; AttnW mid1; std::vector<VqLevel> levels; NormW norm_out; ConvW conv_out; };
 
+// The rows one chain of launches works on: the row-indexed workspaces already offset to its first row, its own split-K slab buffer and step
+// counter, where its rows sit in the KV cache, and the (S, slab) pair its last GEMM left in ``part`` for the kernel that folds the reduction in.
+// A plain value built by pg_engine::view and passed down by reference: nothing it describes is engine state, so nothing has to be put back.
+struct DecodeView {
+    int r0 = 0, rows = 0;             // first row (also the offset into h_len) and row count
+    float* x; void *xn, *qbuf, *obuf, *hbuf, *hfin, *gh_mid; float* part; int32_t *d_len, *d_pos_off, *d_ndec; float* cfg_pv; int* cfg_pi; float* cfg_mix;
+    size_t kv_row_off;                // byte offset of the first row inside a K or V layer block
+    int shared_row;                   // the shared uncond prompt's row (batch row 1), counted from r0
+    const int32_t* row_order;         // longest-first launch order of the decode attention: the whole batch only
+    int S_last = 1; long slab_last = 0;
+};
+// pg_request_token_logprobs / pg_request_token_stats as the decode / generate call they were armed for took them (pg_engine::take_requests)
+struct TokenRequests { float* lp_out; int64_t lp_cap; pg_token_stats ts; bool stats; };
+
 struct pg_engine {
     pg_config cfg{};
     int dev = 0;
@@ -184,7 +198,6 @@ struct pg_engine {
     }
     pg_timing timing{};
     bool have_decode_t = false, have_prefill_t = false, have_vq_t = false;
-    int S_last = 1; long slab_last = 0;
 
     template <typename U> int dalloc(U** p, size_t n_bytes, bool zero = true) {
         void* q = nullptr;
@@ -204,23 +217,35 @@ struct pg_engine {
     // scratch that every layer reuses: prefill runs unchanged on bf16 and kv_quantize_kernel converts the packed tokens after each layer's attention.
     bool kv8 = false; float* kv_scale = nullptr; void* kv_scratch = nullptr;
     size_t kv_layer_slots() const { return (size_t)cfg.max_rows * cfg.n_heads * slots; }
-    void* kc(int layer) const { return kv8 ? kv_scratch : (char*)kv + ((size_t)layer * 2 + 0) * kv_layer_elems() * esz + kv_row_off; }
-    void* vc(int layer) const { return kv8 ? (char*)kv_scratch + kv_layer_elems() * 2 : (char*)kv + ((size_t)layer * 2 + 1) * kv_layer_elems() * esz + kv_row_off; }
+    void* kc(const DecodeView& v, int layer) const { return kv8 ? kv_scratch : (char*)kv + ((size_t)layer * 2 + 0) * kv_layer_elems() * esz + v.kv_row_off; }
+    void* vc(const DecodeView& v, int layer) const { return kv8 ? (char*)kv_scratch + kv_layer_elems() * 2 : (char*)kv + ((size_t)layer * 2 + 1) * kv_layer_elems() * esz + v.kv_row_off; }
     uint8_t* kc8(int layer) const { return (uint8_t*)kv + ((size_t)layer * 2 + 0) * kv_layer_elems(); }
     uint8_t* vc8(int layer) const { return (uint8_t*)kv + ((size_t)layer * 2 + 1) * kv_layer_elems(); }
     float* kvs(int layer) const { return kv_scale + (size_t)layer * 2 * kv_layer_slots(); }
-    int shared_len = 0, shared_row = 1; bool share_uncond = true;
+    int shared_len = 0; bool share_uncond = true;
     int uncond_hint = -1;             // next pg_prefill only: 1 = caller guarantees every odd row carries row 1's ids, 0 = it does not, -1 = probe on the device (one 4-byte read + stream sync)
-    // decode lanes: the batch's rows split into independent chains on separate streams
-    size_t kv_row_off = 0;            // byte offset of the current lane's first row inside a K or V layer block
-    int h_len_off = 0; int lanes_opt = -1;   // -1 auto, 1, 2
+    // decode lanes: the batch's rows split into independent chains on separate streams.  A lane is a DecodeView of its row range -- view(first row,
+    // rows, lane) -- and the whole batch is view(0, R, 0): the workspace pointers above stay the whole-batch bases and are never rebased.  Lane 1
+    // brings its own slab buffer, step counter and stream (part2, d_ndec2, istream2); ev_fork / ev_join tie the two streams together once per step.
+    int lanes_opt = -1;               // -1 auto, 1, 2
     float* part2 = nullptr; hipStream_t istream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int32_t* d_ndec2 = nullptr;
     int32_t* d_row_order = nullptr; bool lpt_order = true; bool order_valid = false; int order_rows = 0;
     // pg_prefill_replicated: the batch is `replicas_n` copies of R / replicas_n distinct rows (row t * R0 + r = replica t of row r); group_rows = R0 while
     // the replicas' prompt slots alias their owner rows (alias = 1), 0 otherwise (plain prefill, alias = 0 after the copy, replicas = 1)
     int group_rows = 0, replicas_n = 1;
-    SeqState seq() const { return SeqState{d_len, d_pos_off, d_ndec, d_tok_row, d_tok_j, shared_len, shared_row, (lpt_order && order_valid && kv_row_off == 0 && R == order_rows) ? d_row_order : nullptr, group_rows}; }
+    DecodeView view(int r0, int rows, int lane) const {
+        const size_t r = (size_t)r0, Hh = H(), HDm = HD();
+        DecodeView v; v.r0 = r0; v.rows = rows;
+        v.x = x + r * Hh; v.xn = (char*)xn + r * Hh * esz; v.qbuf = (char*)qbuf + r * HDm * esz; v.obuf = (char*)obuf + r * HDm * esz;
+        v.hbuf = (char*)hbuf + r * cfg.inter * esz; v.hfin = (char*)hfin + r * Hh * esz; v.gh_mid = (char*)gh_mid + r * cfg.gen_head_dim * esz;
+        v.part = lane ? part2 : part; v.d_len = d_len + r; v.d_pos_off = d_pos_off + r; v.d_ndec = lane ? d_ndec2 : d_ndec;
+        v.cfg_pv = cfg_pv + r * 8; v.cfg_pi = cfg_pi + r * 8; v.cfg_mix = cfg_mix ? cfg_mix + (r / 2) * cfg.img_vocab : nullptr;
+        v.kv_row_off = r * cfg.n_heads * (size_t)slots * 128 * esz; v.shared_row = 1 - r0;
+        v.row_order = (lpt_order && order_valid && r0 == 0 && rows == order_rows) ? d_row_order : nullptr;
+        return v;
+    }
+    SeqState seq(const DecodeView& v) const { return SeqState{v.d_len, v.d_pos_off, v.d_ndec, d_tok_row, d_tok_j, shared_len, v.shared_row, v.row_order, group_rows}; }
 
     int create();
     void add_slot(const std::string& name, void* dst, SlotKind k, long n, int a = 0, int b = 0, int c = 0);
@@ -241,11 +266,17 @@ struct pg_engine {
     // pad_len: [R0] rows; replicas > 1 (pg_prefill_replicated): the batch is R0 * replicas virtual rows of which only the R0 distinct ones are packed
     int prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtype, const int32_t* pad_len, int R0, int L_,
                 int pmode, void* hidden_out, int hidden_dtype, hipStream_t s, int replicas = 1, int alias = 0, bool replicated_api = false);
-    template <typename T> void gemm_residual(hipStream_t s, const T* a, const T* W, int M, int N, int K);
-    template <typename T> void gemm_llm(hipStream_t s, const T* a, const T* W, int M, int N, int K, bool allow_skinny, const void* Wt = nullptr);
-    template <typename T> void run_layers(hipStream_t s, int M, int mode, T* final_out, int32_t* advance = nullptr);
-    template <typename T> void head_logits(hipStream_t s, const T* in, int M);
-    void forward_decode(hipStream_t s);
+    template <typename T> void gemm_residual(hipStream_t s, DecodeView& v, const T* a, const T* W, int M, int N, int K);
+    template <typename T> void gemm_llm(hipStream_t s, DecodeView& v, const T* a, const T* W, int M, int N, int K, bool allow_skinny, const void* Wt = nullptr);
+    template <typename T> void run_layers(hipStream_t s, DecodeView& v, int M, int mode, T* final_out, int32_t* advance = nullptr);
+    template <typename T> void head_logits(hipStream_t s, DecodeView& v, const T* in, int M);
+    void forward_decode(hipStream_t s, DecodeView& v);
+    // what both decode loops share: the one-shot requests, the hop to the engine's own stream and back, the captured step
+    TokenRequests take_requests() { TokenRequests q{lp_req, lp_req_cap, ts_req, ts_pending}; lp_req = nullptr; lp_req_cap = 0; ts_pending = false; return q; }
+    int reserve_requests(const TokenRequests& q);
+    int hop_in(hipStream_t s);
+    int hop_out(hipStream_t ws, hipStream_t s);
+    template <typename F> int graph_step(hipGraphExec_t& exec, std::vector<int64_t>& cached, const std::vector<int64_t>& key, hipStream_t s, F&& record);
     int decode_image(int T, float cfgw, float temp, int top_k, float top_p, uint64_t seed, const int32_t* force_tok,
                      const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s);
     int step(const void* emb, int emb_dtype, void* hidden_out, int hidden_dtype, hipStream_t s);

@@ -227,8 +227,9 @@ int pg_debug_read(pg_handle h, const char* name, int index, void* dst_dev, int64
         launch_kv8_scale_plane((hipStream_t)s, h->kvs(index), nm == "vscale", (float*)dst_dev, cnt);
         return hipGetLastError() == hipSuccess ? PG_OK : PG_ERR_HIP;
     }
-    if (nm == "kcache") { src = h->kv8 ? (void*)h->kc8(index) : h->kc(index); n = (int64_t)h->kv_layer_elems() * (h->kv8 ? 1 : h->esz); }
-    else if (nm == "vcache") { src = h->kv8 ? (void*)h->vc8(index) : h->vc(index); n = (int64_t)h->kv_layer_elems() * (h->kv8 ? 1 : h->esz); }
+    const DecodeView all = h->view(0, h->R, 0);
+    if (nm == "kcache") { src = h->kv8 ? (void*)h->kc8(index) : h->kc(all, index); n = (int64_t)h->kv_layer_elems() * (h->kv8 ? 1 : h->esz); }
+    else if (nm == "vcache") { src = h->kv8 ? (void*)h->vc8(index) : h->vc(all, index); n = (int64_t)h->kv_layer_elems() * (h->kv8 ? 1 : h->esz); }
     else if (nm == "x") { src = h->x; n = (int64_t)h->max_tok * h->H() * 4; }
     else if (nm == "xn") { src = h->xn; n = (int64_t)h->max_tok * h->H() * h->esz; }
     else if (nm == "hfin") { src = h->hfin; n = (int64_t)h->cfg.max_rows * h->H() * h->esz; }

@@ -3,35 +3,35 @@
 #include "engine.h"
 
 // =============================================================================== LLM
-// C = a . W^T into fp32 split-K slabs ``part`` [S_last][M][N].
+// C = a . W^T into the view's fp32 split-K slabs ``part`` [S_last][M][N].
 template <typename T>
-void pg_engine::gemm_llm(hipStream_t s, const T* a, const T* W, int M, int N, int K, bool allow_skinny, const void* Wt) {
-    slab_last = (long)M * N;
+void pg_engine::gemm_llm(hipStream_t s, DecodeView& v, const T* a, const T* W, int M, int N, int K, bool allow_skinny, const void* Wt) {
+    v.slab_last = (long)M * N;
     if constexpr (std::is_same<T, bf16>::value) {
         if (allow_skinny && M <= 512 && K % 128 == 0) {
             const int S = skinny_pick_splits(N, K, M);
             if ((long)S * M * N <= part_elems) {
-                launch_gemm_skinny(s, a, W, part, M, N, K, S, (const bf16*)Wt);
-                S_last = S;
+                launch_gemm_skinny(s, a, W, v.part, M, N, K, S, (const bf16*)Wt);
+                v.S_last = S;
                 return;
             }
         }
     }
     GemmA ga; ga.ptr = a; ga.lda = K;
-    GemmEpi e; e.out = part; e.out_f32 = 1; e.ldc = N;
+    GemmEpi e; e.out = v.part; e.out_f32 = 1; e.ldc = N;
     launch_gemm<T>(s, ga, W, K, 0, e, M, N, K, 1);
-    S_last = 1;
+    v.S_last = 1;
 }
 
 // Prefill form of the two projections that end a residual branch: x[M,N] (fp32 residual stream) += a . W^T in the GEMM's own epilogue
 // (every element is read and written by the same lane), so the norm kernel that follows has no slab to fold in (S_last = 0): it reads x
 // and writes xn only -- 220 MB less traffic per norm at the bench's 13.4 k packed tokens.  Same fp32 sum as the slab form (x + acc), bit for bit.
 template <typename T>
-void pg_engine::gemm_residual(hipStream_t s, const T* a, const T* W, int M, int N, int K) {
+void pg_engine::gemm_residual(hipStream_t s, DecodeView& v, const T* a, const T* W, int M, int N, int K) {
     GemmA ga; ga.ptr = a; ga.lda = K;
-    GemmEpi e; e.out = x; e.out_f32 = 1; e.ldc = N; e.residual = x; e.res_f32 = 1;
+    GemmEpi e; e.out = v.x; e.out_f32 = 1; e.ldc = N; e.residual = v.x; e.res_f32 = 1;
     launch_gemm<T>(s, ga, W, K, 0, e, M, N, K, 1);
-    S_last = 0; slab_last = (long)M * N;
+    v.S_last = 0; v.slab_last = (long)M * N;
 }
 
 // The layer stack on M token rows.  mode 0: decode (row m = batch row, slot len+n_dec);
@@ -39,7 +39,7 @@ void pg_engine::gemm_residual(hipStream_t s, const T* a, const T* W, int M, int 
 // RMSNorm written to final_out (T).  Every GEMM leaves fp32 split-K slabs in ``part``; the
 // next elementwise kernel folds the reduction in (deterministic, no atomics).
 template <typename T>
-void pg_engine::run_layers(hipStream_t s, int M, int mode, T* final_out, int32_t* advance) {
+void pg_engine::run_layers(hipStream_t s, DecodeView& v, int M, int mode, T* final_out, int32_t* advance) {
     const int Hh = H(), I = cfg.inter, HDm = HD();
     const bool sk = mode == 0;
     int S_pend = 0; long slab_pend = 0;
@@ -61,9 +61,9 @@ void pg_engine::run_layers(hipStream_t s, int M, int mode, T* final_out, int32_t
                 Sq = skinny_pick_splits(3 * HDm, Hh, M);
                 d1 = deferred_norm_ok(M, 3 * HDm, Hh, Sq) && (long)Sq * M * 3 * HDm <= part_elems;
             }
-            if (d1) launch_rmsnorm_defer(s, x, part, S_pend, slab_pend, (const bf16*)ly.ln1, (bf16*)xn, ssq_part, M, Hh);
+            if (d1) launch_rmsnorm_defer(s, v.x, v.part, S_pend, slab_pend, (const bf16*)ly.ln1, (bf16*)v.xn, ssq_part, M, Hh);
         }
-        if (!d1) launch_rmsnorm<T>(s, x, part, S_pend, slab_pend, (const T*)ly.ln1, (T*)xn, M, Hh, cfg.rms_eps);
+        if (!d1) launch_rmsnorm<T>(s, v.x, v.part, S_pend, slab_pend, (const T*)ly.ln1, (T*)v.xn, M, Hh, cfg.rms_eps);
         toc(s, TC_NORM, norm_bytes(S_pend));
         tic(s);
         bool qkv_fused = false;
@@ -71,105 +71,105 @@ void pg_engine::run_layers(hipStream_t s, int M, int mode, T* final_out, int32_t
             // prefill: RoPE(q), RoPE(k) and the KV-cache write in the QKV GEMM's own epilogue when the packed batch is big enough
             // for the 256x256 kernel; smaller batches keep GEMM -> fp32 q|k|v -> rope_kv_kernel on the un-interleaved weights
             if (mode == 1 && prefill_rope_epi && ly.wqkv_p) {
-                GemmA ga; ga.ptr = xn; ga.lda = Hh;
-                GemmEpi ge; ge.act = 3; ge.out = qbuf; ge.out_f32 = 0; ge.ldc = 3 * HDm;
-                ge.rope.qbuf = qbuf; ge.rope.kc = kc(li); ge.rope.vc = vc(li); ge.rope.cos_t = cos_t; ge.rope.sin_t = sin_t;
-                ge.rope.tok_row = d_tok_row; ge.rope.tok_j = d_tok_j; ge.rope.pos_off = d_pos_off;
+                GemmA ga; ga.ptr = v.xn; ga.lda = Hh;
+                GemmEpi ge; ge.act = 3; ge.out = v.qbuf; ge.out_f32 = 0; ge.ldc = 3 * HDm;
+                ge.rope.qbuf = v.qbuf; ge.rope.kc = kc(v, li); ge.rope.vc = vc(v, li); ge.rope.cos_t = cos_t; ge.rope.sin_t = sin_t;
+                ge.rope.tok_row = d_tok_row; ge.rope.tok_j = d_tok_j; ge.rope.pos_off = v.d_pos_off;
                 ge.rope.nh = cfg.n_heads; ge.rope.slots = slots; ge.rope.max_pos = max_pos;
                 qkv_fused = gemm256_try(s, ga, (const bf16*)ly.wqkv_p, Hh, 0, ge, M, 3 * HDm, Hh, 1, 1, 0);
             }
         }
         if constexpr (std::is_same<T, bf16>::value) {
             if (d1) {
-                d1 = launch_gemm_skinny_deferred(s, (const bf16*)xn, (const bf16*)ly.wqkv_t, part, M, 3 * HDm, Hh, Sq, ssq_part, cfg.rms_eps);
-                if (d1) { S_last = Sq; slab_last = (long)M * 3 * HDm; qkv_fused = true; }
-                else launch_rmsnorm<T>(s, x, part, 0, 0, (const T*)ly.ln1, (T*)xn, M, Hh, cfg.rms_eps);   // cannot happen (one predicate); the residual is already updated: normalise it the ordinary way
+                d1 = launch_gemm_skinny_deferred(s, (const bf16*)v.xn, (const bf16*)ly.wqkv_t, v.part, M, 3 * HDm, Hh, Sq, ssq_part, cfg.rms_eps);
+                if (d1) { v.S_last = Sq; v.slab_last = (long)M * 3 * HDm; qkv_fused = true; }
+                else launch_rmsnorm<T>(s, v.x, v.part, 0, 0, (const T*)ly.ln1, (T*)v.xn, M, Hh, cfg.rms_eps);   // cannot happen (one predicate); the residual is already updated: normalise it the ordinary way
             }
         }
-        if (!qkv_fused) gemm_llm<T>(s, (const T*)xn, (const T*)ly.wqkv, M, 3 * HDm, Hh, sk, ly.wqkv_t);
+        if (!qkv_fused) gemm_llm<T>(s, v, (const T*)v.xn, (const T*)ly.wqkv, M, 3 * HDm, Hh, sk, ly.wqkv_t);
         toc(s, TC_QKV, 3.0 * HDm * Hh * wb);
         if (mode == 0 && skip_attn) {
             // nothing: the GEMM + norm phase alone (outputs are garbage by construction)
         } else if (mode == 0 && fuse_rope) {
             tic(s);
             if (kv8)
-                launch_attn_decode_kv8(s, part, S_last, slab_last, (bf16*)obuf, kc8(li), vc8(li), kvs(li), cos_t, sin_t, seq(), M, cfg.n_heads,
+                launch_attn_decode_kv8(s, v.part, v.S_last, v.slab_last, (bf16*)v.obuf, kc8(li), vc8(li), kvs(li), cos_t, sin_t, seq(v), M, cfg.n_heads,
                                        slots, max_pos, scale);
             else
-            launch_attn_decode_fused<T>(s, part, S_last, slab_last, (T*)obuf, (T*)kc(li), (T*)vc(li), cos_t, sin_t, seq(), M,
+            launch_attn_decode_fused<T>(s, v.part, v.S_last, v.slab_last, (T*)v.obuf, (T*)kc(v, li), (T*)vc(v, li), cos_t, sin_t, seq(v), M,
                                         cfg.n_heads, slots, max_pos, scale);
         } else {
             if (!qkv_fused)
-                launch_rope_kv<T>(s, part, S_last, slab_last, (T*)qbuf, (T*)kc(li), (T*)vc(li), cos_t, sin_t, seq(), mode, M,
+                launch_rope_kv<T>(s, v.part, v.S_last, v.slab_last, (T*)v.qbuf, (T*)kc(v, li), (T*)vc(v, li), cos_t, sin_t, seq(v), mode, M,
                                   cfg.n_heads, slots, max_pos);
             tic(s);
             bool done = false;
             if constexpr (std::is_same<T, bf16>::value) {
                 if (mode == 1 && flash_prefill) {
-                    launch_attn_prefill_flash(s, (const bf16*)qbuf, (bf16*)obuf, (const bf16*)kc(li), (const bf16*)vc(li), d_row_off, d_len,
-                                              R, max_len_host, cfg.n_heads, slots, scale);
+                    launch_attn_prefill_flash(s, (const bf16*)v.qbuf, (bf16*)v.obuf, (const bf16*)kc(v, li), (const bf16*)vc(v, li), d_row_off, v.d_len,
+                                              v.rows, max_len_host, cfg.n_heads, slots, scale);
                     done = true;
                 }
             }
             if (!done)
-                launch_attn<T>(s, (const T*)qbuf, (T*)obuf, (const T*)kc(li), (const T*)vc(li), seq(), mode, M, cfg.n_heads, slots, scale);
+                launch_attn<T>(s, (const T*)v.qbuf, (T*)v.obuf, (const T*)kc(v, li), (const T*)vc(v, li), seq(v), mode, M, cfg.n_heads, slots, scale);
             // FP8 KV cache: this layer's K/V of the packed tokens, bf16 scratch -> codes + scales (prefill only: decode never takes this branch)
             if (kv8 && mode == 1)
-                launch_kv_quantize(s, (const bf16*)kc(li), (const bf16*)vc(li), kc8(li), vc8(li), kvs(li), d_tok_row, d_tok_j, M, cfg.n_heads, slots);
+                launch_kv_quantize(s, (const bf16*)kc(v, li), (const bf16*)vc(v, li), kc8(li), vc8(li), kvs(li), d_tok_row, d_tok_j, M, cfg.n_heads, slots);
         }
         if (tc_on && !(mode == 0 && skip_attn)) {
             double keys = shared_len;       // the shared uncond prompt is read from HBM once per launch
-            for (int r = 0; r < R; ++r) {
-                keys += (double)(h_len[h_len_off + r] + n_dec_host + 1) - ((shared_len > 0 && (r & 1)) ? shared_len : 0);
+            for (int r = 0; r < v.rows; ++r) {
+                keys += (double)(h_len[v.r0 + r] + n_dec_host + 1) - ((shared_len > 0 && (r & 1)) ? shared_len : 0);
                 // grouped form: a replica's prompt is its owner's -- counted once, with the owner
-                if (group_rows > 0 && r >= group_rows && !(shared_len > 0 && (r & 1))) keys -= (double)h_len[h_len_off + r];
+                if (group_rows > 0 && r >= group_rows && !(shared_len > 0 && (r & 1))) keys -= (double)h_len[v.r0 + r];
             }
             toc(s, TC_ATTN, keys * cfg.n_heads * 2 * (kv8 ? 128.0 + 4.0 : 128.0 * (double)esz));      // FP8 cache: 128 codes + one fp32 scale per key, K and V
         }
         tic(s);
-        if (!sk && prefill_res_epi) gemm_residual<T>(s, (const T*)obuf, (const T*)ly.wo, M, Hh, HDm);      // prefill: x += o . Wo^T in the GEMM's epilogue
-        else gemm_llm<T>(s, (const T*)obuf, (const T*)ly.wo, M, Hh, HDm, sk, ly.wo_t);
+        if (!sk && prefill_res_epi) gemm_residual<T>(s, v, (const T*)v.obuf, (const T*)ly.wo, M, Hh, HDm);      // prefill: x += o . Wo^T in the GEMM's epilogue
+        else gemm_llm<T>(s, v, (const T*)v.obuf, (const T*)ly.wo, M, Hh, HDm, sk, ly.wo_t);
         toc(s, TC_O, (double)Hh * HDm * wb);
         tic(s);
         if constexpr (std::is_same<T, bf16>::value) {
-            if (sk && defer_norm && Hh == 2048 && S_last > 0 && S_last <= 8 && slab_last <= 0x7fffffffL && ly.wgu_t)
+            if (sk && defer_norm && Hh == 2048 && v.S_last > 0 && v.S_last <= 8 && v.slab_last <= 0x7fffffffL && ly.wgu_t)
                 d2 = deferred_norm_ok(M, 2 * I, Hh, 1) && (force_swiglu || skinny_pick_splits(2 * I, Hh, M) == 1);
-            if (d2) launch_rmsnorm_defer(s, x, part, S_last, slab_last, (const bf16*)ly.ln2, (bf16*)xn, ssq_part, M, Hh);
+            if (d2) launch_rmsnorm_defer(s, v.x, v.part, v.S_last, v.slab_last, (const bf16*)ly.ln2, (bf16*)v.xn, ssq_part, M, Hh);
         }
-        if (!d2) launch_rmsnorm<T>(s, x, part, S_last, slab_last, (const T*)ly.ln2, (T*)xn, M, Hh, cfg.rms_eps);
-        toc(s, TC_NORM, norm_bytes(S_last));
+        if (!d2) launch_rmsnorm<T>(s, v.x, v.part, v.S_last, v.slab_last, (const T*)ly.ln2, (T*)v.xn, M, Hh, cfg.rms_eps);
+        toc(s, TC_NORM, norm_bytes(v.S_last));
         bool fused = false;
         tic(s);
         if constexpr (std::is_same<T, bf16>::value) {
             if (d2) {
-                fused = launch_gemm_skinny_swiglu_deferred(s, (const bf16*)xn, (const bf16*)ly.wgu_t, (bf16*)hbuf, M, 2 * I, Hh, ssq_part, cfg.rms_eps);
-                if (!fused) launch_rmsnorm<T>(s, x, part, 0, 0, (const T*)ly.ln2, (T*)xn, M, Hh, cfg.rms_eps);   // cannot happen (one predicate); see the QKV site
+                fused = launch_gemm_skinny_swiglu_deferred(s, (const bf16*)v.xn, (const bf16*)ly.wgu_t, (bf16*)v.hbuf, M, 2 * I, Hh, ssq_part, cfg.rms_eps);
+                if (!fused) launch_rmsnorm<T>(s, v.x, v.part, 0, 0, (const T*)ly.ln2, (T*)v.xn, M, Hh, cfg.rms_eps);   // cannot happen (one predicate); see the QKV site
             }
             // decode: SwiGLU gate fused into the gate|up GEMM epilogue (S = 1, no slab, no extra kernel)
             if (!fused && sk && M <= 512 && Hh % 128 == 0 && (force_swiglu || skinny_pick_splits(2 * I, Hh, M) == 1))   // fused wins at every M (B=4/8/16: -2..3 % loop time)
-                fused = launch_gemm_skinny_swiglu(s, (const bf16*)xn, (const bf16*)ly.wgu, (bf16*)hbuf, M, 2 * I, Hh, (const bf16*)ly.wgu_t);
+                fused = launch_gemm_skinny_swiglu(s, (const bf16*)v.xn, (const bf16*)ly.wgu, (bf16*)v.hbuf, M, 2 * I, Hh, (const bf16*)ly.wgu_t);
         }
         if constexpr (std::is_same<T, bf16>::value) {
             // prefill: SwiGLU in the 256x256 GEMM's epilogue (h written as bf16, no fp32 gate|up tensor, no extra pass)
             if (!fused && !sk && (I % 4) == 0) {
-                GemmA ga; ga.ptr = xn; ga.lda = Hh;
-                GemmEpi ge; ge.out = hbuf; ge.out_f32 = 0; ge.ldc = I; ge.act = 2;
+                GemmA ga; ga.ptr = v.xn; ga.lda = Hh;
+                GemmEpi ge; ge.out = v.hbuf; ge.out_f32 = 0; ge.ldc = I; ge.act = 2;
                 fused = gemm256_try(s, ga, (const bf16*)ly.wgu, Hh, 0, ge, M, 2 * I, Hh, 1, 1, 0);
             }
         }
         if (!fused) {
-            gemm_llm<T>(s, (const T*)xn, (const T*)ly.wgu, M, 2 * I, Hh, sk, ly.wgu_t);
-            launch_silu_mul<T>(s, part, S_last, slab_last, (T*)hbuf, M, I);
+            gemm_llm<T>(s, v, (const T*)v.xn, (const T*)ly.wgu, M, 2 * I, Hh, sk, ly.wgu_t);
+            launch_silu_mul<T>(s, v.part, v.S_last, v.slab_last, (T*)v.hbuf, M, I);
         }
         toc(s, TC_GU, 2.0 * I * Hh * wb);
         tic(s);
-        if (!sk && prefill_res_epi) gemm_residual<T>(s, (const T*)hbuf, (const T*)ly.wd, M, Hh, I);         // prefill: x += h . Wd^T
-        else gemm_llm<T>(s, (const T*)hbuf, (const T*)ly.wd, M, Hh, I, sk, ly.wd_t);
+        if (!sk && prefill_res_epi) gemm_residual<T>(s, v, (const T*)v.hbuf, (const T*)ly.wd, M, Hh, I);         // prefill: x += h . Wd^T
+        else gemm_llm<T>(s, v, (const T*)v.hbuf, (const T*)ly.wd, M, Hh, I, sk, ly.wd_t);
         toc(s, TC_DOWN, (double)Hh * I * wb);
-        S_pend = S_last; slab_pend = slab_last;
+        S_pend = v.S_last; slab_pend = v.slab_last;
     }
     tic(s);
-    launch_rmsnorm<T>(s, x, part, S_pend, slab_pend, (const T*)norm_w, final_out, M, Hh, cfg.rms_eps, advance);
+    launch_rmsnorm<T>(s, v.x, v.part, S_pend, slab_pend, (const T*)norm_w, final_out, M, Hh, cfg.rms_eps, advance);
     toc(s, TC_NORM, norm_bytes(S_pend));
     tc_on = false;
 }
@@ -269,7 +269,8 @@ int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtyp
     HIPCHK(hipMemsetAsync(d_ndec2, 0, 64, s));
     if (ids_dev) launch_embed_gather(s, embed, ids_dev, d_tok_src, x, ntok, H(), cfg.vocab);
     else launch_rows_to_f32(s, emb_dev, emb_dtype == PG_BF16, d_tok_src, x, ntok, H());
-    if (bf) run_layers<bf16>(s, ntok, 1, (bf16*)xn); else run_layers<float>(s, ntok, 1, (float*)xn);
+    DecodeView v = view(0, R, 0);
+    if (bf) run_layers<bf16>(s, v, ntok, 1, (bf16*)xn); else run_layers<float>(s, v, ntok, 1, (float*)xn);
     // last real token of every row -> hfin (input of gen_head / lm_head for the first sample)
     launch_copy_rows(s, xn, d_last, hfin, nullptr, R, (long)H() * esz);
     if (replicas > 1 && alias == 0) {     // the equality-tested fallback: every replica gets a private copy of its owner's prompt K/V, decode runs today's kernels
@@ -292,24 +293,52 @@ int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtyp
 
 // gen_head: Linear+b -> GELU(erf) -> Linear (second bias folded into the consumer)
 template <typename T>
-void pg_engine::head_logits(hipStream_t s, const T* in, int M) {
+void pg_engine::head_logits(hipStream_t s, DecodeView& v, const T* in, int M) {
     const int Hh = H(), G = cfg.gen_head_dim, V = cfg.img_vocab;
-    gemm_llm<T>(s, in, (const T*)gh_w1, M, G, Hh, true, gh_w1_t);
-    launch_bias_act<T>(s, part, S_last, slab_last, gh_b1, (T*)gh_mid, M, G, 1);
-    gemm_llm<T>(s, (const T*)gh_mid, (const T*)gh_w2, M, V, G, true, gh_w2_t);
+    gemm_llm<T>(s, v, in, (const T*)gh_w1, M, G, Hh, true, gh_w1_t);
+    launch_bias_act<T>(s, v.part, v.S_last, v.slab_last, gh_b1, (T*)v.gh_mid, M, G, 1);
+    gemm_llm<T>(s, v, (const T*)v.gh_mid, (const T*)gh_w2, M, V, G, true, gh_w2_t);
 }
 
-void pg_engine::forward_decode(hipStream_t s) {
-    // the final RMSNorm launch also advances the device step counter
-    if (bf) run_layers<bf16>(s, R, 0, (bf16*)hfin, d_ndec); else run_layers<float>(s, R, 0, (float*)hfin, d_ndec);
+void pg_engine::forward_decode(hipStream_t s, DecodeView& v) {
+    // the final RMSNorm launch also advances the view's device step counter
+    if (bf) run_layers<bf16>(s, v, v.rows, 0, (bf16*)v.hfin, v.d_ndec); else run_layers<float>(s, v, v.rows, 0, (float*)v.hfin, v.d_ndec);
+}
+
+// ---- what the two decode loops share
+int pg_engine::reserve_requests(const TokenRequests& q) {      // the library-owned result buffers, allocated by the first request of each kind
+    if (q.lp_out && !d_logprob) TRY(dalloc(&d_logprob, (size_t)cfg.max_rows * (cfg.max_new + 1) * 4, false));
+    if (q.stats && !d_stats) TRY(dalloc(&d_stats, (size_t)cfg.max_rows * (cfg.max_new + 1) * 19 * 4, false));
+    return PG_OK;
+}
+// graphs cannot be captured on the legacy default stream, and a second lane needs a stream to fork from: hop to istream behind the caller's work ...
+int pg_engine::hop_in(hipStream_t s) { HIPCHK(hipEventRecord(ev_in, s)); HIPCHK(hipStreamWaitEvent(istream, ev_in, 0)); return PG_OK; }
+// ... and put the caller's stream behind ours (nothing to do when the loop ran on the caller's stream)
+int pg_engine::hop_out(hipStream_t ws, hipStream_t s) { if (ws != s) { HIPCHK(hipEventRecord(ev_out, ws)); HIPCHK(hipStreamWaitEvent(s, ev_out, 0)); } return PG_OK; }
+// One replay of the step graph ``exec`` on s.  When ``key`` is not the cached one, record() -- which issues one step on s -- is captured first; a
+// recording that fails ends the capture before its error is returned.
+template <typename F>
+int pg_engine::graph_step(hipGraphExec_t& exec, std::vector<int64_t>& cached, const std::vector<int64_t>& key, hipStream_t s, F&& record) {
+    if (!exec || key != cached) {
+        if (exec) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
+        hipGraph_t g = nullptr;
+        HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        const int rc = record();
+        hipError_t ce = hipStreamEndCapture(s, &g);
+        if (rc != PG_OK) return rc;
+        HIPCHK(ce);
+        HIPCHK(hipGraphInstantiate(&exec, g, nullptr, nullptr, 0));
+        (void)hipGraphDestroy(g);
+        cached = key;
+    }
+    HIPCHK(hipGraphLaunch(exec, s));
+    return PG_OK;
 }
 
 int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_p, uint64_t seed, const int32_t* force_tok,
                             const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s) {
-    float* const lp_out = lp_req; const int64_t lp_cap = lp_req_cap;      // the one-shot log-prob request: consumed whatever this call answers
-    lp_req = nullptr; lp_req_cap = 0;
-    const pg_token_stats ts = ts_req; const bool stats = ts_pending;      // the one-shot stats request: the same
-    ts_pending = false;
+    const TokenRequests q = take_requests();      // the one-shot log-prob and stats requests: consumed whatever this call answers
+    const bool score = q.lp_out != nullptr, stats = q.stats;
     if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(PG_ERR_ARG, "top_k=%d must be >= 0 and top_p=%g in (0, 1]", top_k, (double)top_p);
     if (!prefilled) FAIL(PG_ERR_STATE, "pg_decode_image_tokens before pg_prefill");
     if (kv8 && !fuse_rope) FAIL(PG_ERR_ARG, "the FP8 KV cache needs the fused decode attention (fuse_rope)");
@@ -319,15 +348,13 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     if (R % 2) FAIL(PG_ERR_ARG, "CFG decode needs an even number of rows (got %d)", R);
     if (n_dec_host != 0) FAIL(PG_ERR_STATE, "decode loop needs a fresh prefill");
     if (T < 1 || T - 1 > cfg.max_new) FAIL(PG_ERR_CAPACITY, "T=%d exceeds max_new=%d", T, cfg.max_new);
-    if (lp_out && lp_cap < (int64_t)(R / 2) * T) FAIL(PG_ERR_ARG, "token log-probs: capacity %lld floats is below B * T = %lld", (long long)lp_cap, (long long)(R / 2) * T);
-    if (lp_out && lanes_opt == 2) FAIL(PG_ERR_ARG, "token log-probs do not support lanes = 2");
-    if (stats && ts.capacity < (int64_t)(R / 2) * T) FAIL(PG_ERR_ARG, "token stats: capacity %lld positions is below B * T = %lld", (long long)ts.capacity, (long long)(R / 2) * T);
+    if (score && q.lp_cap < (int64_t)(R / 2) * T) FAIL(PG_ERR_ARG, "token log-probs: capacity %lld floats is below B * T = %lld", (long long)q.lp_cap, (long long)(R / 2) * T);
+    if (score && lanes_opt == 2) FAIL(PG_ERR_ARG, "token log-probs do not support lanes = 2");
+    if (stats && q.ts.capacity < (int64_t)(R / 2) * T) FAIL(PG_ERR_ARG, "token stats: capacity %lld positions is below B * T = %lld", (long long)q.ts.capacity, (long long)(R / 2) * T);
     if (stats && lanes_opt == 2) FAIL(PG_ERR_ARG, "token stats do not support lanes = 2");
     HIPCHK(hipSetDevice(dev));
-    const int Rtot = R, B = R / 2;
-    const bool score = lp_out != nullptr;
-    if (score && !d_logprob) TRY(dalloc(&d_logprob, (size_t)cfg.max_rows * (cfg.max_new + 1) * 4, false));
-    if (stats && !d_stats) TRY(dalloc(&d_stats, (size_t)cfg.max_rows * (cfg.max_new + 1) * 19 * 4, false));
+    const int B = R / 2;
+    TRY(reserve_requests(q));
     const bool stored = score || stats;                                   // the step also leaves the row the draw is made from in the row workspace
     // Lanes: at large batch the rows are split into two independent chains on two streams so one
     // half's latency-bound GEMM / norm kernels overlap the other half's bandwidth-bound attention.
@@ -335,7 +362,7 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     // Measured on MI355X at B=64: two lanes are 6 % SLOWER (kernels of both streams each fill the chip, the
     // weights are read twice) -> one lane unless asked for (pg_set_option "lanes").
     int nl = lanes_opt > 0 ? lanes_opt : 1;
-    if (Rtot % 4 || (long)decode_part_elems <= 0) nl = 1;
+    if (R % 4 || (long)decode_part_elems <= 0) nl = 1;
     const bool graph = use_graph && !time_attn && T > 2;
     // top-k / top-p only act on sampled draws (greedy ignores them, as HF's warpers do)
     const bool filtered = temp > 0.f && (top_k > 0 || top_p < 1.f);
@@ -343,56 +370,34 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
         if (cfg.img_vocab > SEL_MAXV) FAIL(PG_ERR_CAPACITY, "top-k / top-p sampler supports img_vocab <= %d (got %d)", SEL_MAXV, cfg.img_vocab);
     }
     if ((filtered || stored) && !cfg_mix) TRY(dalloc(&cfg_mix, (size_t)(cfg.max_rows / 2) * cfg.img_vocab * 4, false));
-    struct LaneDef { int r0, nrows; float* part; int32_t* ndec; };
-    LaneDef ld[2];
-    ld[0] = {0, nl == 2 ? Rtot / 2 : Rtot, part, d_ndec};
-    ld[1] = {Rtot / 2, Rtot / 2, part2, d_ndec2};
-    // saved whole-batch views (a lane = pointer rebasing of the row-indexed buffers)
-    float* const x0 = x; void* const xn0 = xn; void* const q0 = qbuf; void* const o0 = obuf; void* const hb0 = hbuf;
-    void* const hf0 = hfin; void* const gm0 = gh_mid; float* const p0 = part; int32_t* const len0 = d_len;
-    int32_t* const po0 = d_pos_off; int32_t* const nd0 = d_ndec; float* const pv0 = cfg_pv; int* const pi0 = cfg_pi; float* const mx0 = cfg_mix;
-    const int Hh = H(), HDm = HD(), G = cfg.gen_head_dim, I = cfg.inter;
-    auto enter = [&](const LaneDef& L) {
-        const size_t r = (size_t)L.r0;
-        x = x0 + r * Hh; xn = (char*)xn0 + r * Hh * esz; qbuf = (char*)q0 + r * HDm * esz; obuf = (char*)o0 + r * HDm * esz;
-        hbuf = (char*)hb0 + r * I * esz; hfin = (char*)hf0 + r * Hh * esz; gh_mid = (char*)gm0 + r * G * esz;
-        part = L.part; d_len = len0 + r; d_pos_off = po0 + r; d_ndec = L.ndec; cfg_pv = pv0 + r * 8; cfg_pi = pi0 + r * 8;
-        if (mx0) cfg_mix = mx0 + (r / 2) * cfg.img_vocab;
-        kv_row_off = r * cfg.n_heads * (size_t)slots * 128 * esz; shared_row = 1 - L.r0; h_len_off = L.r0; R = L.nrows;
-    };
-    auto leave = [&]() {
-        x = x0; xn = xn0; qbuf = q0; obuf = o0; hbuf = hb0; hfin = hf0; gh_mid = gm0; part = p0; d_len = len0; d_pos_off = po0;
-        d_ndec = nd0; cfg_pv = pv0; cfg_pi = pi0; cfg_mix = mx0; kv_row_off = 0; shared_row = 1; h_len_off = 0; R = Rtot;
-    };
+    // a lane is a view of its row range, built once: the loop writes no engine member (a second view is built, and unused, with one lane)
+    DecodeView lane[2] = {view(0, nl == 2 ? R / 2 : R, 0), view(R / 2, R / 2, 1)};
+    const int Hh = H(), G = cfg.gen_head_dim;
     if (force_mask && !force_tok) FAIL(PG_ERR_ARG, "force_mask needs force_tok");
     SampleArgs sa{};
     sa.bias = gh_b2; sa.V = cfg.img_vocab; sa.p = d_sparams;
     sa.force_tok = d_force_tok; sa.force_mask = d_force_mask; sa.out_tok = d_out_tok; sa.logits_out = logits_out;
     sa.embed_table = gen_table; sa.H = Hh; sa.B_total = B;
-    auto sample = [&](hipStream_t st, const LaneDef& L) {
+    auto sample = [&](hipStream_t st, DecodeView& v) {
         tc_on = time_attn && (n_dec_host % (time_stride > 0 ? time_stride : 1)) == 0;
         tic(st);
-        if (bf) head_logits<bf16>(st, (const bf16*)hfin, R); else head_logits<float>(st, (const float*)hfin, R);
+        if (bf) head_logits<bf16>(st, v, (const bf16*)v.hfin, v.rows); else head_logits<float>(st, v, (const float*)v.hfin, v.rows);
         toc(st, TC_HEAD, ((double)G * Hh + (double)cfg.img_vocab * G) * (double)esz);
-        sa.logits_partial = part; sa.S = S_last; sa.slab = slab_last; sa.x = x; sa.n_dec = d_ndec; sa.b_off = L.r0 / 2;
+        sa.logits_partial = v.part; sa.S = v.S_last; sa.slab = v.slab_last; sa.x = v.x; sa.n_dec = v.d_ndec; sa.b_off = v.r0 / 2;
         tic(st);
-        if (filtered) launch_cfg_sample_filtered(st, sa, R / 2, cfg_pv, cfg_pi, cfg_mix);
+        if (filtered) launch_cfg_sample_filtered(st, sa, v.rows / 2, v.cfg_pv, v.cfg_pi, v.cfg_mix);
         else {
-            if (stored) launch_cfg_store(st, sa, R / 2, cfg_mix);    // the filtered route already leaves the mixed rows in cfg_mix
-            launch_cfg_sample(st, sa, R / 2, cfg_pv, cfg_pi);
+            if (stored) launch_cfg_store(st, sa, v.rows / 2, v.cfg_mix);    // the filtered route already leaves the mixed rows in cfg_mix
+            launch_cfg_sample(st, sa, v.rows / 2, v.cfg_pv, v.cfg_pi);
         }
-        if (score) launch_token_logprob_image(st, sa, R / 2, cfg_mix, d_logprob);
-        if (stats) launch_token_stats_image(st, sa, R / 2, cfg_mix, stats_out(ts.n_alt));
-        toc(st, TC_SAMPLE, (double)S_last * R * cfg.img_vocab * 4.0);
+        if (score) launch_token_logprob_image(st, sa, v.rows / 2, v.cfg_mix, d_logprob);
+        if (stats) launch_token_stats_image(st, sa, v.rows / 2, v.cfg_mix, stats_out(q.ts.n_alt));
+        toc(st, TC_SAMPLE, (double)v.S_last * v.rows * cfg.img_vocab * 4.0);
         tc_on = false;
     };
     if (time_attn) { tc_used = 0; tc_meta.clear(); }
     hipStream_t ws = s;
-    if (graph || nl == 2) {      // graphs cannot be captured on the legacy default stream: hop to our own
-        HIPCHK(hipEventRecord(ev_in, s));
-        HIPCHK(hipStreamWaitEvent(istream, ev_in, 0));
-        ws = istream;
-    }
+    if (graph || nl == 2) { TRY(hop_in(s)); ws = istream; }
     // one loop iteration for every lane: sample token i from hfin (step index = n_dec), then
     // (with_forward) run the stack on its embedding (appends KV slot len+n_dec) and advance n_dec.
     // In time_attn mode the lanes run back to back on one stream so the per-launch events are clean.
@@ -401,10 +406,8 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
         if (two_streams) { HIPCHK(hipEventRecord(ev_fork, ws)); HIPCHK(hipStreamWaitEvent(istream2, ev_fork, 0)); }
         for (int li = 0; li < nl; ++li) {
             hipStream_t st = (two_streams && li == 1) ? istream2 : ws;
-            enter(ld[li]);
-            sample(st, ld[li]);
-            if (with_forward) forward_decode(st);
-            leave();
+            sample(st, lane[li]);
+            if (with_forward) forward_decode(st, lane[li]);
         }
         if (two_streams) { HIPCHK(hipEventRecord(ev_join, istream2)); HIPCHK(hipStreamWaitEvent(ws, ev_join, 0)); }
         return PG_OK;
@@ -424,36 +427,21 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     if (graph) {
         // shapes and kernel selection only: seeds, temperatures, T and the caller's buffers reach the kernels through
         // device memory, so a bench / serving loop replays ONE instantiated graph across calls
-        std::vector<int64_t> key = {Rtot, (int64_t)bf, (int64_t)logits_out, (int64_t)shared_len, (int64_t)fuse_rope, (int64_t)nl,
+        std::vector<int64_t> key = {R, (int64_t)bf, (int64_t)logits_out, (int64_t)shared_len, (int64_t)fuse_rope, (int64_t)nl,
                                     (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch, (int64_t)skip_attn, (int64_t)filtered,
                                     (int64_t)group_rows,         // replica geometry: never replay a graph across different aliasing
                                     (int64_t)score,              // the scored step holds two more launches
-                                    (int64_t)(stats ? 1 + ts.n_alt : 0)};        // the stats step one more (and the store, if score did not bring it)
-        if (!gexec || key != gkey) {
-            if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
-            hipGraph_t g = nullptr;
-            HIPCHK(hipStreamBeginCapture(ws, hipStreamCaptureModeThreadLocal));
-            const int rc = iteration(true);
-            hipError_t ce = hipStreamEndCapture(ws, &g);
-            if (rc != PG_OK) return rc;
-            HIPCHK(ce);
-            HIPCHK(hipGraphInstantiate(&gexec, g, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(g);
-            gkey = key;
-        }
-        for (; i < T - 1; ++i) { HIPCHK(hipGraphLaunch(gexec, ws)); n_dec_host++; }
+                                    (int64_t)(stats ? 1 + q.ts.n_alt : 0)};      // the stats step one more (and the store, if score did not bring it)
+        for (; i < T - 1; ++i) { TRY(graph_step(gexec, gkey, key, ws, [&] { return iteration(true); })); n_dec_host++; }
     } else {
         for (; i < T - 1; ++i) { TRY(iteration(true)); n_dec_host++; }
     }
     if (T > 1) TRY(iteration(false));
     HIPCHK(hipMemcpyAsync(out_tok, d_out_tok, (size_t)B * T * 4, hipMemcpyDeviceToDevice, ws));
-    if (score) HIPCHK(hipMemcpyAsync(lp_out, d_logprob, (size_t)B * T * 4, hipMemcpyDeviceToDevice, ws));
-    if (stats) TRY(stats_copy_out(ts, B, T, T, ws));
+    if (score) HIPCHK(hipMemcpyAsync(q.lp_out, d_logprob, (size_t)B * T * 4, hipMemcpyDeviceToDevice, ws));
+    if (stats) TRY(stats_copy_out(q.ts, B, T, T, ws));
     HIPCHK(hipEventRecord(ev_t1, ws));
-    if (ws != s) {
-        HIPCHK(hipEventRecord(ev_out, ws));
-        HIPCHK(hipStreamWaitEvent(s, ev_out, 0));
-    }
+    TRY(hop_out(ws, s));
     have_decode_t = true;
     HIPCHK(hipGetLastError());
     return PG_OK;
@@ -465,8 +453,9 @@ int pg_engine::step(const void* emb, int emb_dtype, void* hidden_out, int hidden
     if (group_rows > 0 && !fuse_rope) FAIL(PG_ERR_ARG, "replicas that alias their owner's prompt need the fused decode attention (fuse_rope)");
     if (n_dec_host + 1 > cfg.max_new) FAIL(PG_ERR_CAPACITY, "decode capacity max_new=%d exhausted", cfg.max_new);
     HIPCHK(hipSetDevice(dev));
-    launch_rows_to_f32(s, emb, emb_dtype == PG_BF16, nullptr, x, R, H());
-    forward_decode(s);
+    DecodeView v = view(0, R, 0);
+    launch_rows_to_f32(s, emb, emb_dtype == PG_BF16, nullptr, v.x, R, H());
+    forward_decode(s, v);
     n_dec_host++;
     if (hidden_out) {
         if (bf) launch_t_to_rows<bf16>(s, (const bf16*)hfin, hidden_out, hidden_dtype == PG_BF16, nullptr, R, H());
@@ -480,16 +469,17 @@ int pg_engine::gen_head(const void* h_dev, int h_dtype, float* logits, int R_, h
     if (!finalized) FAIL(PG_ERR_STATE, "pg_finalize_weights not called");
     if (R_ < 1 || R_ > cfg.max_rows) FAIL(PG_ERR_CAPACITY, "rows %d > max_rows %d", R_, cfg.max_rows);
     HIPCHK(hipSetDevice(dev));
+    DecodeView v = view(0, R_, 0);
     // bring h into the compute dtype
     if (bf) {
         if (h_dtype == PG_BF16) HIPCHK(hipMemcpyAsync(gh_in, h_dev, (size_t)R_ * H() * 2, hipMemcpyDeviceToDevice, s));
         else launch_t_to_rows<float>(s, (const float*)h_dev, gh_in, 1, nullptr, R_, H());
-        head_logits<bf16>(s, (const bf16*)gh_in, R_);
+        head_logits<bf16>(s, v, (const bf16*)gh_in, R_);
     } else {
         launch_rows_to_f32(s, h_dev, h_dtype == PG_BF16, nullptr, (float*)gh_in, R_, H());
-        head_logits<float>(s, (const float*)gh_in, R_);
+        head_logits<float>(s, v, (const float*)gh_in, R_);
     }
-    launch_bias_f32(s, part, S_last, slab_last, gh_b2, logits, R_, cfg.img_vocab);
+    launch_bias_f32(s, v.part, v.S_last, v.slab_last, gh_b2, logits, R_, cfg.img_vocab);
     HIPCHK(hipGetLastError());
     return PG_OK;
 }
@@ -574,7 +564,8 @@ int pg_engine::text_constrain(const float* logits, int B, int V, const int32_t* 
     TextDfaArgs da{};
     da.token_class = d_dfa_class; da.next_state = d_dfa_next; da.dist = d_dfa_dist; da.hdr = d_dfa_hdr;
     da.state = state; da.state_out = next_state; da.keep = keep; da.tok = tok;
-    launch_text_constrained(s, ta, da, B, mode, cfg_pv, cfg_pi, txt_mix);
+    const DecodeView v = view(0, B, 0);
+    launch_text_constrained(s, ta, da, B, mode, v.cfg_pv, v.cfg_pi, txt_mix);
     HIPCHK(hipGetLastError());
     return PG_OK;
 }
@@ -643,11 +634,7 @@ int pg_engine::head_logprob(const char* who, const void* x, int64_t rows, const 
     const long chunk = bf ? 0 : std::min<long>((long)n, std::max<long>(1, (64L << 20) / (4L * V)));
     const long need = bf ? (long)head_logprob_ws_bytes((long)n, V, K) : (((chunk * V * 4 + 255) & ~255L) + chunk * K * 4);
     sh_mid_bytes = 0;
-    if (need > sh_ws_bytes) {
-        if (sh_ws) { HIPCHK(hipFree(sh_ws)); bytes -= sh_ws_bytes; sh_ws = nullptr; sh_ws_bytes = 0; }   // hipFree waits for the work that still reads it
-        HIPCHK(hipMalloc(&sh_ws, (size_t)need));
-        sh_ws_bytes = need; bytes += need;
-    }
+    TRY(sh_reserve(need));
     if (bf) {
         if (!launch_head_logprob(s, (const bf16*)x, (const bf16*)w, row_idx, target, (long)n, V, K, temp, (float*)sh_ws, out)) FAIL(PG_ERR_ARG, "%s: shape not supported (n=%lld V=%d K=%d)", who, (long long)n, V, K);
     } else {
@@ -747,10 +734,8 @@ int pg_engine::score_image_tokens(const void* hidden, int64_t rows, const int32_
 
 int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int top_k, float top_p, uint64_t seed, int64_t* out, int* out_len,
                              float* logits_out, hipStream_t s, bool constrained, int32_t* state_out) {
-    float* const lp_out = lp_req; const int64_t lp_cap = lp_req_cap;      // the one-shot log-prob request: consumed whatever this call answers
-    lp_req = nullptr; lp_req_cap = 0;
-    const pg_token_stats ts = ts_req; const bool stats = ts_pending;      // the one-shot stats request: the same
-    ts_pending = false;
+    const TokenRequests q = take_requests();      // the one-shot log-prob and stats requests: consumed whatever this call answers
+    const bool score = q.lp_out != nullptr, stats = q.stats;
     if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(PG_ERR_ARG, "top_k=%d must be >= 0 and top_p=%g in (0, 1]", top_k, (double)top_p);
     if (!prefilled) FAIL(PG_ERR_STATE, "text decode before pg_prefill");
     if (replicas_n > 1) FAIL(PG_ERR_STATE, "text decode after pg_prefill_replicated (position_mode 0, image sampling only)");
@@ -762,13 +747,11 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
         if (!dfa_set) FAIL(PG_ERR_STATE, "constrained text decode without an automaton (pg_set_text_dfa)");
         if (dfa_dist_start > max_new) FAIL(PG_ERR_ARG, "max_new=%d is below dist[start_state]=%d: no row could finish", max_new, dfa_dist_start);
     }
-    if (lp_out && lp_cap < (int64_t)R * max_new) FAIL(PG_ERR_ARG, "token log-probs: capacity %lld floats is below B * max_new = %lld", (long long)lp_cap, (long long)R * max_new);
-    if (stats && ts.capacity < (int64_t)R * max_new) FAIL(PG_ERR_ARG, "token stats: capacity %lld positions is below B * max_new = %lld", (long long)ts.capacity, (long long)R * max_new);
+    if (score && q.lp_cap < (int64_t)R * max_new) FAIL(PG_ERR_ARG, "token log-probs: capacity %lld floats is below B * max_new = %lld", (long long)q.lp_cap, (long long)R * max_new);
+    if (stats && q.ts.capacity < (int64_t)R * max_new) FAIL(PG_ERR_ARG, "token stats: capacity %lld positions is below B * max_new = %lld", (long long)q.ts.capacity, (long long)R * max_new);
     HIPCHK(hipSetDevice(dev));
     const int B = R;
-    const bool score = lp_out != nullptr;
-    if (score && !d_logprob) TRY(dalloc(&d_logprob, (size_t)cfg.max_rows * (cfg.max_new + 1) * 4, false));
-    if (stats && !d_stats) TRY(dalloc(&d_stats, (size_t)cfg.max_rows * (cfg.max_new + 1) * 19 * 4, false));
+    TRY(reserve_requests(q));
     const bool stored = score || stats;                                   // the step also leaves the row the draw is made from in the row workspace
     // launch structure: greedy argmax (temperature <= 0 ignores the filters, as HF's warpers do) / Gumbel-max folded into the scan /
     // scan -> workspace -> select.  Everything else about sampling is a value in TextParams.
@@ -778,20 +761,17 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
     HIPCHK(hipMemcpyAsync(d_unf, ones.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(d_anyunf, 0, 1024 * 4, s));
     HIPCHK(hipStreamSynchronize(s));
+    DecodeView v = view(0, R, 0);
     TextArgs ta{};
     ta.V = cfg.vocab; ta.p = d_tparams; ta.out = d_text_out; ta.unfinished = d_unf;
-    ta.any_unfinished = d_anyunf; ta.embed_table = embed; ta.x = x; ta.H = H(); ta.n_dec = d_ndec; ta.logits_out = logits_out;
+    ta.any_unfinished = d_anyunf; ta.embed_table = embed; ta.x = v.x; ta.H = H(); ta.n_dec = v.d_ndec; ta.logits_out = logits_out;
     std::vector<int32_t> flags(1024);
     int checked = 0, done_len = -1;
     // one step = lm_head GEMM -> argmax or draw / EOS bookkeeping (device step counter) -> the stack on the new
     // token's embedding.  Like the image loop it is captured once and replayed; every 8th step the
     // any-unfinished flags come back to the host (HF generate stops when every row has emitted EOS).
     hipStream_t ws = s;
-    if (use_graph) {
-        HIPCHK(hipEventRecord(ev_in, s));
-        HIPCHK(hipStreamWaitEvent(istream, ev_in, 0));
-        ws = istream;
-    }
+    if (use_graph) { TRY(hop_in(s)); ws = istream; }
     {
         TextParams tp{}; tp.eos = eos; tp.min_new = min_new; tp.max_new = max_new;
         tp.temperature = temp; tp.top_k = top_k; tp.top_p = top_p; tp.seed = seed; tp.row_off = rng_image_offset;
@@ -804,36 +784,27 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
         launch_text_dfa_reset(ws, d_dfa_state, d_dfa_hdr, B);
     }
     auto iteration = [&](bool with_forward) {
-        if (bf) gemm_llm<bf16>(ws, (const bf16*)hfin, (const bf16*)lm_head, B, cfg.vocab, H(), true, lm_head_t);
-        else gemm_llm<float>(ws, (const float*)hfin, (const float*)lm_head, B, cfg.vocab, H(), true);
-        ta.logits_partial = part; ta.S = S_last; ta.slab = slab_last;
+        if (bf) gemm_llm<bf16>(ws, v, (const bf16*)v.hfin, (const bf16*)lm_head, B, cfg.vocab, H(), true, lm_head_t);
+        else gemm_llm<float>(ws, v, (const float*)v.hfin, (const float*)lm_head, B, cfg.vocab, H(), true);
+        ta.logits_partial = v.part; ta.S = v.S_last; ta.slab = v.slab_last;
         // scored greedy / Gumbel-in-the-scan steps: the row goes to txt_mix first (mode 2 leaves it there anyway); the step's own scan follows
-        if (stored && mode != 2) launch_text_store(ws, ta, constrained ? &da : nullptr, B, cfg_pv, cfg_pi, txt_mix);
-        if (constrained) launch_text_constrained(ws, ta, da, B, mode, cfg_pv, cfg_pi, txt_mix);
-        else if (mode == 2) launch_text_sample_filtered(ws, ta, B, cfg_pv, cfg_pi, txt_mix);
-        else if (mode == 1) launch_text_sample(ws, ta, B, cfg_pv, cfg_pi);
-        else launch_text_argmax(ws, ta, B, cfg_pv, cfg_pi);
+        if (stored && mode != 2) launch_text_store(ws, ta, constrained ? &da : nullptr, B, v.cfg_pv, v.cfg_pi, txt_mix);
+        if (constrained) launch_text_constrained(ws, ta, da, B, mode, v.cfg_pv, v.cfg_pi, txt_mix);
+        else if (mode == 2) launch_text_sample_filtered(ws, ta, B, v.cfg_pv, v.cfg_pi, txt_mix);
+        else if (mode == 1) launch_text_sample(ws, ta, B, v.cfg_pv, v.cfg_pi);
+        else launch_text_argmax(ws, ta, B, v.cfg_pv, v.cfg_pi);
         if (score) launch_token_logprob_text(ws, ta, B, txt_mix, d_logprob);
-        if (stats) launch_token_stats_text(ws, ta, B, txt_mix, stats_out(ts.n_alt));
-        if (with_forward) forward_decode(ws);
+        if (stats) launch_token_stats_text(ws, ta, B, txt_mix, stats_out(q.ts.n_alt));
+        if (with_forward) forward_decode(ws, v);
+        return PG_OK;
     };
     for (int step_i = 0; step_i < max_new; ++step_i) {
         const bool last = step_i == max_new - 1;
         if (use_graph && !last && step_i > 0) {
             // shapes and kernel selection only: temperature, top_k, top_p, seed and the row offset reach the kernels through TextParams
             std::vector<int64_t> key = {R, (int64_t)bf, (int64_t)fuse_rope, (int64_t)shared_len, (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch,
-                                        (int64_t)mode, (int64_t)logits_out, (int64_t)constrained, (int64_t)score, (int64_t)(stats ? 1 + ts.n_alt : 0)};
-            if (!gexec_txt || key != gkey_txt) {
-                if (gexec_txt) { (void)hipGraphExecDestroy(gexec_txt); gexec_txt = nullptr; }
-                hipGraph_t g = nullptr;
-                HIPCHK(hipStreamBeginCapture(ws, hipStreamCaptureModeThreadLocal));
-                iteration(true);
-                HIPCHK(hipStreamEndCapture(ws, &g));
-                HIPCHK(hipGraphInstantiate(&gexec_txt, g, nullptr, nullptr, 0));
-                (void)hipGraphDestroy(g);
-                gkey_txt = key;
-            }
-            HIPCHK(hipGraphLaunch(gexec_txt, ws));
+                                        (int64_t)mode, (int64_t)logits_out, (int64_t)constrained, (int64_t)score, (int64_t)(stats ? 1 + q.ts.n_alt : 0)};
+            TRY(graph_step(gexec_txt, gkey_txt, key, ws, [&] { return iteration(true); }));
         } else {
             iteration(!last);
         }
@@ -849,13 +820,10 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
     if (done_len < 0) done_len = max_new;
     // only the columns this call produced; the caller's buffer keeps its own fill beyond them
     HIPCHK(hipMemcpy2DAsync(out, (size_t)max_new * 8, d_text_out, (size_t)max_new * 8, (size_t)done_len * 8, B, hipMemcpyDeviceToDevice, ws));
-    if (score) HIPCHK(hipMemcpy2DAsync(lp_out, (size_t)max_new * 4, d_logprob, (size_t)max_new * 4, (size_t)done_len * 4, B, hipMemcpyDeviceToDevice, ws));
-    if (stats) TRY(stats_copy_out(ts, B, done_len, max_new, ws));
+    if (score) HIPCHK(hipMemcpy2DAsync(q.lp_out, (size_t)max_new * 4, d_logprob, (size_t)max_new * 4, (size_t)done_len * 4, B, hipMemcpyDeviceToDevice, ws));
+    if (stats) TRY(stats_copy_out(q.ts, B, done_len, max_new, ws));
     if (constrained && state_out) HIPCHK(hipMemcpyAsync(state_out, d_dfa_state, (size_t)B * 4, hipMemcpyDeviceToDevice, ws));
-    if (ws != s) {
-        HIPCHK(hipEventRecord(ev_out, ws));
-        HIPCHK(hipStreamWaitEvent(s, ev_out, 0));
-    }
+    TRY(hop_out(ws, s));
     if (out_len) *out_len = done_len;
     HIPCHK(hipGetLastError());
     return PG_OK;

@@ -324,6 +324,39 @@ def test_two_decode_lanes_equal_one_lane(tiny_cfg, tiny_weights, ocfg):
     assert torch.equal(samp[0], samp[1])
 
 
+@pytest.mark.parametrize("dtype,esz", [("f32", 4), ("bf16", 2)])
+def test_two_lanes_count_the_same_attention_bytes(tiny_cfg, tiny_weights, dtype, esz):
+    """The timed pass's attention byte count reads the host lengths of the rows a launch works on: a second lane must read ITS rows'
+    lengths.  R = 8 with eight different prompt lengths (no shared negative prompt, which is counted once per launch), T = 4 greedy:
+    lanes = 2 counts the bytes of lanes = 1 -- the sum over steps, layers and rows of (len + n_dec + 1) keys of n_heads * 2 * 128
+    elements, integers held in doubles, so exact -- in twice the launches, and draws the same tokens."""
+    lens, T = (9, 5, 30, 6, 2, 7, 14, 11), 4
+    L = max(lens)
+    g = torch.Generator().manual_seed(43)
+    ids = torch.full((len(lens), L), tiny_cfg.pad_id, dtype=torch.long)
+    for r, n in enumerate(lens):
+        ids[r, L - n:] = torch.randint(8, tiny_cfg.vocab, (n,), generator=g)
+    expect = sum((n + n_dec + 1) * tiny_cfg.n_heads * 2 * 128 * esz for n_dec in range(T - 1) for _ in range(tiny_cfg.n_layers) for n in lens)
+    e = get_engine(tiny_cfg, tiny_weights, dtype)
+    runs = []
+    e.set_option("time_attn", 1)
+    e.set_option("time_stride", 1)
+    try:
+        for lanes in (1, 2):
+            e.set_option("lanes", lanes)
+            e.prefill(ids, [L - n for n in lens], position_mode=0)
+            tok = e.decode_image_tokens(T=T, cfg_weight=5.0, temperature=0.0).cpu()
+            runs.append((tok, e.timing()))
+    finally:
+        e.set_option("lanes", -1)
+        e.set_option("time_attn", 0)
+    (tok1, t1), (tok2, t2) = runs
+    print(dtype, "attn_bytes_sum", t1["attn_bytes_sum"], t2["attn_bytes_sum"], "expected", expect, "launches", t1["attn_launches"], t2["attn_launches"])
+    assert t1["attn_bytes_sum"] == t2["attn_bytes_sum"] == expect
+    assert t1["attn_launches"] == (T - 1) * tiny_cfg.n_layers and t2["attn_launches"] == 2 * t1["attn_launches"]
+    assert torch.equal(tok1, tok2)
+
+
 def test_uni_2stage_layout_then_image(tiny_cfg, tiny_weights, ocfg):
     """task_type='uni_2stage' (plangen_base.py:1117-1118): greedy layout tokens, host hand-off, then
     the CFG image loop; both stages bit-exact vs the oracle in fp32."""
