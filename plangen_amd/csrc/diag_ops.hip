@@ -27,6 +27,7 @@ struct LocalTune {                  // the thread's pg_tune points at `t` for th
     ~LocalTune() { pg_tune = saved; }
 };
 constexpr int kMaxGridYZ = 65535;
+bool opt256_ok(int o) { return o == 1 || o == 4 || o == 5 || o == 6 || o == 12 || o == 13 || o == 14; }      // gemm256.hip pick_tile_height: auto, 256 / 224 / 192 rows, + 8 = four phases
 bool to_host(std::vector<int32_t>& dst, const int32_t* src, int n) {
     dst.assign(n > 0 ? n : 0, 0);
     if (n <= 0) return true;
@@ -402,6 +403,7 @@ int pg_diag_op_softmax_rows(int out_bf16, const float* x, void* y, int rows, int
 // out fp32 (out_f32) or T (ldc, strideC), v = acc scale + bias_n[col] + bias_m[row] + residual (fp32 when res_f32, else T; ldr / strideR, 0: as out), act 0 / 1 (erf GELU).
 // engine_bf16 0: gemm_f32_kernel.  form: 0 launch_gemm as the engine calls it, 1 the 128 x 128 kernel (gemm256 = 0), 2 gemm256_try (gn_epilogue256 = gn_hw > 0).
 // gn_hw > 0: GroupNorm partials of the output (pixels per image) -> ws, *nsplit_out, stats as pg_diag_op_conv3x3.
+// gemm256_opt (pg_diag_op_gemm_epi256 only; 1 everywhere else): pg_tune->gemm256 of a form-2 launch.
 }  // extern "C"
 namespace {
 // Output blocks of a two-level batched GEMM: block (b, b2) starts at b strideC + b2 strideC2 and covers M rows of N elements, ldc apart.  Seen on the grid of
@@ -426,9 +428,10 @@ bool blocks_disjoint(int M, int N, long ldc, int batch, int batch2, long strideC
 int gemm_epi_impl(int engine_bf16, int form, const void* A, long lda, long strideA, const void* W, long ldb, long strideB, void* out, int out_f32, long ldc,
                   long strideC, const float* bias_n, const float* bias_m, const void* residual, int res_f32, long ldr, long strideR, float scale, int act,
                   int M, int N, int K, int batch, int batch2, long strideA2, long strideB2, long strideC2, int gn_hw, float* ws, long ws_floats, float* stats,
-                  float eps, int* nsplit_out, pg_stream stream) {
+                  float eps, int* nsplit_out, pg_stream stream, int gemm256_opt = 1) {
     if (!A || !W || !out || !nsplit_out) return PG_ERR_ARG;
     if (form < 0 || form > 2 || (!engine_bf16 && form == 2) || (act != 0 && act != 1)) return PG_ERR_ARG;
+    if (gemm256_opt != 1 && (form != 2 || gn_hw || !opt256_ok(gemm256_opt))) return PG_ERR_ARG;       // a pinned tile height / phase count names gemm256_try's plain launch
     if (M < 1 || N < 1 || K < 1 || batch < 1 || batch > kMaxGridYZ || lda < K || ldb < K || ldc < N || strideA < 0 || strideB < 0 || strideC < 0) return PG_ERR_ARG;
     if (batch2 < 1 || (long)batch * batch2 > kMaxGridYZ || strideA2 < 0 || strideB2 < 0 || strideC2 < 0) return PG_ERR_ARG;      // gemm_f32_kernel: grid z = batch x batch2
     if (batch2 == 1) {
@@ -449,7 +452,7 @@ int gemm_epi_impl(int engine_bf16, int form, const void* A, long lda, long strid
         if (ws_floats < (long)(M / gn_hw) * ((gn_hw + 63) / 64) * 64) return PG_ERR_ARG;
     }
     LocalTune lt;
-    lt.t.gemm256 = form == 1 ? 0 : 1;
+    lt.t.gemm256 = form == 1 ? 0 : gemm256_opt;
     lt.t.gn_epilogue256 = form == 2 && gn_hw ? 1 : 0;
     const hipStream_t s = (hipStream_t)stream;
     GemmA a; a.ptr = A; a.lda = lda; a.strideA = strideA; a.strideA2 = strideA2;
@@ -474,6 +477,15 @@ int pg_diag_op_gemm_epi(int engine_bf16, int form, const void* A, long lda, long
                         int M, int N, int K, int batch, int gn_hw, float* ws, long ws_floats, float* stats, float eps, int* nsplit_out, pg_stream stream) {
     return gemm_epi_impl(engine_bf16, form, A, lda, strideA, W, ldb, strideB, out, out_f32, ldc, strideC, bias_n, bias_m, residual, res_f32, ldr, strideR, scale, act,
                          M, N, K, batch, 1, 0, 0, 0, gn_hw, ws, ws_floats, stats, eps, nsplit_out, stream);
+}
+
+// pg_diag_op_gemm_epi, form 2 only, with pg_tune->gemm256 = gemm256_opt (4 / 5 / 6 pin 256 / 224 / 192 rows, + 8 = four phases per K tile; 1 = what
+// pg_diag_op_gemm_epi runs): every instantiation of gemm256_try's plain launch by name (tests/test_gpu_prefill_lin_ops.py).  No GroupNorm partials.
+int pg_diag_op_gemm_epi256(int gemm256_opt, const void* A, long lda, long strideA, const void* W, long ldb, long strideB, void* out, int out_f32, long ldc,
+                           long strideC, const float* bias_n, const float* bias_m, const void* residual, int res_f32, long ldr, long strideR, float scale, int act,
+                           int M, int N, int K, int batch, int* nsplit_out, pg_stream stream) {
+    return gemm_epi_impl(1, 2, A, lda, strideA, W, ldb, strideB, out, out_f32, ldc, strideC, bias_n, bias_m, residual, res_f32, ldr, strideR, scale, act,
+                         M, N, K, batch, 1, 0, 0, 0, 0, nullptr, 0, nullptr, 0.f, nsplit_out, stream, gemm256_opt);
 }
 
 // The decoder's conv_out (Cin -> Cout <= 4), NHWC in -> NCHW out (fp32, or bf16 when out_bf16).  form 1: launch_conv3x3_small<T> (x, w T; engine_bf16 picks T);
@@ -522,7 +534,6 @@ int pg_diag_op_vq_gather(int is_bf16, const void* table, const int32_t* codes, v
 // Every entry point below synchronises the stream before it returns.
 }  // extern "C"
 namespace {
-bool opt256_ok(int o) { return o == 1 || o == 4 || o == 5 || o == 6 || o == 12 || o == 13 || o == 14; }      // gemm256.hip pick_tile_height: auto, 256 / 224 / 192 rows, + 8 = four phases
 bool aligned16(std::initializer_list<const void*> ps) {
     uintptr_t a = 0;
     for (const void* p : ps) a |= (uintptr_t)p;

@@ -20,6 +20,7 @@ _SIGS = {
     "pg_diag_op_gn_stats_raw": [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "pg_diag_op_softmax_rows": [_I, _P, _P, _I, _I, _F, _P],
     "pg_diag_op_gemm_epi": [_I, _I, _P, _L, _L, _P, _L, _L, _P, _I, _L, _L, _P, _P, _P, _I, _L, _L, _F, _I, _I, _I, _I, _I, _I, _P, _L, _P, _F, _P, _P],
+    "pg_diag_op_gemm_epi256": [_I, _P, _L, _L, _P, _L, _L, _P, _I, _L, _L, _P, _P, _P, _I, _L, _L, _F, _I, _I, _I, _I, _I, _P, _P],
     "pg_diag_op_conv_out": [_I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "pg_diag_op_vq_gather": [_I, _P, _P, _P, _I, _I, _I, _P],
 }
@@ -160,10 +161,12 @@ def run_softmax(x, scale, out_kind, dev="cuda"):
 
 
 def run_gemm_epi(A, W, out_kind, M, N, K, batch, lda, strideA, ldb, strideB, ldc, strideC, bias_n=None, bias_m=None, residual=None, res_kind="f32", ldr=0,
-                 strideR=0, scale=1.0, act=0, gn_hw=0, form=1, engine="bf16", dev="cuda", expect=PG_OK, inplace=False):
+                 strideR=0, scale=1.0, act=0, gn_hw=0, form=1, engine="bf16", dev="cuda", expect=PG_OK, inplace=False, opt=None, dev_out=False):
     """A, W: flat or shaped tensors holding the operands in the layout the strides describe.  Returns dict(rc, out [batch, M, N] CPU (rows ldc apart are
-    compacted), nsplit, stats, guards, gaps: the elements between rows / batches (ldc > N) still NaN).  inplace: the fp32 residual [batch, M, N] is laid into the
-    output buffer itself and the kernel is handed ONE pointer as out and residual (pg_engine::lin's x += proj(o)); fp32 output, ldr / strideR as the output's."""
+    compacted), nsplit, stats, guards, gaps: the elements between rows / batches (ldc > N) still NaN, untouched: the whole output still NaN).  inplace: the fp32
+    residual [batch, M, N] is laid into the output buffer itself and the kernel is handed ONE pointer as out and residual (pg_engine::lin's x += proj(o)); fp32
+    output, ldr / strideR as the output's.  opt: form 2 through pg_diag_op_gemm_epi256 with pg_tune->gemm256 = opt (tile height / phase count pinned; no GroupNorm
+    partials).  dev_out: ``out`` stays on the device (a compacted copy).  Operands already on the device in the right type are used where they lie."""
     T = tdt(engine)
     Ad, Wd = A.to(dev, T).contiguous(), W.to(dev, T).contiguous()
     bn = None if bias_n is None else bias_n.to(dev, torch.float32)
@@ -180,16 +183,27 @@ def run_gemm_epi(A, W, out_kind, M, N, K, batch, lda, strideA, ldb, strideB, ldc
     nb = M // gn_hw if gn_hw else 1
     stats = Banded(nb * 64, torch.float32, dev)
     nsp = C.c_int(-7)
-    rc = lib().pg_diag_op_gemm_epi(int(engine == "bf16"), form, _ptr(Ad), lda, strideA, _ptr(Wd), ldb, strideB, _ptr(out.t), int(out_kind == "f32"), ldc, strideC,
-                                   _ptr(bn), _ptr(bm), _ptr(rd), int(res_kind == "f32"), ldr, strideR, scale, act, M, N, K, batch, gn_hw, _ptr(ws.buf), need,
-                                   _ptr(stats.t), 1e-6, C.addressof(nsp), _stream())
+    if opt is None:
+        rc = lib().pg_diag_op_gemm_epi(int(engine == "bf16"), form, _ptr(Ad), lda, strideA, _ptr(Wd), ldb, strideB, _ptr(out.t), int(out_kind == "f32"), ldc, strideC,
+                                       _ptr(bn), _ptr(bm), _ptr(rd), int(res_kind == "f32"), ldr, strideR, scale, act, M, N, K, batch, gn_hw, _ptr(ws.buf), need,
+                                       _ptr(stats.t), 1e-6, C.addressof(nsp), _stream())
+    else:
+        assert form == 2 and engine == "bf16" and not gn_hw
+        rc = lib().pg_diag_op_gemm_epi256(opt, _ptr(Ad), lda, strideA, _ptr(Wd), ldb, strideB, _ptr(out.t), int(out_kind == "f32"), ldc, strideC, _ptr(bn), _ptr(bm),
+                                          _ptr(rd), int(res_kind == "f32"), ldr, strideR, scale, act, M, N, K, batch, C.addressof(nsp), _stream())
     torch.cuda.synchronize()
     assert rc == expect, (rc, expect)
     n = nsp.value
     used = nb * n * 64 if rc == PG_OK and n > 0 else 0
-    o = torch.as_strided(out.t, (batch, M, N), (strideC, ldc, 1)).cpu()
-    return dict(rc=rc, out=o, nsplit=n, stats=stats.t.view(nb, 32, 2).cpu() if used else None,
-                guards=out.intact() and stats.intact() and ws.tail_intact(used) and ws.used_all_written(used))
+    view = torch.as_strided(out.t, (batch, M, N), (strideC, ldc, 1))
+    gaps = True
+    if numel > batch * M * N:
+        own = torch.zeros(numel, dtype=torch.bool, device=dev)
+        torch.as_strided(own, (batch, M, N), (strideC, ldc, 1)).fill_(True)
+        gaps = bool(torch.isnan(out.t[~own].float()).all())
+    return dict(rc=rc, out=view.contiguous() if dev_out else view.cpu(), nsplit=n, stats=stats.t.view(nb, 32, 2).cpu() if used else None,
+                guards=out.intact() and stats.intact() and ws.tail_intact(used) and ws.used_all_written(used), gaps=gaps,
+                untouched=rc != PG_OK and bool(torch.isnan(out.t.float()).all()))
 
 
 def run_conv_out(x, w_oihw, bias, out_kind, form, coef=None, swish=1, engine="bf16", dev="cuda", expect=PG_OK):
