@@ -358,6 +358,44 @@ typedef struct pg_token_stats {
  * decode. */
 int pg_request_token_stats(pg_handle h, const pg_token_stats* req);
 
+/* -- attention mass on prompt spans ------------------------------------------------------------
+ * What output_attentions=True would be reduced to, without the [R, heads, W, W] tensor: for one layer, query column q_i and span s of
+ * row r,
+ *   A[r, i, s] = (1 / n_heads) * sum_h  sum_{k in span(r, s), k <= q_i, k a real token}  softmax_k( scale * Q[r,h,q_i] . K[r,h,k] ),
+ * the softmax over ALL real keys k <= q_i of the row (the prefill attention's causal and left-pad rule: slots 0 .. len[r), slot =
+ * column - pad_len[r]), scale = 1 / sqrt(128), Q / K the RoPE'd bf16 tensors the prefill attention of that layer reads.  The queries
+ * are the n_q columns from q_col0, the same for every row; span(r, s) = [lo, hi) in columns of the padded [R, L] frame.  A query column
+ * inside a row's padding gives zeros; an empty span (hi <= lo) gives zeros; a span that reaches into the padding or past the query
+ * counts only the real keys <= q_i; spans may overlap.  A partition of [0, L) sums to 1 on every real query.
+ * Arithmetic (attn_span.hip): scores by bf16 MFMA with fp32 accumulation, the scale applied to the FP32 score (the attention kernel
+ * itself rounds a pre-scaled Q to bf16: its probabilities differ from these in the last bf16 bits of q), running maximum and sum per
+ * query in fp32 with __expf, the span sum by one more MFMA against the 0/1 span matrix with P split into hi + lo bf16 halves (relative
+ * 2^-17), rescaled when the maximum rises; the head mean is a fixed-order fp32 sum inside one block, so two calls give the same bits.
+ * rows must be the R of the consuming call (the struct carries it because the host arrays are copied when the request is made). */
+typedef struct pg_attn_spans {
+    const int32_t* span_lo_host;  /* [rows * n_spans] columns */
+    const int32_t* span_hi_host;  /* [rows * n_spans] */
+    int32_t rows;                 /* = R of the prefill that serves it */
+    int32_t n_spans;              /* 1..16 */
+    int32_t q_col0, n_q;          /* reported queries: columns [q_col0, q_col0 + n_q) */
+    uint64_t layer_mask;          /* bit l = report layer l; non-zero, within n_layers */
+    float* out_dev;               /* fp32 [popcount(layer_mask)][R][n_q][n_spans], layers ascending */
+    int64_t capacity_floats;
+} pg_attn_spans;
+/* ONE-SHOT in front of the NEXT pg_prefill / pg_prefill_embeds on this handle, like pg_request_token_logprobs: consumed by that call
+ * whatever it answers; req == NULL forgets a pending request.  The host arrays are copied here; out_dev must stay valid until that
+ * call's work on the stream is done.  The serving prefill launches one more kernel (and a memset of the layer's block) after the
+ * attention of every selected layer -- flash or not -- and, with kv_dtype = PG_FP8_E4M3, reads the bf16 scratch K the prefill attention
+ * itself reads, before it is quantised: the FP8 handle returns the bf16 handle's bits.  A shared negative prompt is not shared in that
+ * call (every row keeps its own Q and K).  A prefill without a pending request launches exactly what it launched before.
+ * PG_F32 handles REFUSE the request at the prefill (the kernel is bf16; no fallback).
+ * PG_ERR_ARG, here (nothing pending afterwards): a null pointer, rows outside 1..max_rows, n_spans outside 1..16, q_col0 < 0, n_q < 1,
+ * layer_mask zero or naming a layer >= n_layers, capacity_floats < 1.  At the consuming call, before anything is launched (the
+ * prefill does not happen, nothing stays pending): PG_ERR_ARG when rows != R, q_col0 + n_q > L, a span bound outside [0, L], a
+ * PG_F32 handle, or the call is pg_prefill_replicated (only owner rows are packed there); PG_ERR_CAPACITY when capacity_floats <
+ * popcount(layer_mask) * R * n_q * n_spans. */
+int pg_request_attn_spans(pg_handle h, const pg_attn_spans* req /* NULL: forget it */);
+
 /* -- scoring given text ---------------------------------------------------------------------
  * log softmax(lm_head(hidden))[target] for n chosen rows of a hidden-state tensor, logits never materialised: the evaluation half of
  * pg_request_token_logprobs.  hidden_dev [rows, hidden] in the compute dtype (hidden_dtype must say so) -- typically what pg_prefill /
@@ -604,6 +642,15 @@ int pg_op_cfg_head_logprob(pg_handle h, const void* x_dev, int64_t rows, const v
  * x_dev bf16 [n, 128] -> codes_dev uint8 [n, 128] (e4m3fn), scale_dev fp32 [n] (powers of two).  Works on any handle. */
 int pg_op_kv_quantize(pg_handle h, const void* x_dev /*bf16 [n,128]*/, uint8_t* codes_dev /*[n,128]*/, float* scale_dev /*[n]*/,
                       int64_t n, pg_stream s);
+
+/* The kernel of pg_request_attn_spans on caller-provided device arrays, one layer (semantics above): q_dev packed bf16
+ * [tokens][nh * 128] (row r's slot j at token row_off[r] + j; row_off[r] < 0: the row has no tokens and gives zeros), k_dev bf16
+ * [R][nh][slots][128], row_off_dev / len_dev / pad_len_dev int32 [R], span_lo_dev / span_hi_dev int32 [R][n_spans] (columns),
+ * out_dev fp32 [R][n_q][n_spans] (every element is written).  len[r] <= slots and the extent of q_dev are the caller's.
+ * PG_ERR_ARG: a null pointer, a PG_F32 handle, R outside 1..65535, nh / slots / n_q < 1, q_col0 < 0, n_spans outside 1..16. */
+int pg_op_attn_span_mass(pg_handle h, const void* q_dev, const void* k_dev, const int32_t* row_off_dev, const int32_t* len_dev,
+                         const int32_t* pad_len_dev, const int32_t* span_lo_dev, const int32_t* span_hi_dev, int R, int nh, int slots,
+                         int n_spans, int q_col0, int n_q, float scale, float* out_dev, pg_stream s);
 
 /* 3x3 convolution over NHWC activations (compute dtype), the VQ-16 ResnetBlock / Upsample /
  * Downsample conv (vq_model.py:337-352, :417-427, :440-447).  w_dev is [Cout][9][Cin]

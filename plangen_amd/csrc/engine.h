@@ -71,6 +71,8 @@ struct DecodeView {
 };
 // pg_request_token_logprobs / pg_request_token_stats as the decode / generate call they were armed for took them (pg_engine::take_requests)
 struct TokenRequests { float* lp_out; int64_t lp_cap; pg_token_stats ts; bool stats; };
+// pg_request_attn_spans as the prefill that took it serves it: device copies of pad_len [R] and the spans [R][n_spans], where layer li's block goes
+struct AttnSpanRun { const int32_t *d_pad, *d_lo, *d_hi; int n_spans, q_col0, n_q; uint64_t mask; float* out; long layer_floats; };
 
 struct pg_engine {
     pg_config cfg{};
@@ -140,6 +142,13 @@ struct pg_engine {
         return TokenStatsOut{d_stats, d_stats + P, (int32_t*)(d_stats + 2 * P), (int32_t*)(d_stats + 3 * P), d_stats + 11 * P, n_alt};
     }
     int stats_copy_out(const pg_token_stats& r, int B, int cols, int pitch_cols, hipStream_t s);   // the first cols columns of [B, pitch_cols]
+    // pg_request_attn_spans: one-shot in front of the next pg_prefill / pg_prefill_embeds (consumed whatever that call answers).  The host arrays
+    // are copied at request time; d_as (first request) holds [pad_len max_rows | lo 16 max_rows | hi 16 max_rows]; as_run is non-null only while
+    // the prefill that took the request runs its layers
+    pg_attn_spans as_req{}; bool as_pending = false; std::vector<int32_t> as_lo, as_hi; int32_t* d_as = nullptr; const AttnSpanRun* as_run = nullptr;
+    int request_attn_spans(const pg_attn_spans* req);
+    int op_attn_span_mass(const void* q, const void* k, const int32_t* row_off, const int32_t* len, const int32_t* pad_len, const int32_t* lo,
+                          const int32_t* hi, int R_, int nh, int slots_, int n_spans, int q_col0, int n_q, float scale, float* out, hipStream_t s);
     int rng_image_offset = 0;                                    // pg_set_option("rng_image_offset", lo): this rank's first image in the global batch
     PgTune tune;                                                 // per-handle tuning knobs (pg_set_option)
     int tune_epoch = 0;                                          // bumped by every option that changes what a captured graph contains

@@ -141,6 +141,17 @@ int pg_request_token_stats(pg_handle h, const pg_token_stats* req) {
     h->ts_req = *req; h->ts_pending = true;
     return PG_OK;
 }
+int pg_request_attn_spans(pg_handle h, const pg_attn_spans* req) {
+    if (!h) return PG_ERR_ARG;
+    return h->request_attn_spans(req);
+}
+int pg_op_attn_span_mass(pg_handle h, const void* q_dev, const void* k_dev, const int32_t* row_off_dev, const int32_t* len_dev,
+                         const int32_t* pad_len_dev, const int32_t* span_lo_dev, const int32_t* span_hi_dev, int R, int nh, int slots, int n_spans,
+                         int q_col0, int n_q, float scale, float* out_dev, pg_stream s) {
+    if (!h) return PG_ERR_ARG;
+    return h->op_attn_span_mass(q_dev, k_dev, row_off_dev, len_dev, pad_len_dev, span_lo_dev, span_hi_dev, R, nh, slots, n_spans, q_col0, n_q, scale,
+                                out_dev, (hipStream_t)s);
+}
 int pg_vq_decode(pg_handle h, const int32_t* codes_dev, void* img_out_dev, int out_dtype, int B, pg_stream s) { TuneGuard _tg(h);
     if (!h || !codes_dev || !img_out_dev) return PG_ERR_ARG;
     return h->bf ? h->vq_decode<bf16>(codes_dev, img_out_dev, out_dtype, B, (hipStream_t)s)

@@ -113,6 +113,15 @@ void pg_engine::run_layers(hipStream_t s, DecodeView& v, int M, int mode, T* fin
             }
             if (!done)
                 launch_attn<T>(s, (const T*)v.qbuf, (T*)v.obuf, (const T*)kc(v, li), (const T*)vc(v, li), seq(v), mode, M, cfg.n_heads, slots, scale);
+            // pg_request_attn_spans: this layer's RoPE'd Q and K are both still in place (FP8 cache: the bf16 scratch, before it is quantised)
+            if constexpr (std::is_same<T, bf16>::value) {
+                if (mode == 1 && as_run && ((as_run->mask >> li) & 1)) {
+                    const AttnSpanRun& a = *as_run;
+                    const int nth = __builtin_popcountll(a.mask & ((1ull << li) - 1));          // layers ascending
+                    launch_attn_span_mass(s, (const bf16*)v.qbuf, (const bf16*)kc(v, li), d_row_off, v.d_len, a.d_pad, a.d_lo, a.d_hi, a.n_spans,
+                                          a.q_col0, a.n_q, v.rows, cfg.n_heads, slots, scale, a.out + nth * a.layer_floats);
+                }
+            }
             // FP8 KV cache: this layer's K/V of the packed tokens, bf16 scratch -> codes + scales (prefill only: decode never takes this branch)
             if (kv8 && mode == 1)
                 launch_kv_quantize(s, (const bf16*)kc(v, li), (const bf16*)vc(v, li), kc8(li), vc8(li), kvs(li), d_tok_row, d_tok_j, M, cfg.n_heads, slots);
@@ -179,7 +188,19 @@ int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtyp
     // one-shot: the hint describes the ids of THIS call only -- consumed before anything can fail, so that a rejected call
     // cannot leave it armed for the next batch
     const int hint = uncond_hint; uncond_hint = -1;
+    const bool as = as_pending; as_pending = false;      // pg_request_attn_spans: one-shot in the same way
     if (!finalized) FAIL(PG_ERR_STATE, "pg_finalize_weights not called");
+    if (as) {       // nothing is launched when the request does not fit this call
+        const pg_attn_spans& q = as_req;
+        if (replicated_api) FAIL(PG_ERR_ARG, "pg_request_attn_spans: pg_prefill_replicated packs owner rows only and cannot serve it");
+        if (!bf) FAIL(PG_ERR_ARG, "pg_request_attn_spans: the span kernel is bf16; a PG_F32 handle cannot serve it");
+        if (q.rows != R0) FAIL(PG_ERR_ARG, "pg_request_attn_spans: requested for %d rows, the prefill has %d", q.rows, R0);
+        if (q.q_col0 < 0 || q.n_q < 1 || (long)q.q_col0 + q.n_q > L_) FAIL(PG_ERR_ARG, "pg_request_attn_spans: query columns [%d, %d + %d) leave the %d columns of the prefill", q.q_col0, q.q_col0, q.n_q, L_);
+        for (size_t i = 0; i < as_lo.size(); ++i)
+            if (as_lo[i] < 0 || as_lo[i] > L_ || as_hi[i] < 0 || as_hi[i] > L_) FAIL(PG_ERR_ARG, "pg_request_attn_spans: span %d of row %d, [%d, %d), leaves [0, %d]", (int)(i % q.n_spans), (int)(i / q.n_spans), as_lo[i], as_hi[i], L_);
+        if (q.capacity_floats < (int64_t)__builtin_popcountll(q.layer_mask) * R0 * q.n_q * q.n_spans)
+            FAIL(PG_ERR_CAPACITY, "pg_request_attn_spans: capacity_floats %lld < %d layers x %d rows x %d queries x %d spans", (long long)q.capacity_floats, __builtin_popcountll(q.layer_mask), R0, q.n_q, q.n_spans);
+    }
     // Replicated batch (pg_prefill_replicated): R_ = R0 * replicas VIRTUAL rows, row t * R0 + r = replica t of row r (the reference's [all pairs] x p,
     // plangen_base.py:547).  Everything below is decided on the virtual rows exactly as a plain prefill of the replicated ids would decide it; only the
     // rows that own their prompt (owner(row) == row) are packed and run through the layer stack.
@@ -207,7 +228,8 @@ int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtyp
     // the prefill, depends on the answer).  Only on the fused path (no per-position hidden output).
     shared_len = 0;
     // (replicated: the odd virtual rows are the odd rows of every replica -- R0 must be even for that -- and the probe compares the distinct ones)
-    if (share_uncond && fuse_rope && ids_dev && !hidden_out && pmode == 0 && R_ >= 4 && (R0 % 2) == 0) {
+    // (a pending span request needs every row's own Q and K: no sharing)
+    if (share_uncond && fuse_rope && ids_dev && !hidden_out && pmode == 0 && R_ >= 4 && (R0 % 2) == 0 && !as) {
         bool same = true;
         for (int r = 3; r < R_ && same; r += 2) same = pad_of(r) == pad_len[1];
         if (same && hint == 1) shared_len = L_ - pad_len[1];      // the caller compared the ids on the host (its collate built them): no probe, no sync
@@ -263,6 +285,19 @@ int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtyp
     HIPCHK(hipMemcpyAsync(d_tok_row, s_row, (size_t)ntok * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_tok_j, s_j, (size_t)ntok * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_tok_src, s_src, (size_t)ntok * 4, hipMemcpyHostToDevice, s));
+    AttnSpanRun asr{};
+    if (as) {       // pad_len and the spans ride in the same pinned staging buffer, behind the token lists
+        const int n = as_req.rows * as_req.n_spans;
+        int32_t* s_as = hs + 5 * cfg.max_rows + 3 * max_tok + 16;
+        for (int r = 0; r < R_; ++r) s_as[r] = pad_of(r);
+        std::copy(as_lo.begin(), as_lo.end(), s_as + cfg.max_rows);
+        std::copy(as_hi.begin(), as_hi.end(), s_as + 17 * cfg.max_rows);
+        HIPCHK(hipMemcpyAsync(d_as, s_as, (size_t)R_ * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_as + cfg.max_rows, s_as + cfg.max_rows, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_as + 17 * cfg.max_rows, s_as + 17 * cfg.max_rows, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        asr = AttnSpanRun{d_as, d_as + cfg.max_rows, d_as + 17 * cfg.max_rows, as_req.n_spans, as_req.q_col0, as_req.n_q, as_req.layer_mask,
+                          as_req.out_dev, (long)R_ * as_req.n_q * as_req.n_spans};
+    }
     HIPCHK(hipEventRecord(ev_stage[stage_sel], s));
     stage_used[stage_sel] = true;
     HIPCHK(hipMemsetAsync(d_ndec, 0, 64, s));
@@ -270,7 +305,9 @@ int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtyp
     if (ids_dev) launch_embed_gather(s, embed, ids_dev, d_tok_src, x, ntok, H(), cfg.vocab);
     else launch_rows_to_f32(s, emb_dev, emb_dtype == PG_BF16, d_tok_src, x, ntok, H());
     DecodeView v = view(0, R, 0);
+    as_run = as ? &asr : nullptr;
     if (bf) run_layers<bf16>(s, v, ntok, 1, (bf16*)xn); else run_layers<float>(s, v, ntok, 1, (float*)xn);
+    as_run = nullptr;
     // last real token of every row -> hfin (input of gen_head / lm_head for the first sample)
     launch_copy_rows(s, xn, d_last, hfin, nullptr, R, (long)H() * esz);
     if (replicas > 1 && alias == 0) {     // the equality-tested fallback: every replica gets a private copy of its owner's prompt K/V, decode runs today's kernels
@@ -288,6 +325,37 @@ int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtyp
     have_prefill_t = true;
     HIPCHK(hipGetLastError());
     prefilled = true;
+    return PG_OK;
+}
+
+// pg_request_attn_spans: what can be checked without the prefill is checked here; the host arrays are copied
+int pg_engine::request_attn_spans(const pg_attn_spans* q) {
+    if (!q) { as_pending = false; return PG_OK; }
+    as_pending = false;                                   // a refused request leaves nothing pending either
+    if (!q->span_lo_host || !q->span_hi_host || !q->out_dev) FAIL(PG_ERR_ARG, "pg_request_attn_spans: null pointer");
+    if (q->rows < 1 || q->rows > cfg.max_rows) FAIL(PG_ERR_ARG, "pg_request_attn_spans: rows=%d not in [1, max_rows=%d]", q->rows, cfg.max_rows);
+    if (q->n_spans < 1 || q->n_spans > 16) FAIL(PG_ERR_ARG, "pg_request_attn_spans: n_spans=%d not in [1, 16]", q->n_spans);
+    if (q->q_col0 < 0 || q->n_q < 1) FAIL(PG_ERR_ARG, "pg_request_attn_spans: q_col0=%d must be >= 0 and n_q=%d >= 1", q->q_col0, q->n_q);
+    if (q->layer_mask == 0 || (cfg.n_layers < 64 && (q->layer_mask >> cfg.n_layers) != 0))
+        FAIL(PG_ERR_ARG, "pg_request_attn_spans: layer_mask must be non-zero and name layers below %d", cfg.n_layers);
+    if (q->capacity_floats < 1) FAIL(PG_ERR_ARG, "pg_request_attn_spans: capacity_floats must be >= 1");
+    if (!d_as) { HIPCHK(hipSetDevice(dev)); TRY(dalloc(&d_as, (size_t)33 * cfg.max_rows * 4)); }
+    as_lo.assign(q->span_lo_host, q->span_lo_host + (size_t)q->rows * q->n_spans);
+    as_hi.assign(q->span_hi_host, q->span_hi_host + (size_t)q->rows * q->n_spans);
+    as_req = *q; as_req.span_lo_host = nullptr; as_req.span_hi_host = nullptr;
+    as_pending = true;
+    return PG_OK;
+}
+// pg_op_attn_span_mass: the kernel alone on the caller's device arrays
+int pg_engine::op_attn_span_mass(const void* q, const void* k, const int32_t* row_off, const int32_t* len, const int32_t* pad_len, const int32_t* lo,
+                                 const int32_t* hi, int R_, int nh, int slots_, int n_spans, int q_col0, int n_q, float scale, float* out, hipStream_t s) {
+    if (!q || !k || !row_off || !len || !pad_len || !lo || !hi || !out) FAIL(PG_ERR_ARG, "pg_op_attn_span_mass: null pointer");
+    if (!bf) FAIL(PG_ERR_ARG, "pg_op_attn_span_mass: the span kernel is bf16; a PG_F32 handle cannot run it");
+    if (R_ < 1 || R_ > 65535 || nh < 1 || slots_ < 1 || n_spans < 1 || n_spans > 16 || q_col0 < 0 || n_q < 1)
+        FAIL(PG_ERR_ARG, "pg_op_attn_span_mass: needs 1 <= R <= 65535, nh >= 1, slots >= 1, n_spans in [1, 16], q_col0 >= 0, n_q >= 1");
+    HIPCHK(hipSetDevice(dev));
+    launch_attn_span_mass(s, (const bf16*)q, (const bf16*)k, row_off, len, pad_len, lo, hi, n_spans, q_col0, n_q, R_, nh, slots_, scale, out);
+    HIPCHK(hipGetLastError());
     return PG_OK;
 }
 

@@ -162,6 +162,12 @@ void launch_attn(hipStream_t s, const T* qbuf, T* obuf, const T* kc, const T* vc
 // prefill: causal varlen flash attention on MFMA (bf16, head_dim 128); row_off[r] = first packed token of row r or -1
 void launch_attn_prefill_flash(hipStream_t s, const bf16* qbuf, bf16* obuf, const bf16* kc, const bf16* vc,
                                const int32_t* row_off, const int32_t* len, int R, int max_len, int nh, int slots, float scale);
+// prefill: attention mass of the query columns [q_col0, q_col0 + n_q) on at most 16 spans per row (attn_span.hip; definition: include/plangen_hip.h,
+// pg_request_attn_spans).  q / K / row_off / len as the flash attention gets them; pad_len / span_lo / span_hi are device arrays ([R], [R][n_spans],
+// columns of the padded frame: slot = column - pad_len[r]); out fp32 [R][n_q][n_spans] (zeroed, then written).  len[r] <= slots is the caller's.
+void launch_attn_span_mass(hipStream_t s, const bf16* qbuf, const bf16* kc, const int32_t* row_off, const int32_t* len, const int32_t* pad_len,
+                           const int32_t* span_lo, const int32_t* span_hi, int n_spans, int q_col0, int n_q, int R, int nh, int slots,
+                           float scale, float* out);
 // decode step: RoPE + KV append + attention in one kernel (reads the QKV split-K slabs)
 template <typename T>
 void launch_attn_decode_fused(hipStream_t s, const float* qkv, int S, long slab, T* obuf, T* kc, T* vc,

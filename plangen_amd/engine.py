@@ -422,11 +422,33 @@ class Engine:
             return False
         return bool((ids[3::2, int(pad_len[1]):] == ids[1, int(pad_len[1]):]).all())
 
+    def _request_attn_spans(self, attn_spans, R: int) -> torch.Tensor:
+        """``pg_request_attn_spans`` for the next prefill: ``attn_spans`` = (lo, hi, q_col0, n_q, layers) with lo / hi int [R, S] span
+        bounds in columns (S in 1..16), the reported query columns [q_col0, q_col0 + n_q) and ``layers`` an iterable of layer indices
+        (None: all).  Returns the fp32 [len(layers), R, n_q, S] tensor that prefill fills (NaN where it writes nothing), layers ascending."""
+        lo, hi, q_col0, n_q, layers = attn_spans
+        lo = torch.as_tensor(lo).to("cpu", torch.int32).contiguous()
+        hi = torch.as_tensor(hi).to("cpu", torch.int32).contiguous()
+        if lo.dim() != 2 or lo.shape != hi.shape or lo.shape[0] != R:
+            raise PlanGenError(f"attn_spans: lo / hi must both be [R, S] = [{R}, S] (got {tuple(lo.shape)} / {tuple(hi.shape)})")
+        layers = sorted(set(int(l) for l in (range(self.cfg.n_layers) if layers is None else layers)))
+        if not layers or layers[0] < 0 or layers[-1] >= self.cfg.n_layers:
+            raise PlanGenError(f"attn_spans: layers must be a non-empty subset of 0 .. {self.cfg.n_layers - 1}")
+        mask = 0
+        for l in layers:
+            mask |= 1 << l
+        S = lo.shape[1]
+        out = torch.full((len(layers), R, max(int(n_q), 0), S), float("nan"), dtype=torch.float32, device=self.device)
+        req = _lib.pg_attn_spans(lo.data_ptr(), hi.data_ptr(), R, S, int(q_col0), int(n_q), mask, out.data_ptr(), out.numel())
+        self._check(self.lib.pg_request_attn_spans(self.h, C.byref(req)), "pg_request_attn_spans")
+        return out
+
     def prefill(self, ids: torch.Tensor, pad_len: Sequence[int], position_mode: int = 0,
-                return_hidden: bool = False, hidden_dtype=torch.float32, uncond_shared: Optional[bool] = None) -> Optional[torch.Tensor]:
+                return_hidden: bool = False, hidden_dtype=torch.float32, uncond_shared: Optional[bool] = None, attn_spans=None):
         """uncond_shared: None -> decided here when ``ids`` is still a HOST tensor (the collate's output; exact comparison, no device
         sync inside pg_prefill), probed on the device otherwise; True / False -> the caller's own host-side answer (bench.py:
-        rank 0 compares the collated ids once and broadcasts the flag with them)."""
+        rank 0 compares the collated ids once and broadcasts the flag with them).  attn_spans (see ``_request_attn_spans``): the call
+        returns (hidden or None, fp32 [layers, R, n_q, S] attention mass on the spans) instead."""
         if uncond_shared is None and not ids.is_cuda and position_mode == 0 and not return_hidden:
             uncond_shared = self.uncond_rows_shared(ids, pad_len)
         self.set_option("uncond_shared_hint", -1 if uncond_shared is None else int(bool(uncond_shared)))    # always sent: never a stale hint
@@ -434,11 +456,12 @@ class Engine:
         R, L = ids.shape
         pl = (C.c_int32 * R)(*[int(v) for v in pad_len])
         out = torch.empty((R, L, self.cfg.hidden), dtype=hidden_dtype, device=self.device) if return_hidden else None
+        mass = self._request_attn_spans(attn_spans, R) if attn_spans is not None else None
         self._check(self.lib.pg_prefill(self.h, self._p(ids), pl, R, L, position_mode, self._p(out),
                                         _dt(out) if out is not None else PG_F32, self.stream), "pg_prefill")
         self.R, self.L = R, L
-        self._keep = [ids]
-        return out
+        self._keep = [ids, mass]
+        return out if attn_spans is None else (out, mass)
 
     def prefill_replicated(self, ids: torch.Tensor, pad_len: Sequence[int], replicas: int, alias: bool = True,
                            uncond_shared: Optional[bool] = None) -> None:
@@ -459,17 +482,19 @@ class Engine:
         self._keep = [ids]
 
     def prefill_embeds(self, embeds: torch.Tensor, pad_len: Sequence[int], position_mode: int = 0,
-                       return_hidden: bool = False, hidden_dtype=torch.float32) -> Optional[torch.Tensor]:
+                       return_hidden: bool = False, hidden_dtype=torch.float32, attn_spans=None):
+        """attn_spans: as in :meth:`prefill` -- the call returns (hidden or None, attention mass) instead."""
         embeds = self._dev(embeds)
         R, L, _ = embeds.shape
         pl = (C.c_int32 * R)(*[int(v) for v in pad_len])
         out = torch.empty((R, L, self.cfg.hidden), dtype=hidden_dtype, device=self.device) if return_hidden else None
+        mass = self._request_attn_spans(attn_spans, R) if attn_spans is not None else None
         self._check(self.lib.pg_prefill_embeds(self.h, self._p(embeds), _dt(embeds), pl, R, L, position_mode,
                                                self._p(out), _dt(out) if out is not None else PG_F32, self.stream),
                     "pg_prefill_embeds")
         self.R, self.L = R, L
-        self._keep = [embeds]
-        return out
+        self._keep = [embeds, mass]
+        return out if attn_spans is None else (out, mass)
 
     def step(self, embeds: torch.Tensor, hidden_dtype=torch.float32) -> torch.Tensor:
         embeds = self._dev(embeds).view(self.R, self.cfg.hidden)
@@ -707,30 +732,89 @@ class Engine:
         with c / u the gen_head logits of rows 2b / 2b + 1 after [prompt | codes[b, :j]] -- what ``decode_image_tokens(force_tokens=codes,
         force_mask=zeros, return_logprobs=True)`` returns.  Needs max_prompt >= L + T - 1 and at most ``score_image_max_tokens()`` packed
         tokens (PlanGenError otherwise).  The engine is left prefilled with the L + T - 1 columns."""
+        codes, emb = self._image_prefix_embeds("score_image", ids, pad_len, codes)
+        R, L = ids.shape
+        B, T = codes.shape
+        cond, uncond = image_score_index(L, T, R, device=self.device)
+        hid = self.prefill_embeds(emb, pad_len, position_mode=0, return_hidden=True, hidden_dtype=self.tdtype)
+        return self.score_image_tokens(hid, codes.reshape(-1), cond, uncond, cfg_weight, temperature).view(B, T)
+
+    def _image_prefix_embeds(self, who: str, ids: torch.Tensor, pad_len: Sequence[int], codes: torch.Tensor):
+        """What ``score_image`` and ``attribute_image`` send through their one prefill: the checks and limits they share, then (codes int32
+        [B, T] on the device, fp32 [2B, L + T - 1, hidden] = [embed(prompt) | gen_embed(codes[:, :T-1]) on both rows of a pair])."""
         if ids.dim() != 2 or ids.shape[0] < 2 or ids.shape[0] % 2:
-            raise PlanGenError(f"score_image: ids must be [2B, L] with CFG-interleaved rows (got {tuple(ids.shape)})")
+            raise PlanGenError(f"{who}: ids must be [2B, L] with CFG-interleaved rows (got {tuple(ids.shape)})")
         R, L = ids.shape
         B = R // 2
         if codes.dim() != 2 or codes.shape[0] != B or codes.shape[1] < 1:
-            raise PlanGenError(f"score_image: codes must be [B, T] = [{B}, T >= 1] for {R} prompt rows (got {tuple(codes.shape)})")
+            raise PlanGenError(f"{who}: codes must be [B, T] = [{B}, T >= 1] for {R} prompt rows (got {tuple(codes.shape)})")
         if len(pad_len) != R:
-            raise PlanGenError(f"score_image: {len(pad_len)} pad lengths for {R} rows")
+            raise PlanGenError(f"{who}: {len(pad_len)} pad lengths for {R} rows")
         T = codes.shape[1]
         W = L + T - 1
         longest = W - min(int(p) for p in pad_len)
         if longest > self.max_prompt:
-            raise PlanGenError(f"score_image: [prompt | image tokens] is {longest} tokens long: the engine needs max_prompt >= {longest} (it has {self.max_prompt})")
+            raise PlanGenError(f"{who}: [prompt | image tokens] is {longest} tokens long: the engine needs max_prompt >= {longest} (it has {self.max_prompt})")
         ntok = sum(W - int(p) for p in pad_len)
         if ntok > self.score_image_max_tokens():
-            raise PlanGenError(f"score_image: {ntok} packed tokens in one prefill exceed the limit of {self.score_image_max_tokens()}: score fewer images per call")
-        cond, uncond = image_score_index(L, T, R, device=self.device)
+            raise PlanGenError(f"{who}: {ntok} packed tokens in one prefill exceed the limit of {self.score_image_max_tokens()}: score fewer images per call")
         codes = self._dev(codes, torch.int32)
         emb = torch.empty((R, W, self.cfg.hidden), dtype=torch.float32, device=self.device)
         emb[:, :L] = self.embed_tokens(ids)
         if T > 1:
             emb[:, L:] = self.gen_embed(codes[:, :T - 1]).view(B, T - 1, -1).repeat_interleave(2, dim=0)      # the same tokens on both rows of a pair
-        hid = self.prefill_embeds(emb, pad_len, position_mode=0, return_hidden=True, hidden_dtype=self.tdtype)
-        return self.score_image_tokens(hid, codes.reshape(-1), cond, uncond, cfg_weight, temperature).view(B, T)
+        return codes, emb
+
+    # ------------------------------------------------------------------ attention mass on prompt spans
+    def attn_span_mass(self, q: torch.Tensor, k: torch.Tensor, row_off: Sequence[int], length: Sequence[int], pad_len: Sequence[int],
+                       lo, hi, q_col0: int, n_q: int, scale: Optional[float] = None) -> torch.Tensor:
+        """``pg_op_attn_span_mass``: the span kernel on caller-given tensors, one layer.  ``q`` bf16 [tokens, nh * 128] packed (row r's slot j
+        at token row_off[r] + j), ``k`` bf16 [R, nh, slots, 128], ``row_off`` / ``length`` / ``pad_len`` [R], ``lo`` / ``hi`` int [R, S] span
+        bounds in columns (column = slot + pad_len[r]) -> fp32 [R, n_q, S], the attention mass of query columns [q_col0, q_col0 + n_q) on
+        every span, mean over heads (definition: include/plangen_hip.h).  scale defaults to 1 / sqrt(128)."""
+        q = self._dev(q, torch.bfloat16)
+        k = self._dev(k, torch.bfloat16)
+        if k.dim() != 4 or k.shape[3] != 128 or q.dim() != 2 or q.shape[1] != k.shape[1] * 128:
+            raise PlanGenError(f"attn_span_mass: q must be [tokens, nh * 128] and k [R, nh, slots, 128] (got {tuple(q.shape)} / {tuple(k.shape)})")
+        R, nh, slots, _ = k.shape
+        lo_t = torch.as_tensor(lo).to(torch.int32).reshape(R, -1)
+        hi_t = torch.as_tensor(hi).to(torch.int32).reshape(R, -1)
+        S = lo_t.shape[1]
+        if hi_t.shape != lo_t.shape or len(row_off) != R or len(length) != R or len(pad_len) != R:
+            raise PlanGenError("attn_span_mass: row_off / length / pad_len must have R entries and lo / hi the same [R, S] shape")
+        for r in range(R):      # the kernel trusts these: check them where they are still host numbers
+            if int(length[r]) < 0 or int(length[r]) > slots or (int(row_off[r]) >= 0 and int(row_off[r]) + int(length[r]) > q.shape[0]):
+                raise PlanGenError(f"attn_span_mass: row {r}: length {int(length[r])} / row_off {int(row_off[r])} leave k's {slots} slots or q's {q.shape[0]} tokens")
+        dv = [self._dev(torch.as_tensor([int(v) for v in x], dtype=torch.int32)) for x in (row_off, length, pad_len)]
+        lo_d, hi_d = self._dev(lo_t), self._dev(hi_t)
+        out = torch.full((R, max(int(n_q), 0), S), float("nan"), dtype=torch.float32, device=self.device)
+        sc = float(scale) if scale is not None else 128.0 ** -0.5
+        self._check(self.lib.pg_op_attn_span_mass(self.h, self._p(q), self._p(k), self._p(dv[0]), self._p(dv[1]), self._p(dv[2]), self._p(lo_d),
+                                                  self._p(hi_d), R, nh, slots, S, int(q_col0), int(n_q), sc, self._p(out), self.stream),
+                    "pg_op_attn_span_mass")
+        self._keep = [q, k, dv, lo_d, hi_d, out]
+        return out
+
+    def attribute_image(self, ids: torch.Tensor, pad_len: Sequence[int], codes: torch.Tensor, lo, hi, layers=None) -> torch.Tensor:
+        """Attention mass of the query positions that PREDICT the image tokens on prompt spans, in the one teacher-forced prefill
+        ``score_image`` runs: ``ids`` int [2B, L] / ``pad_len`` [2B] / ``codes`` int [B, T] as there; ``lo`` / ``hi`` int [B, S] (S in
+        1..16): span s of image b is the prompt columns [lo, hi) of its CONDITIONAL row 2b.  Returns fp32 [n_layers_sel, B, T, S]: entry
+        [l, b, j, s] is the share of attention (mean over heads, layer layers[l], ascending; None: all) that column L - 1 + j of row 2b
+        -- the query that produced image token j, the row ``image_score_index`` names -- puts on span s.  Same limits and errors as
+        ``score_image``; the engine is left prefilled with the L + T - 1 columns."""
+        codes, emb = self._image_prefix_embeds("attribute_image", ids, pad_len, codes)
+        R, L = ids.shape
+        B, T = codes.shape
+        lo_t = torch.as_tensor(lo).to("cpu", torch.int32)
+        hi_t = torch.as_tensor(hi).to("cpu", torch.int32)
+        if lo_t.dim() != 2 or lo_t.shape[0] != B or lo_t.shape != hi_t.shape:
+            raise PlanGenError(f"attribute_image: lo / hi must both be [B, S] = [{B}, S] (got {tuple(lo_t.shape)} / {tuple(hi_t.shape)})")
+        S = lo_t.shape[1]
+        lo_r = torch.zeros((R, S), dtype=torch.int32)      # unconditional rows: empty spans
+        hi_r = torch.zeros((R, S), dtype=torch.int32)
+        lo_r[0::2], hi_r[0::2] = lo_t, hi_t
+        _, mass = self.prefill_embeds(emb, pad_len, position_mode=0, attn_spans=(lo_r, hi_r, L - 1, T, layers))
+        return mass[:, 0::2].contiguous()
 
     def generate_text(self, max_new_tokens: int, eos_id: int, min_new_tokens: int = 0, temperature: float = 0.0, top_k: int = 0,
                       top_p: float = 1.0, seed: int = 0, return_logits: bool = False, return_logprobs: bool = False, return_stats=False):

@@ -424,6 +424,12 @@ class System:
             # the generation: it re-prefills.
             sc = self.score_images(batch, scored=(batch["edit_region"] != 0) if batch.get("edit_region") is not None else None)
             out["gt_image_logprob"] = {k: sc[k] for k in ("sum", "mean", "n_tokens")}
+        if getattr(self.args, "layout_attribution", False) and pred_image:
+            # uni / uni_2stage: attention of the image positions on the layout items of the prompt, scored on the tokens just generated (replica 0
+            # when parallel_size > 1).  Runs after the generation: it re-prefills.
+            att = self.attribute_layout(batch, codes=self.last_generated_tokens[:batch["uni_inputs_ids"].shape[0]])
+            out["layout_attribution"] = [[dict(phrase=p, inside=(None if v != v else v)) for p, v in zip(a["phrases"], a["inside"])] for a in att]
+            out["layout_attribution_maps"] = [a["maps"] for a in att]
         if getattr(self.args, "score_gt_layout", False) and pred_layout and batch.get("gt_grounding") is not None:
             # plan / uni_2stage: P(ground-truth layout | caption); mmu: P(ground-truth layout | image).  Runs after the generation: it re-prefills.
             sc = self.score_layouts(batch, given="image" if is_mmu else "caption")
@@ -445,6 +451,14 @@ class System:
                 if "image_entropy" in out:
                     import numpy as np
                     np.save(os.path.join(gen_path, f"{batch_idx}_entropy.npy"), out["image_entropy"].float().cpu().numpy())
+                if "layout_attribution" in out:
+                    import numpy as np
+                    extra["layout_attribution"] = out["layout_attribution"]
+                    maps = out["layout_attribution_maps"]          # [B, most items of a row, grid, grid], NaN where a row has fewer
+                    arr = np.full((len(maps), max((m.shape[0] for m in maps), default=0), self.cfg.grid, self.cfg.grid), np.nan, dtype=np.float32)
+                    for b, m in enumerate(maps):
+                        arr[b, :m.shape[0]] = m.numpy()
+                    np.save(os.path.join(gen_path, f"{batch_idx}_attribution.npy"), arr)
                 json.dump(dict(base_caption=base_caption, gt_grounding=batch.get("gt_grounding"),
                                pr_grounding=pr_grounding if pred_layout else "", **extra), f)
         return out
@@ -504,6 +518,69 @@ class System:
         n_tok = m.sum(-1)
         sums = torch.where(m, lp, torch.zeros_like(lp)).sum(-1)
         return dict(sum=sums.cpu().tolist(), mean=(sums / n_tok.clamp(min=1)).cpu().tolist(), n_tokens=n_tok.cpu().tolist(), logprobs=lp)
+
+    @torch.no_grad()
+    def attribute_layout(self, batch: dict, codes: Optional[torch.Tensor] = None, kind: str = "entity", layers=None) -> List[dict]:
+        """Was the model reading entity e of the layout while it painted inside box e?  For every image of the batch, the share of attention
+        that the query positions predicting its image tokens put on the prompt tokens of each ``<ref>...</ref><box>...</box>`` item of its
+        image-stage prompt (``_cfg_prompt``, the conditional row), from one teacher-forced prefill per pass (``Engine.attribute_image``):
+        ``codes`` int [B, T] (e.g. the tokens just generated), or None: ``batch['image']`` is VQ-encoded as in ``score_images``.  kind
+        'entity' / 'phrase' / 'box': which tokens of an item count (``textproc.layout_spans``).  layers: layer indices, None: all; the
+        maps are their mean.  A row with more than 16 items takes ceil(E / 16) passes.  Needs a tokenizer (the tags are found by their
+        ids), a bf16 engine with max_prompt >= L + T - 1.
+        Returns one dict per image: ``phrases`` [E] str, ``maps`` fp32 [E, grid, grid] (attention mass of image position (y, x) on item e),
+        ``inside`` [E]: the share of item e's mass over the image that falls into the cells of its own box (``textproc.box_cells`` with
+        args.use_centerhw) -- NaN when the box holds no cell or the mass is 0."""
+        from .textproc import box_cells, layout_spans
+        eng, g = self.engine, self.cfg.grid
+        if self.codec is None:
+            raise PlanGenError("attribute_layout needs a tokenizer (System(codec=...)): the layout items are found by their tag ids")
+        tags = {t: self.codec.token_id(t) for t in ("<ref>", "</ref>", "<box>", "</box>")}
+        if codes is None:
+            if not eng._c.with_vq_encoder:
+                raise PlanGenError("attribute_layout VQ-encodes batch['image']: the engine must be created with_vq_encoder=True (or pass codes)")
+            img = batch["image"]
+            gi = img.to(torch.bfloat16) if eng.dtype == "bf16" else img
+            codes = self.vl_gpt.gen_vision_model.encode(gi)[-1][-1].reshape(img.shape[0], -1)
+        codes = codes.to(torch.int32)
+        B, T = codes.shape
+        cfg_ids, cfg_mask = self._cfg_prompt(batch)
+        if cfg_ids.shape[0] != 2 * B or T != g * g:
+            raise PlanGenError(f"attribute_layout: codes {tuple(codes.shape)} do not match the batch's {cfg_ids.shape[0] // 2} prompts x {g * g} image tokens")
+        L = cfg_ids.shape[1]
+        pad = Engine.pad_len_from_mask(cfg_mask, L)
+        use_chw = bool(getattr(self.args, "use_centerhw", False))
+        rows = [cfg_ids[2 * b].tolist() for b in range(B)]
+        spans = [layout_spans(r, tags, kind) for r in rows]
+        phrases = [[self.decode_text(r[a:z]) for a, z in layout_spans(r, tags, "phrase")] for r in rows]
+        cells = [[box_cells(self.decode_text(r[a:z]), g, use_chw) for a, z in layout_spans(r, tags, "box")] for r in rows]
+        e_max = max((len(s) for s in spans), default=0)
+        mass = torch.zeros((B, T, e_max), dtype=torch.float32)
+        per = min(eng.max_rows // 2, eng.score_image_max_tokens() // (2 * (L + T - 1)))
+        if per < 1:
+            raise PlanGenError(f"attribute_layout: one image pair of {L + T - 1} columns does not fit the engine (max_rows={eng.max_rows}, "
+                               f"at most {eng.score_image_max_tokens()} packed tokens per prefill)")
+        for e0 in range(0, e_max, 16):
+            S = min(16, e_max - e0)
+            lo = torch.zeros((B, S), dtype=torch.int32)
+            hi = torch.zeros((B, S), dtype=torch.int32)          # rows with fewer items: empty spans
+            for b, sp in enumerate(spans):
+                for j, (a, z) in enumerate(sp[e0:e0 + S]):
+                    lo[b, j], hi[b, j] = a, z
+            for b0 in range(0, B, per):
+                m = eng.attribute_image(cfg_ids[2 * b0:2 * (b0 + per)], pad[2 * b0:2 * (b0 + per)], codes[b0:b0 + per], lo[b0:b0 + per],
+                                        hi[b0:b0 + per], layers)
+                mass[b0:b0 + per, :, e0:e0 + S] = m.mean(0).cpu()
+        out = []
+        for b in range(B):
+            E = len(spans[b])
+            maps = mass[b, :, :E].t().reshape(E, g, g).contiguous()
+            inside = []
+            for e in range(E):
+                tot, c = float(maps[e].double().sum()), torch.from_numpy(cells[b][e])
+                inside.append(float(maps[e][c].double().sum()) / tot if c.any() and tot > 0 else float("nan"))
+            out.append(dict(phrases=phrases[b], maps=maps, inside=inside))
+        return out
 
     def _layout_ids(self, grounding: str, strip_open: bool) -> List[int]:
         """Token ids of a layout string without BOS; strip_open: also without the leading ``<grounding>`` the stage-1 prompt already carries."""

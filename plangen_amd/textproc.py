@@ -135,6 +135,55 @@ def trans_gr_to_creati(prompt: str) -> Tuple[List[List[float]], List[str]]:
     return boxes, prompts
 
 
+# ------------------------------------------------------------------------------------------ layout attribution (host side)
+def layout_spans(ids_row: Sequence[int], tag_ids: Dict[str, int], kind: str = "entity") -> List[Tuple[int, int]]:
+    """The token spans [lo, hi) (indices into ``ids_row``, i.e. columns of its row) of every complete ``<ref>...</ref><box>...</box>``
+    item, in order.  ``tag_ids`` maps the four tags to their single-token ids (the tokens ``layout_grammar`` requires).  kind 'phrase':
+    strictly between ``<ref>`` and ``</ref>``; 'box': strictly between ``<box>`` and ``</box>``; 'entity': ``<ref>`` through ``</box>``
+    inclusive.  An item is the innermost well-formed sequence: a second ``<ref>`` restarts it, any other tag out of place drops it, and a
+    truncated tail yields nothing."""
+    if kind not in ("entity", "phrase", "box"):
+        raise ValueError(f"layout_spans: kind must be 'entity', 'phrase' or 'box' (got {kind!r})")
+    ref_o, ref_c, box_o, box_c = (int(tag_ids[t]) for t in ("<ref>", "</ref>", "<box>", "</box>"))
+    out: List[Tuple[int, int]] = []
+    state, a, b, c = 0, 0, 0, 0          # 0 outside; 1 after <ref> at a; 2 after </ref> at b (next must be <box>); 3 after <box> at c
+    for i, t in enumerate(int(v) for v in ids_row):
+        if t == ref_o:
+            state, a = 1, i
+        elif t == ref_c:
+            state, b = (2, i) if state == 1 else (0, b)
+        elif t == box_o:
+            state, c = (3, i) if state == 2 and i == b + 1 else (0, c)
+        elif t == box_c:
+            if state == 3:
+                out.append({"entity": (a, i + 1), "phrase": (a + 1, b), "box": (c + 1, i)}[kind])
+            state = 0
+        elif state == 2:
+            state = 0                    # something between </ref> and <box>: not an item
+    return out
+
+
+def box_cells(box_text: str, grid: int, use_centerhw: bool = False):
+    """Boolean [grid, grid] mask (row = y, column = x, the image tokens' raster order) of the cells whose CENTRE lies inside the box
+    ``box_text`` = "[a,b,c,d]" (brackets optional): coordinates in 1/1000 of the image side as ``draw_boxes_on_image`` reads them --
+    x1,y1,x2,y2, or with ``use_centerhw`` cx,cy,h,w.  Edges are inclusive; a malformed text or a box that holds no centre gives all False."""
+    import numpy as np
+    m = np.zeros((grid, grid), dtype=bool)
+    try:
+        a, b, c, d = (int(v) for v in box_text.strip().lstrip("[").rstrip("]").split(","))
+    except ValueError:
+        return m
+    if use_centerhw:
+        x1, y1, x2, y2 = a - d / 2, b - c / 2, a + d / 2, b + c / 2
+    else:
+        x1, y1, x2, y2 = a, b, c, d
+    centre = (np.arange(grid) + 0.5) * (1000.0 / grid)
+    inx = (centre >= x1) & (centre <= x2)
+    iny = (centre >= y1) & (centre <= y2)
+    m[np.ix_(iny, inx)] = True
+    return m
+
+
 # ------------------------------------------------------------------------------------------ tokenizers
 class HFCodec:
     """The Janus-Pro tokenizer files (tokenizer.json / tokenizer_config.json / special_tokens_map.json) through

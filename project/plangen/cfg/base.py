@@ -25,6 +25,8 @@ layout_best_of = 1                     # uni_2stage / plan with text_temperature
 score_gt_layout = False                # plan / uni_2stage / mmu: also write gt_layout_logprob = {sum, mean, n_tokens} per row to the batch JSON: log P(gt_grounding + EOS | caption) (mmu: | image) from one teacher-forced prefill (an extension beyond the reference)
 score_gt_image = False                 # uni / uni_2stage: also write gt_image_logprob = {sum, mean, n_tokens} per row to the batch JSON: log P(VQ tokens of the ground-truth image | prompt) under the guided distribution (cfg_weight, temperature), from one teacher-forced prefill; with edit_region only the edited positions count (an extension beyond the reference)
 token_stats = False                    # True, or an int n_alt in 1..8: per-token uncertainty from the decode loops, reduced on the device. uni / uni_2stage / t2i: image_token_stats (per image: mean entropy, mean rank, share of rank-0 positions; with use_teacher_forcing also top1 / top5 over edit_region == 0) in the batch JSON and <batch_idx>_entropy.npy fp32 [B * parallel_size, grid, grid]; plan / uni_2stage stage 1 / mmu: text_token_stats (per row: mean entropy, with n_alt > 0 the alternatives' ids) (an extension beyond the reference)
+layout_attribution = False             # uni / uni_2stage (bf16): after generating, one more teacher-forced prefill on the generated tokens reports the attention the image positions put on every <ref>..</ref><box>..</box> item of the prompt: layout_attribution (per item: phrase, inside = share of its mass inside its own box) in the batch JSON and <batch_idx>_attribution.npy fp32 [B, items, grid, grid] (layer mean; NaN rows where a prompt has fewer items); the prompt capacity grows by the image's length (an extension beyond the reference)
+use_centerhw = False                   # base.py:100: boxes are cx,cy,h,w instead of x1,y1,x2,y2 (read by layout_attribution's box cells)
 use_numhw_tokens = False               # base.py:65: add <h0> <w0> ... <h99> <w99> to the tokenizer (plangen_base.py:120-127)
 use_special_tokens = False             # base.py:69: add <grounding> </grounding> <box> </box> <ref> </ref> to the tokenizer (plangen_base.py:110-118)
 use_teacher_forcing = False            # base.py:36

@@ -82,7 +82,8 @@ class System(_HotPath):
         # rows: the CFG batch of every replica, or the stage-1 batch with layout_best_of draws per row, whichever is larger
         stage1 = task in ("uni_2stage", "plan")
         # score_gt_image prefills [prompt | image tokens]: the prompt capacity grows by the image's length
-        max_prompt = int(getattr(args, "max_prompt", 768)) + (cfg.img_tokens - 1 if getattr(args, "score_gt_image", False) else 0)
+        # (layout_attribution prefills the same [prompt | image tokens])
+        max_prompt = int(getattr(args, "max_prompt", 768)) + (cfg.img_tokens - 1 if getattr(args, "score_gt_image", False) or getattr(args, "layout_attribution", False) else 0)
         eng = Engine(cfg, dtype=args.dtype, max_rows=max(2 * bs * int(args.parallel_size), bs * layout_best_of if stage1 else 0), max_prompt=max_prompt,
                      max_new=max(cfg.img_tokens if needs_image else 1, text_new if task != "uni" and task != "t2i" else 1),
                      max_images=bs * int(args.parallel_size), with_lm_head=task in ("uni_2stage", "mmu", "plan"),
@@ -95,6 +96,8 @@ class System(_HotPath):
                                                    score_gt_layout=bool(getattr(args, "score_gt_layout", False)),
                                                    score_gt_image=bool(getattr(args, "score_gt_image", False)),
                                                    token_stats=getattr(args, "token_stats", False),
+                                                   layout_attribution=bool(getattr(args, "layout_attribution", False)),
+                                                   use_centerhw=bool(getattr(args, "use_centerhw", False)),
                                                    use_teacher_forcing=args.use_teacher_forcing, share_replicas=cfg.share_replicas,
                                                    debug_max_seq_len=args.debug_max_seq_len, janus_hw=args.janus_hw,
                                                    neg_prompt=getattr(args, "neg_prompt", ""),
