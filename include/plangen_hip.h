@@ -358,6 +358,43 @@ typedef struct pg_token_stats {
  * decode. */
 int pg_request_token_stats(pg_handle h, const pg_token_stats* req);
 
+/* -- sample plans: per-image sampler parameters, per-(image, step) guidance ---------------------
+ * A sample plan replaces the scalar sampler parameters of the NEXT pg_decode_image_tokens[_filtered] by per-image values; the guidance
+ * weight is per image AND per step.  For the global image bg (local image + the lane's first image) at step t:
+ *   mixed = u + w[bg, t] * (c - u)              fp32, the expression of the unplanned sampler; logits_out_dev and the stored row the
+ *                                               log-prob / stats reducers read receive exactly this value;
+ *   temperature[bg] <= 0                        the image is greedy: lowest index on ties, its top_k / top_p ignored; greedy and sampled
+ *                                               images may share a call;
+ *   temperature[bg] > 0                         Gumbel-max over mixed * (1 / temperature[bg]) with the noise of (seed, key[bg] * 1000003 + t,
+ *                                               v), restricted to the kept set of (top_k[bg], top_p[bg]) by the rule of
+ *                                               pg_decode_image_tokens_filtered.  Two images with the same key and seed draw the same noise.
+ * The filtered route (store, select, pick) is taken when any image of the plan is sampled with top_k > 0 or top_p < 1; an image with
+ * (0, 1.0) draws there exactly what the unfiltered sampler draws.  The log-prob and stats requests use temperature[bg].  A NULL array
+ * stands for the call's scalar (image_key: bg + "rng_image_offset"), so a plan whose arrays are constant and equal to the call's scalars
+ * gives the bits of the call without a plan: tokens, logits_out, log-probs and stats.  Forcing (force_tok, force_mask) is unchanged.
+ * The arrays are HOST arrays, validated and copied here (pinned staging on s guarded by an event, no stream synchronisation; the consuming call's stream
+ * waits on that event, so s need not be the stream of that call) into a
+ * library-owned device copy sized by max_rows / 2 and max_new (allocated by the first request, counted by pg_device_bytes).  The
+ * values reach the kernels through device memory: a captured step graph replays with a new plan, its key only gains "a plan is present".
+ * A call without a plan launches exactly what it launched before this entry point existed. */
+typedef struct pg_sample_plan {
+    const float*   cfg_weight_host;   /* [B, T] or NULL: the call's scalar */
+    const float*   temperature_host;  /* [B]    or NULL */
+    const int32_t* top_k_host;        /* [B]    or NULL */
+    const float*   top_p_host;        /* [B]    or NULL */
+    const int32_t* image_key_host;    /* [B]    or NULL: global image index used in the RNG stream key instead of
+                                         b + "rng_image_offset"; two images with the same key and seed draw the same noise */
+    int32_t B, T;                     /* must equal the consuming call's images and steps */
+} pg_sample_plan;
+/* ONE-SHOT, with the rules of pg_request_token_logprobs: the next pg_decode_image_tokens[_filtered] on the handle consumes it, whether
+ * or not that call succeeds; independent of the log-prob and stats requests (all three may be pending for one call); the text loops
+ * neither consume nor see it.  plan == NULL forgets a pending plan.
+ * PG_ERR_ARG here (nothing pending afterwards): B or T < 1, a non-finite weight or temperature, top_k < 0, top_p outside (0, 1] or NaN,
+ * a negative key (key * 1000003 + T fits the 64-bit stream word for every int32 key >= 0), all five pointers NULL.  PG_ERR_CAPACITY
+ * here: B > max_rows / 2 or T > max_new.  PG_ERR_ARG at the consuming call (nothing launched, the handle still usable): B / T differ
+ * from the call's, the "lanes" = 2 decode, a filtered image with img_vocab > 16384. */
+int pg_request_sample_plan(pg_handle h, const pg_sample_plan* plan /* NULL: forget it */, pg_stream s);
+
 /* -- attention mass on prompt spans ------------------------------------------------------------
  * What output_attentions=True would be reduced to, without the [R, heads, W, W] tensor: for one layer, query column q_i and span s of
  * row r,

@@ -45,6 +45,11 @@ class pg_token_stats(C.Structure):
                 ("alt_logprob_dev", C.c_void_p), ("n_alt", C.c_int32), ("capacity", C.c_int64)]
 
 
+class pg_sample_plan(C.Structure):
+    _fields_ = [("cfg_weight_host", C.c_void_p), ("temperature_host", C.c_void_p), ("top_k_host", C.c_void_p), ("top_p_host", C.c_void_p),
+                ("image_key_host", C.c_void_p), ("B", C.c_int32), ("T", C.c_int32)]
+
+
 class pg_attn_spans(C.Structure):
     _fields_ = [("span_lo_host", C.c_void_p), ("span_hi_host", C.c_void_p), ("rows", C.c_int32), ("n_spans", C.c_int32),
                 ("q_col0", C.c_int32), ("n_q", C.c_int32), ("layer_mask", C.c_uint64), ("out_dev", C.c_void_p), ("capacity_floats", C.c_int64)]
@@ -79,6 +84,7 @@ SYMBOLS = [
     ("pg_generate_text_constrained", C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_int32, C.c_float, C.c_uint64, _P, C.POINTER(C.c_int), _P, _P, _P]),
     ("pg_request_token_logprobs", C.c_int, [_P, _P, C.c_int64]),
     ("pg_request_token_stats", C.c_int, [_P, C.POINTER(pg_token_stats)]),
+    ("pg_request_sample_plan", C.c_int, [_P, C.POINTER(pg_sample_plan), _P]),
     ("pg_request_attn_spans", C.c_int, [_P, C.POINTER(pg_attn_spans)]),
     ("pg_op_attn_span_mass", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, _P, _P]),
     ("pg_score_tokens", C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.c_int64, C.c_float, _P, _P]),

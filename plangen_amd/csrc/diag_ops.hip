@@ -833,6 +833,39 @@ int pg_diag_op_cfg_sample(int filtered, const float* partial, int S, long slab, 
     return finish(s);                                                                                // before the scratch goes away
 }
 
+// pg_diag_op_cfg_sample under a sample plan (tests/test_gpu_sample_plan_ops.py): device plan arrays in place of the five scalars -- w fp32 [B_total][T],
+// temperature fp32 / top_k int32 / top_p fp32 / key int32 [B_total], all indexed by the global image b_off + b -- through launch_cfg_sample_plan.  filtered != 0
+// takes the store -> select -> pick route (the caller says so: the arrays live on the device; V <= SEL_MAXV); stored != 0 also runs the store scan on the
+// unfiltered route.  Everything else as pg_diag_op_cfg_sample.
+int pg_diag_op_cfg_sample_plan(int filtered, int stored, const float* partial, int S, long slab, const float* bias, int V, int B, const int32_t* force_tok,
+                               const uint8_t* force_mask, int32_t* out_tok, float* logits_out, const float* embed_table, float* x, int H, const float* w_dev,
+                               const float* temperature_dev, const int32_t* top_k_dev, const float* top_p_dev, const int32_t* key_dev, uint64_t seed, int T,
+                               int step, int b_off, int B_total, pg_stream stream) {
+    if (!partial || !out_tok || !embed_table || !x || (force_mask && !force_tok)) return PG_ERR_ARG;
+    if (!w_dev || !temperature_dev || !top_k_dev || !top_p_dev || !key_dev) return PG_ERR_ARG;
+    if (S < 1 || V < 1 || B < 1 || B > kMaxGridYZ / 2 || H < 4 || (H & 3) || T < 1 || step < 0 || b_off < 0 || B_total < 1) return PG_ERR_ARG;
+    if ((long)b_off + B > B_total || slab < 2L * B * V || (long)V * H >= (1L << 40) || !aligned16({embed_table, x})) return PG_ERR_ARG;
+    if (logits_out && step >= T) return PG_ERR_ARG;                                                  // the tap has T steps
+    if (filtered && V > SEL_MAXV) return PG_ERR_ARG;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    Scratch sp, nd, pv, pi, mix;
+    if (!sp.get(sizeof(SampleParams)) || !nd.get(4) || !pv.get((size_t)B * 16 * 4) || !pi.get((size_t)B * 16 * 4)) return PG_ERR_HIP;
+    if ((filtered || stored) && !mix.get((size_t)B * V * 4)) return PG_ERR_HIP;
+    const int32_t hstep = step;
+    if (hipMemcpy(nd.p, &hstep, 4, hipMemcpyHostToDevice) != hipSuccess) return PG_ERR_HIP;
+    SampleParams p{};
+    p.seed = seed; p.T = T; p.has_force = force_tok != nullptr; p.has_mask = force_mask != nullptr; p.top_p = 1.f;
+    launch_set_sample_params(s, (SampleParams*)sp.p, p);
+    SampleArgsPlan a{};
+    a.logits_partial = partial; a.S = S; a.slab = slab; a.bias = bias; a.V = V; a.p = (const SampleParams*)sp.p;
+    a.force_tok = force_tok; a.force_mask = force_mask; a.out_tok = out_tok; a.logits_out = logits_out;
+    a.embed_table = embed_table; a.x = x; a.H = H; a.n_dec = (const int32_t*)nd.p; a.b_off = b_off; a.B_total = B_total;
+    a.plan = SamplePlanDev{w_dev, temperature_dev, top_k_dev, top_p_dev, key_dev};
+    launch_cfg_sample_plan(s, a, B, filtered != 0, stored != 0, (float*)pv.p, (int*)pi.p, (float*)mix.p);
+    return finish(s);                                                                                // before the scratch goes away
+}
+
 // The text sampler's step through launch_text_argmax (mode 0) or launch_text_sample (mode 1: the in-scan Gumbel draw, temperature > 0).  partial fp32: slab s at
 // partial + s * slab, rows [B][V], slab >= B V -- an odd slab or V sends the scan down its scalar branch, multiples of 4 down the 16-byte one (then partial and
 // logits_out are 16-byte aligned).  out int64 [B][max_new] (written when step < max_new); unfinished int32 [B] in / out; logits_out fp32 [max_new][B][V] or null

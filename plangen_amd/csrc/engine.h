@@ -149,6 +149,17 @@ struct pg_engine {
     int request_attn_spans(const pg_attn_spans* req);
     int op_attn_span_mass(const void* q, const void* k, const int32_t* row_off, const int32_t* len, const int32_t* pad_len, const int32_t* lo,
                           const int32_t* hi, int R_, int nh, int slots_, int n_spans, int q_col0, int n_q, float scale, float* out, hipStream_t s);
+    // pg_request_sample_plan: one-shot in front of the next image decode.  The host arrays are validated and staged at request time into d_plan
+    // (first request): [w Bmax * max_new | temperature Bmax | top_k Bmax | top_p Bmax | key Bmax], Bmax = max_rows / 2; plan_mask says which arrays
+    // the request carried -- the consuming call fills the others with its scalars (launch_plan_fill).  The host copies of temperature / top_k /
+    // top_p choose the kernel route before anything is launched.  Pinned staging guarded by an event, like the automaton's.
+    struct PlanRequest { bool pending = false; int B = 0, T = 0, mask = 0; std::vector<float> temp, top_p; std::vector<int32_t> top_k; };
+    PlanRequest plan_req; float* d_plan = nullptr; unsigned char* h_plan = nullptr; hipEvent_t ev_plan = nullptr; bool plan_staged = false;
+    SamplePlanDev plan_dev() const {
+        const size_t Bm = (size_t)cfg.max_rows / 2, nw = Bm * cfg.max_new;
+        return SamplePlanDev{d_plan, d_plan + nw, (const int32_t*)(d_plan + nw + Bm), d_plan + nw + 2 * Bm, (const int32_t*)(d_plan + nw + 3 * Bm)};
+    }
+    int request_sample_plan(const pg_sample_plan* plan, hipStream_t s);
     int rng_image_offset = 0;                                    // pg_set_option("rng_image_offset", lo): this rank's first image in the global batch
     PgTune tune;                                                 // per-handle tuning knobs (pg_set_option)
     int tune_epoch = 0;                                          // bumped by every option that changes what a captured graph contains

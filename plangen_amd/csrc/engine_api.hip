@@ -141,6 +141,10 @@ int pg_request_token_stats(pg_handle h, const pg_token_stats* req) {
     h->ts_req = *req; h->ts_pending = true;
     return PG_OK;
 }
+int pg_request_sample_plan(pg_handle h, const pg_sample_plan* plan, pg_stream s) {
+    if (!h) return PG_ERR_ARG;
+    return h->request_sample_plan(plan, (hipStream_t)s);
+}
 int pg_request_attn_spans(pg_handle h, const pg_attn_spans* req) {
     if (!h) return PG_ERR_ARG;
     return h->request_attn_spans(req);

@@ -384,6 +384,8 @@ void pg_engine::destroy() {
     if (h_flag) (void)hipHostFree(h_flag);
     if (h_dfa) (void)hipHostFree(h_dfa);
     if (ev_dfa) (void)hipEventDestroy(ev_dfa);
+    if (h_plan) (void)hipHostFree(h_plan);
+    if (ev_plan) (void)hipEventDestroy(ev_plan);
     for (hipEvent_t e : tc_ev) (void)hipEventDestroy(e);
     hipEvent_t evs[] = {ev_in, ev_out, ev_t0, ev_t1, ev_p0, ev_p1, ev_v0, ev_v1, ev_fork, ev_join};
     if (istream2) (void)hipStreamDestroy(istream2);

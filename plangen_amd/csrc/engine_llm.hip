@@ -403,10 +403,59 @@ int pg_engine::graph_step(hipGraphExec_t& exec, std::vector<int64_t>& cached, co
     return PG_OK;
 }
 
+// pg_request_sample_plan: validate on the host, then stage the given arrays through pinned memory into their places in d_plan (no stream
+// synchronisation: the staging buffer is guarded by an event).  Anything refused leaves nothing pending.
+int pg_engine::request_sample_plan(const pg_sample_plan* pl, hipStream_t s) {
+    plan_req.pending = false;
+    if (!pl) return PG_OK;
+    const int B = pl->B, T = pl->T;
+    if (B < 1 || T < 1) FAIL(PG_ERR_ARG, "pg_request_sample_plan: B=%d and T=%d must be >= 1", B, T);
+    if (!pl->cfg_weight_host && !pl->temperature_host && !pl->top_k_host && !pl->top_p_host && !pl->image_key_host)
+        FAIL(PG_ERR_ARG, "pg_request_sample_plan: all five arrays are NULL");
+    if (B > cfg.max_rows / 2 || T > cfg.max_new) FAIL(PG_ERR_CAPACITY, "pg_request_sample_plan: B=%d > max_rows / 2 = %d or T=%d > max_new=%d", B, cfg.max_rows / 2, T, cfg.max_new);
+    if (pl->cfg_weight_host)
+        for (long i = 0; i < (long)B * T; ++i)
+            if (!std::isfinite(pl->cfg_weight_host[i])) FAIL(PG_ERR_ARG, "pg_request_sample_plan: cfg_weight[%ld][%ld] is not finite", i / T, i % T);
+    for (int b = 0; b < B; ++b) {
+        if (pl->temperature_host && !std::isfinite(pl->temperature_host[b])) FAIL(PG_ERR_ARG, "pg_request_sample_plan: temperature[%d] is not finite", b);
+        if (pl->top_k_host && pl->top_k_host[b] < 0) FAIL(PG_ERR_ARG, "pg_request_sample_plan: top_k[%d]=%d must be >= 0", b, pl->top_k_host[b]);
+        if (pl->top_p_host && !(pl->top_p_host[b] > 0.f && pl->top_p_host[b] <= 1.f)) FAIL(PG_ERR_ARG, "pg_request_sample_plan: top_p[%d]=%g must be in (0, 1]", b, (double)pl->top_p_host[b]);
+        if (pl->image_key_host && pl->image_key_host[b] < 0) FAIL(PG_ERR_ARG, "pg_request_sample_plan: image_key[%d]=%d must be >= 0", b, pl->image_key_host[b]);
+    }
+    HIPCHK(hipSetDevice(dev));
+    const size_t Bm = (size_t)cfg.max_rows / 2, total = (Bm * cfg.max_new + 4 * Bm) * 4;
+    if (!ev_plan) {          // first request: the event is created last, so a failure part-way is retried from the start by the next call
+        if (!d_plan) TRY(dalloc(&d_plan, total, false));     // no zero fill (and so no synchronisation): every array is copied here or filled by the consuming call before it is read
+        if (!h_plan) HIPCHK(hipHostMalloc((void**)&h_plan, total));
+        HIPCHK(hipEventCreateWithFlags(&ev_plan, hipEventDisableTiming));
+    }
+    if (plan_staged) HIPCHK(hipEventSynchronize(ev_plan));
+    const SamplePlanDev d = plan_dev();
+    const void* dst[5] = {d.w, d.temperature, d.top_k, d.top_p, d.key};
+    const void* src[5] = {pl->cfg_weight_host, pl->temperature_host, pl->top_k_host, pl->top_p_host, pl->image_key_host};
+    int mask = 0;
+    for (int i = 0; i < 5; ++i) {
+        if (!src[i]) continue;
+        const size_t off = (const char*)dst[i] - (const char*)d_plan, n = (i == 0 ? (size_t)B * T : (size_t)B) * 4;
+        memcpy(h_plan + off, src[i], n);
+        HIPCHK(hipMemcpyAsync(const_cast<void*>(dst[i]), h_plan + off, n, hipMemcpyHostToDevice, s));
+        mask |= 1 << i;
+    }
+    HIPCHK(hipEventRecord(ev_plan, s));
+    plan_staged = true;
+    plan_req.B = B; plan_req.T = T; plan_req.mask = mask;
+    plan_req.temp.assign(pl->temperature_host ? pl->temperature_host : nullptr, pl->temperature_host ? pl->temperature_host + B : nullptr);
+    plan_req.top_k.assign(pl->top_k_host ? pl->top_k_host : nullptr, pl->top_k_host ? pl->top_k_host + B : nullptr);
+    plan_req.top_p.assign(pl->top_p_host ? pl->top_p_host : nullptr, pl->top_p_host ? pl->top_p_host + B : nullptr);
+    plan_req.pending = true;
+    return PG_OK;
+}
+
 int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_p, uint64_t seed, const int32_t* force_tok,
                             const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s) {
     const TokenRequests q = take_requests();      // the one-shot log-prob and stats requests: consumed whatever this call answers
     const bool score = q.lp_out != nullptr, stats = q.stats;
+    const bool plan = plan_req.pending; plan_req.pending = false;      // pg_request_sample_plan: one-shot in the same way
     if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(PG_ERR_ARG, "top_k=%d must be >= 0 and top_p=%g in (0, 1]", top_k, (double)top_p);
     if (!prefilled) FAIL(PG_ERR_STATE, "pg_decode_image_tokens before pg_prefill");
     if (kv8 && !fuse_rope) FAIL(PG_ERR_ARG, "the FP8 KV cache needs the fused decode attention (fuse_rope)");
@@ -420,8 +469,21 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     if (score && lanes_opt == 2) FAIL(PG_ERR_ARG, "token log-probs do not support lanes = 2");
     if (stats && q.ts.capacity < (int64_t)(R / 2) * T) FAIL(PG_ERR_ARG, "token stats: capacity %lld positions is below B * T = %lld", (long long)q.ts.capacity, (long long)(R / 2) * T);
     if (stats && lanes_opt == 2) FAIL(PG_ERR_ARG, "token stats do not support lanes = 2");
+    if (plan && (plan_req.B != R / 2 || plan_req.T != T)) FAIL(PG_ERR_ARG, "sample plan: requested for B=%d, T=%d, the call has B=%d, T=%d", plan_req.B, plan_req.T, R / 2, T);
+    if (plan && lanes_opt == 2) FAIL(PG_ERR_ARG, "sample plans do not support lanes = 2");
     HIPCHK(hipSetDevice(dev));
     const int B = R / 2;
+    // the route of a planned call, from the host copies: filtered when any image is sampled with an active top-k / top-p
+    bool plan_filtered = false;
+    if (plan) {
+        for (int b = 0; b < B; ++b) {
+            const float tb = plan_req.temp.empty() ? temp : plan_req.temp[b];
+            const int kb = plan_req.top_k.empty() ? top_k : plan_req.top_k[b];
+            const float pb = plan_req.top_p.empty() ? top_p : plan_req.top_p[b];
+            plan_filtered |= tb > 0.f && (kb > 0 || pb < 1.f);
+        }
+        if (plan_filtered && cfg.img_vocab > SEL_MAXV) FAIL(PG_ERR_ARG, "sample plan: a filtered image needs img_vocab <= %d (got %d)", SEL_MAXV, cfg.img_vocab);
+    }
     TRY(reserve_requests(q));
     const bool stored = score || stats;                                   // the step also leaves the row the draw is made from in the row workspace
     // Lanes: at large batch the rows are split into two independent chains on two streams so one
@@ -433,8 +495,8 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     if (R % 4 || (long)decode_part_elems <= 0) nl = 1;
     const bool graph = use_graph && !time_attn && T > 2;
     // top-k / top-p only act on sampled draws (greedy ignores them, as HF's warpers do)
-    const bool filtered = temp > 0.f && (top_k > 0 || top_p < 1.f);
-    if (filtered) {
+    const bool filtered = plan ? plan_filtered : temp > 0.f && (top_k > 0 || top_p < 1.f);
+    if (filtered && !plan) {
         if (cfg.img_vocab > SEL_MAXV) FAIL(PG_ERR_CAPACITY, "top-k / top-p sampler supports img_vocab <= %d (got %d)", SEL_MAXV, cfg.img_vocab);
     }
     if ((filtered || stored) && !cfg_mix) TRY(dalloc(&cfg_mix, (size_t)(cfg.max_rows / 2) * cfg.img_vocab * 4, false));
@@ -453,13 +515,20 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
         toc(st, TC_HEAD, ((double)G * Hh + (double)cfg.img_vocab * G) * (double)esz);
         sa.logits_partial = v.part; sa.S = v.S_last; sa.slab = v.slab_last; sa.x = v.x; sa.n_dec = v.d_ndec; sa.b_off = v.r0 / 2;
         tic(st);
-        if (filtered) launch_cfg_sample_filtered(st, sa, v.rows / 2, v.cfg_pv, v.cfg_pi, v.cfg_mix);
-        else {
-            if (stored) launch_cfg_store(st, sa, v.rows / 2, v.cfg_mix);    // the filtered route already leaves the mixed rows in cfg_mix
-            launch_cfg_sample(st, sa, v.rows / 2, v.cfg_pv, v.cfg_pi);
+        if (plan) {          // the planned instantiations of the same launches
+            SampleArgsPlan pa{}; static_cast<SampleArgs&>(pa) = sa; pa.plan = plan_dev();
+            launch_cfg_sample_plan(st, pa, v.rows / 2, filtered, stored, v.cfg_pv, v.cfg_pi, v.cfg_mix);
+            if (score) launch_token_logprob_image_plan(st, pa, v.rows / 2, v.cfg_mix, d_logprob);
+            if (stats) launch_token_stats_image_plan(st, pa, v.rows / 2, v.cfg_mix, stats_out(q.ts.n_alt));
+        } else {
+            if (filtered) launch_cfg_sample_filtered(st, sa, v.rows / 2, v.cfg_pv, v.cfg_pi, v.cfg_mix);
+            else {
+                if (stored) launch_cfg_store(st, sa, v.rows / 2, v.cfg_mix);    // the filtered route already leaves the mixed rows in cfg_mix
+                launch_cfg_sample(st, sa, v.rows / 2, v.cfg_pv, v.cfg_pi);
+            }
+            if (score) launch_token_logprob_image(st, sa, v.rows / 2, v.cfg_mix, d_logprob);
+            if (stats) launch_token_stats_image(st, sa, v.rows / 2, v.cfg_mix, stats_out(q.ts.n_alt));
         }
-        if (score) launch_token_logprob_image(st, sa, v.rows / 2, v.cfg_mix, d_logprob);
-        if (stats) launch_token_stats_image(st, sa, v.rows / 2, v.cfg_mix, stats_out(q.ts.n_alt));
         toc(st, TC_SAMPLE, (double)v.S_last * v.rows * cfg.img_vocab * 4.0);
         tc_on = false;
     };
@@ -486,6 +555,8 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
         sp.has_force = force_tok != nullptr; sp.has_mask = force_mask != nullptr; sp.img_off = rng_image_offset;
         sp.top_k = top_k; sp.top_p = top_p;
         launch_set_sample_params(ws, d_sparams, sp);
+        if (plan) HIPCHK(hipStreamWaitEvent(ws, ev_plan, 0));      // the request may have staged its arrays on another stream
+        if (plan) launch_plan_fill(ws, plan_dev(), plan_req.mask, B, T, cfgw, temp, top_k, top_p, rng_image_offset);      // the arrays the plan left out
         if (force_tok) HIPCHK(hipMemcpyAsync(d_force_tok, force_tok, (size_t)B * T * 4, hipMemcpyDeviceToDevice, ws));
         if (force_mask) HIPCHK(hipMemcpyAsync(d_force_mask, force_mask, (size_t)B * T, hipMemcpyDeviceToDevice, ws));
     }
@@ -499,7 +570,8 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
                                     (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch, (int64_t)skip_attn, (int64_t)filtered,
                                     (int64_t)group_rows,         // replica geometry: never replay a graph across different aliasing
                                     (int64_t)score,              // the scored step holds two more launches
-                                    (int64_t)(stats ? 1 + q.ts.n_alt : 0)};      // the stats step one more (and the store, if score did not bring it)
+                                    (int64_t)(stats ? 1 + q.ts.n_alt : 0),       // the stats step one more (and the store, if score did not bring it)
+                                    (int64_t)plan};              // a plan is present: the planned instantiations (its values come from device memory)
         for (; i < T - 1; ++i) { TRY(graph_step(gexec, gkey, key, ws, [&] { return iteration(true); })); n_dec_host++; }
     } else {
         for (; i < T - 1; ++i) { TRY(iteration(true)); n_dec_host++; }

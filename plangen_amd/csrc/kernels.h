@@ -218,6 +218,16 @@ struct SampleArgs {
     int b_off, B_total;                                           // this launch covers images [b_off, b_off + gridDim) of B_total
 };
 void launch_set_sample_params(hipStream_t s, SampleParams* dst, SampleParams v);
+// Sample plan (pg_request_sample_plan; definition: include/plangen_hip.h): per-image sampler parameters and a per-(image, step) guidance weight in
+// device memory, indexed by the GLOBAL image bg = b + b_off: w [B_total, T], temperature / top_k / top_p / key [B_total].  Every array is present (the
+// library fills the ones a request left out with the call's scalars; key defaults to bg + img_off).  The planned instantiations of the kernels that read
+// sampler parameters take the *Plan structs below; a call without a plan launches the plain instantiations with the plain structs, as before.
+struct SamplePlanDev { const float* w; const float* temperature; const int32_t* top_k; const float* top_p; const int32_t* key; };      // T: p->T (device memory, like every per-call value)
+struct SampleArgsPlan : SampleArgs { SamplePlanDev plan; };
+// bit i of mask: array i (w, temperature, top_k, top_p, key) was given by the request and is already in place.  Fills the others.
+void launch_plan_fill(hipStream_t s, const SamplePlanDev& d, int mask, int B, int T, float cfg_weight, float temperature, int top_k, float top_p, int img_off);
+// the planned step: filtered = some image of the plan is sampled with top_k > 0 or top_p < 1 (decided on the host); stored = also leave the mixed rows in mix
+void launch_cfg_sample_plan(hipStream_t s, const SampleArgsPlan& a, int B, bool filtered, bool stored, float* scratch_v, int* scratch_i, float* mix);
 // scratch: >= 16*B floats and ints
 void launch_cfg_sample(hipStream_t s, const SampleArgs& a, int B, float* scratch_v, int* scratch_i);
 // top-k / top-p sampler (temperature > 0; p->top_k, p->top_p): the scan writes the CFG-mixed rows to mix [B, V] (V <= SEL_MAXV),
@@ -232,6 +242,7 @@ struct FilterArgs {
     const int32_t* n_dec; int b_off;
 };
 void launch_cfg_sample_filtered(hipStream_t s, const SampleArgs& a, int B, float* scratch_v, int* scratch_i, float* mix);
+struct FilterArgsPlan : FilterArgs { SamplePlanDev plan; };
 void launch_sample_filter(hipStream_t s, const float* rows, int B, int V, float temperature, int top_k, float top_p, uint8_t* keep);
 // text token: argmax over vocab of (sum_s partial) per row + EOS bookkeeping, writes out[b, step] (int64) and next-token embedding into x.
 // Per-call parameters (device memory, like SampleParams): temperature <= 0 is the greedy argmax; temperature > 0 draws by Gumbel-max over
@@ -304,6 +315,8 @@ void launch_token_logprob_op(hipStream_t s, const float* rows, int B, int V, con
 // the CFG-mixed rows of this step -> mix [B, V] (cfg_scan_kernel<true>; nothing else is written except the logits_out tap's own values)
 void launch_cfg_store(hipStream_t s, const SampleArgs& a, int B, float* mix);
 void launch_token_logprob_image(hipStream_t s, const SampleArgs& a, int B, const float* mix, float* out);
+struct LogprobArgsPlan : LogprobArgs { const float* plan_temperature; };      // [B_total]: the image loop under a sample plan
+void launch_token_logprob_image_plan(hipStream_t s, const SampleArgsPlan& a, int B, const float* mix, float* out);
 // the reduced text rows of this step (EOS ban and, with d != null, the automaton's mask applied) -> mix [B, V] (the TEXT_STORE scan).  It
 // also leaves chunk maxima in scratch_v / scratch_i: launch it BEFORE the step's own scan, which overwrites them with its winners.
 void launch_text_store(hipStream_t s, const TextArgs& a, const TextDfaArgs* d, int B, float* scratch_v, int* scratch_i, float* mix);
@@ -323,6 +336,8 @@ struct StatsArgs {
 };
 void launch_token_stats_op(hipStream_t s, const float* rows, int B, int V, const int32_t* tok, float temperature, const TokenStatsOut& o);
 void launch_token_stats_image(hipStream_t s, const SampleArgs& a, int B, const float* mix, const TokenStatsOut& o);
+struct StatsArgsPlan : StatsArgs { const float* plan_temperature; };          // as LogprobArgsPlan
+void launch_token_stats_image_plan(hipStream_t s, const SampleArgsPlan& a, int B, const float* mix, const TokenStatsOut& o);
 void launch_token_stats_text(hipStream_t s, const TextArgs& a, int B, const float* mix, const TokenStatsOut& o);
 // Fused lm_head + log-softmax at a target (score_head.hip; contract and geometry in its header): X bf16 [rows, K], W bf16 [V, K] row-major,
 // row_idx int32 [n] or null (identity), target int32 [n] -> out fp32 [n].  part: >= head_logprob_ws_bytes(n, V, K) bytes of workspace

@@ -501,15 +501,27 @@ __device__ __forceinline__ float gumbel_perturb(float mixed, float invT, uint64_
     return mixed * invT - __logf(-__logf(uu));
 }
 // STORE (filtered sampler): also write the CFG-mixed row to mix [B, V] and leave the draw to cfg_select_kernel
-template <bool STORE>
-__global__ __launch_bounds__(256) void cfg_scan_kernel(SampleArgs a, float* __restrict__ pv, int* __restrict__ pi, float* __restrict__ mix) {
+// PLAN (pg_request_sample_plan): the block's image reads its own temperature, key and this step's weight from the plan's device arrays, once,
+// in front of the loop; everything else is the same code.  The plain instantiations take the plain SampleArgs.
+template <bool STORE, bool PLAN = false>
+__global__ __launch_bounds__(256) void cfg_scan_kernel(typename std::conditional<PLAN, SampleArgsPlan, SampleArgs>::type a, float* __restrict__ pv,
+                                                       int* __restrict__ pi, float* __restrict__ mix) {
     __shared__ float sv[4]; __shared__ int si[4];
     const int b = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x, step = *a.n_dec;
     const int bg = b + a.b_off, B = a.B_total;            // global image index (lane-independent results)
     const int per = (a.V + CFG_CHUNKS - 1) / CFG_CHUNKS, v0 = ch * per, v1 = min(a.V, v0 + per);
     const long rc = (long)(2 * b) * a.V, ru = (long)(2 * b + 1) * a.V;
     float best = -INFINITY; int bi = 0x7fffffff;
-    const float temperature = a.p->temperature, cfg_weight = a.p->cfg_weight;
+    float temperature, cfg_weight; uint64_t stream;
+    if constexpr (PLAN) {
+        const int T = a.p->T;
+        temperature = a.plan.temperature[bg];
+        cfg_weight = a.plan.w[(long)bg * T + (step < T ? step : T - 1)];
+        stream = (uint64_t)a.plan.key[bg] * 1000003ull + step;
+    } else {
+        temperature = a.p->temperature; cfg_weight = a.p->cfg_weight;
+        stream = (uint64_t)(bg + a.p->img_off) * 1000003ull + step;
+    }
     const uint64_t seed = a.p->seed;
     const float invT = temperature > 0.f ? 1.f / temperature : 1.f;
     // four vocabulary entries per thread per pass, ALL their loads (bias, cond / uncond row of every slab) issued before the first use
@@ -552,7 +564,7 @@ __global__ __launch_bounds__(256) void cfg_scan_kernel(SampleArgs a, float* __re
                 float mixed = u + cfg_weight * (c - u);
                 if (a.logits_out) a.logits_out[((long)step * B + bg) * a.V + v] = mixed;
                 if (STORE) { mix[(long)b * a.V + v] = mixed; continue; }
-                if (temperature > 0.f) mixed = gumbel_perturb(mixed, invT, seed, (uint64_t)(bg + a.p->img_off) * 1000003ull + step, v);
+                if (temperature > 0.f) mixed = gumbel_perturb(mixed, invT, seed, stream, v);
                 if (mixed > best) { best = mixed; bi = v; }
             }
         }
@@ -640,7 +652,11 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
     const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)(v >> 32), o, 64);
     return ((unsigned long long)hi << 32) | lo;
 }
-__global__ __launch_bounds__(SEL_THREADS) void cfg_select_kernel(FilterArgs f) {
+// PLAN: image b + b_off takes its temperature, (top_k, top_p) and key from the plan.  A greedy image (temperature <= 0) ignores its filter and is the
+// plain first-index argmax of the row, an image with (0, 1) keeps everything: both leave the winner the unfiltered scan would leave (nothing to
+// choose from -> the out-of-range index that cfg_pick_kernel clamps, not the filtered form's token 0).
+template <bool PLAN>
+__global__ __launch_bounds__(SEL_THREADS) void cfg_select_kernel(typename std::conditional<PLAN, FilterArgsPlan, FilterArgs>::type f) {
     __shared__ float vals[SEL_MAXV];
     __shared__ uint32_t hist[256];
     __shared__ unsigned long long mhist[256];
@@ -648,9 +664,17 @@ __global__ __launch_bounds__(SEL_THREADS) void cfg_select_kernel(FilterArgs f) {
     __shared__ unsigned long long s_z, s_above;
     __shared__ float wv[SEL_THREADS / 64]; __shared__ int wi[SEL_THREADS / 64];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, V = f.V;
-    const float temperature = f.p ? f.p->temperature : f.temperature;
-    const int top_k = f.p ? f.p->top_k : f.top_k;
-    const float top_p = f.p ? f.p->top_p : f.top_p;
+    float temperature; int top_k; float top_p;
+    if constexpr (PLAN) {
+        const int bg = b + f.b_off;
+        temperature = f.plan.temperature[bg];
+        const bool greedy = !(temperature > 0.f);
+        top_k = greedy ? 0 : f.plan.top_k[bg]; top_p = greedy ? 1.f : f.plan.top_p[bg];
+    } else {
+        temperature = f.p ? f.p->temperature : f.temperature;
+        top_k = f.p ? f.p->top_k : f.top_k;
+        top_p = f.p ? f.p->top_p : f.top_p;
+    }
     const float invT = temperature > 0.f ? 1.f / temperature : 1.f;
     const float* row = f.mix + (long)b * V;
     if (tid == 0) { s_max = 0; s_z = 0; }
@@ -756,14 +780,16 @@ __global__ __launch_bounds__(SEL_THREADS) void cfg_select_kernel(FilterArgs f) {
     uint64_t seed = 0, stream = 0;
     if (f.pv) {
         const int step = *f.n_dec;
-        seed = f.p->seed; stream = (uint64_t)(b + f.b_off + f.p->img_off) * 1000003ull + step;
+        seed = f.p->seed;
+        if constexpr (PLAN) stream = (uint64_t)f.plan.key[b + f.b_off] * 1000003ull + step;
+        else stream = (uint64_t)(b + f.b_off + f.p->img_off) * 1000003ull + step;
     }
     for (int v = tid; v < V; v += SEL_THREADS) {
         const float mv = vals[v];
         const bool kept = sel_key(mv, invT) >= tau;
         if (f.keep) f.keep[(long)b * V + v] = kept;
         if (f.pv && kept) {
-            const float g = gumbel_perturb(mv, invT, seed, stream, v);
+            const float g = (PLAN && !(temperature > 0.f)) ? mv : gumbel_perturb(mv, invT, seed, stream, v);
             if (g > best) { best = g; bi = v; }
         }
     }
@@ -780,7 +806,7 @@ __global__ __launch_bounds__(SEL_THREADS) void cfg_select_kernel(FilterArgs f) {
         if (tid == 0) {
             v = wv[0]; i = wi[0];
             for (int w = 1; w < SEL_THREADS / 64; ++w) argmax_combine(v, i, wv[w], wi[w]);
-            if (i == 0x7fffffff) i = 0;          // nothing kept (every entry -inf / NaN): token 0
+            if (i == 0x7fffffff && !(PLAN && top_k <= 0 && !(top_p < 1.f))) i = 0;          // nothing kept (every entry -inf / NaN): token 0
         }
         f.pv[b * CFG_CHUNKS + tid] = v; f.pi[b * CFG_CHUNKS + tid] = i;
     }
@@ -789,13 +815,40 @@ void launch_cfg_sample_filtered(hipStream_t s, const SampleArgs& a, int B, float
     hipLaunchKernelGGL(cfg_scan_kernel<true>, dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i, mix);
     FilterArgs f{};
     f.mix = mix; f.V = a.V; f.p = a.p; f.pv = scratch_v; f.pi = scratch_i; f.n_dec = a.n_dec; f.b_off = a.b_off;
-    hipLaunchKernelGGL(cfg_select_kernel, dim3(B), dim3(SEL_THREADS), 0, s, f);
+    hipLaunchKernelGGL(cfg_select_kernel<false>, dim3(B), dim3(SEL_THREADS), 0, s, f);
     hipLaunchKernelGGL(cfg_pick_kernel, dim3(B), dim3(256), 0, s, a, scratch_v, scratch_i);
+}
+// The planned step.  Filtered route: store scan -> planned select -> pick (the mixed rows are in mix afterwards).  Otherwise: [store scan ->] scan -> pick.
+void launch_cfg_sample_plan(hipStream_t s, const SampleArgsPlan& a, int B, bool filtered, bool stored, float* scratch_v, int* scratch_i, float* mix) {
+    const SampleArgs& base = a;
+    if (filtered || stored) hipLaunchKernelGGL((cfg_scan_kernel<true, true>), dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i, mix);
+    if (filtered) {
+        FilterArgsPlan f{};
+        f.mix = mix; f.V = a.V; f.p = a.p; f.pv = scratch_v; f.pi = scratch_i; f.n_dec = a.n_dec; f.b_off = a.b_off; f.plan = a.plan;
+        hipLaunchKernelGGL(cfg_select_kernel<true>, dim3(B), dim3(SEL_THREADS), 0, s, f);
+    } else hipLaunchKernelGGL((cfg_scan_kernel<false, true>), dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i, (float*)nullptr);
+    hipLaunchKernelGGL(cfg_pick_kernel, dim3(B), dim3(256), 0, s, base, scratch_v, scratch_i);
+}
+// the arrays a plan left out <- the call's scalars (key: global image index + img_off); one thread per (image, step)
+__global__ __launch_bounds__(256) void plan_fill_kernel(SamplePlanDev d, int mask, int B, int T, float cfg_weight, float temperature, int top_k, float top_p,
+                                                        int img_off) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (!(mask & 1) && i < (long)B * T) const_cast<float*>(d.w)[i] = cfg_weight;
+    if (i < B) {
+        if (!(mask & 2)) const_cast<float*>(d.temperature)[i] = temperature;
+        if (!(mask & 4)) const_cast<int32_t*>(d.top_k)[i] = top_k;
+        if (!(mask & 8)) const_cast<float*>(d.top_p)[i] = top_p;
+        if (!(mask & 16)) const_cast<int32_t*>(d.key)[i] = (int32_t)i + img_off;
+    }
+}
+void launch_plan_fill(hipStream_t s, const SamplePlanDev& d, int mask, int B, int T, float cfg_weight, float temperature, int top_k, float top_p, int img_off) {
+    const long n = (long)B * T;
+    hipLaunchKernelGGL(plan_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, mask, B, T, cfg_weight, temperature, top_k, top_p, img_off);
 }
 void launch_sample_filter(hipStream_t s, const float* rows, int B, int V, float temperature, int top_k, float top_p, uint8_t* keep) {
     FilterArgs f{};
     f.mix = rows; f.V = V; f.temperature = temperature; f.top_k = top_k; f.top_p = top_p; f.keep = keep;
-    hipLaunchKernelGGL(cfg_select_kernel, dim3(B), dim3(SEL_THREADS), 0, s, f);
+    hipLaunchKernelGGL(cfg_select_kernel<false>, dim3(B), dim3(SEL_THREADS), 0, s, f);
 }
 
 // text token (HF generate): greedy = argmax over vocab; sampled = Gumbel-max over logits / T (== multinomial(softmax(logits / T)));
@@ -1220,19 +1273,24 @@ void launch_text_constrained(hipStream_t s, const TextArgs& a, const TextDfaArgs
 // bits do not depend on how the block was scheduled.  x == max contributes exactly 1 (this is expf(0), and it keeps a row whose
 // maximum is +inf meaningful: the mass sits evenly on the +inf entries).
 #define LP_THREADS 1024
-enum { LP_OP = 0, LP_IMAGE = 1, LP_TEXT = 2 };
+enum { LP_OP = 0, LP_IMAGE = 1, LP_TEXT = 2, LP_IMAGE_PLAN = 3 };      // LP_IMAGE_PLAN: LP_IMAGE with the image's own temperature (sample plan)
+// the argument struct of a form, by specialisation: an expression over the unnamed enum in the kernel's signature would put the enum's
+// compiler-made name into the mangled symbol, and the host and device passes number such names differently
+template <int FORM> struct LpArgsOf { using type = LogprobArgs; };
+template <> struct LpArgsOf<3> { using type = LogprobArgsPlan; };
 template <int FORM>
-__global__ __launch_bounds__(LP_THREADS) void token_logprob_kernel(LogprobArgs a) {
+__global__ __launch_bounds__(LP_THREADS) void token_logprob_kernel(typename LpArgsOf<FORM>::type a) {
     __shared__ float red[LP_THREADS / 64];
     __shared__ float s_m;
     const int b = blockIdx.x, tid = threadIdx.x, V = a.V;
     int tok; float temperature; float* dst;
     if (FORM == LP_OP) { tok = a.tok32[b]; temperature = a.temperature; dst = a.out + b; }
-    else if (FORM == LP_IMAGE) {
+    else if (FORM == LP_IMAGE || FORM == LP_IMAGE_PLAN) {
         const int step = *a.n_dec, T = a.sp->T;
         if (step >= T) return;
         const long at = (long)(b + a.b_off) * T + step;
-        tok = a.tok32[at]; temperature = a.sp->temperature; dst = a.out + at;
+        tok = a.tok32[at]; dst = a.out + at;
+        if constexpr (FORM == LP_IMAGE_PLAN) temperature = a.plan_temperature[b + a.b_off]; else temperature = a.sp->temperature;
     } else {
         const int step = *a.n_dec, max_new = a.tp->max_new;
         if (step >= max_new) return;
@@ -1313,6 +1371,11 @@ void launch_token_logprob_image(hipStream_t s, const SampleArgs& a, int B, const
     LogprobArgs l{};
     l.rows = mix; l.V = a.V; l.sp = a.p; l.tok32 = a.out_tok; l.n_dec = a.n_dec; l.b_off = a.b_off; l.out = out;
     hipLaunchKernelGGL(token_logprob_kernel<LP_IMAGE>, dim3(B), dim3(LP_THREADS), 0, s, l);
+}
+void launch_token_logprob_image_plan(hipStream_t s, const SampleArgsPlan& a, int B, const float* mix, float* out) {
+    LogprobArgsPlan l{};
+    l.rows = mix; l.V = a.V; l.sp = a.p; l.tok32 = a.out_tok; l.n_dec = a.n_dec; l.b_off = a.b_off; l.out = out; l.plan_temperature = a.plan.temperature;
+    hipLaunchKernelGGL(token_logprob_kernel<LP_IMAGE_PLAN>, dim3(B), dim3(LP_THREADS), 0, s, l);
 }
 void launch_text_store(hipStream_t s, const TextArgs& a, const TextDfaArgs* d, int B, float* scratch_v, int* scratch_i, float* mix) {
     if (d) {

@@ -9,13 +9,14 @@
 //         xor butterfly over the wave; serial sum of the 16 wave sums), so logprob has that kernel's bits; t = sum expf(x - m) (x - m)
 //         and the count of x_v > x_tok are reduced in the same fixed shape.  x = -inf adds 0 to s and t; x == m adds exactly 1 and 0.
 // H = logf(s) - t / s.  m = +inf: only the +inf entries count (s = k, t = 0, H = logf(k)).  No finite entry: H = 0, rank = V.
+#include <type_traits>
 #include "kernels.h"
 
 #define TS_THREADS 1024
 #define TS_WAVES (TS_THREADS / 64)
 #define TS_NALT 8
 #define TS_NOIDX 0x7fffffff
-enum { TS_OP = 0, TS_IMAGE = 1, TS_TEXT = 2 };
+enum { TS_OP = 0, TS_IMAGE = 1, TS_TEXT = 2, TS_IMAGE_PLAN = 3 };      // TS_IMAGE_PLAN: TS_IMAGE with the image's own temperature (sample plan)
 
 __device__ __forceinline__ bool ts_better(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
 
@@ -51,8 +52,12 @@ __device__ __forceinline__ void ts_wave_merge(float (&v)[TS_NALT], int (&i)[TS_N
     }
 }
 
+// the argument struct of a form, by specialisation (no expression over the unnamed enum in the kernel's signature: its compiler-made name would
+// enter the mangled symbol, and the host and device passes number such names differently)
+template <int FORM> struct TsArgsOf { using type = StatsArgs; };
+template <> struct TsArgsOf<3> { using type = StatsArgsPlan; };
 template <int FORM, bool ALT>
-__global__ __launch_bounds__(TS_THREADS) void token_stats_kernel(StatsArgs a) {
+__global__ __launch_bounds__(TS_THREADS) void token_stats_kernel(typename TsArgsOf<FORM>::type a) {
     __shared__ float red[TS_WAVES];
     __shared__ float red_t[TS_WAVES];
     __shared__ int red_c[TS_WAVES];
@@ -62,11 +67,12 @@ __global__ __launch_bounds__(TS_THREADS) void token_stats_kernel(StatsArgs a) {
     const int b = blockIdx.x, tid = threadIdx.x, V = a.V, n_alt = a.o.n_alt;
     int tok; float temperature; long at;
     if (FORM == TS_OP) { tok = a.tok32[b]; temperature = a.temperature; at = b; }
-    else if (FORM == TS_IMAGE) {
+    else if (FORM == TS_IMAGE || FORM == TS_IMAGE_PLAN) {
         const int step = *a.n_dec, T = a.sp->T;
         if (step >= T) return;
         at = (long)(b + a.b_off) * T + step;
-        tok = a.tok32[at]; temperature = a.sp->temperature;
+        tok = a.tok32[at];
+        if constexpr (FORM == TS_IMAGE_PLAN) temperature = a.plan_temperature[b + a.b_off]; else temperature = a.sp->temperature;
     } else {
         const int step = *a.n_dec, max_new = a.tp->max_new;
         if (step >= max_new) return;
@@ -194,8 +200,8 @@ __global__ __launch_bounds__(TS_THREADS) void token_stats_kernel(StatsArgs a) {
     }
 }
 
-template <int FORM>
-static void ts_launch(hipStream_t s, int B, const StatsArgs& l) {
+template <int FORM, class A>
+static void ts_launch(hipStream_t s, int B, const A& l) {
     if (l.o.n_alt > 0) hipLaunchKernelGGL((token_stats_kernel<FORM, true>), dim3(B), dim3(TS_THREADS), 0, s, l);
     else hipLaunchKernelGGL((token_stats_kernel<FORM, false>), dim3(B), dim3(TS_THREADS), 0, s, l);
 }
@@ -208,6 +214,11 @@ void launch_token_stats_image(hipStream_t s, const SampleArgs& a, int B, const f
     StatsArgs l{};
     l.rows = mix; l.V = a.V; l.sp = a.p; l.tok32 = a.out_tok; l.n_dec = a.n_dec; l.b_off = a.b_off; l.o = o;
     ts_launch<TS_IMAGE>(s, B, l);
+}
+void launch_token_stats_image_plan(hipStream_t s, const SampleArgsPlan& a, int B, const float* mix, const TokenStatsOut& o) {
+    StatsArgsPlan l{};
+    l.rows = mix; l.V = a.V; l.sp = a.p; l.tok32 = a.out_tok; l.n_dec = a.n_dec; l.b_off = a.b_off; l.o = o; l.plan_temperature = a.plan.temperature;
+    ts_launch<TS_IMAGE_PLAN>(s, B, l);
 }
 void launch_token_stats_text(hipStream_t s, const TextArgs& a, int B, const float* mix, const TokenStatsOut& o) {
     StatsArgs l{};

@@ -529,21 +529,26 @@ class Engine:
     def decode_image_tokens(self, T: Optional[int] = None, cfg_weight: float = 5.0, temperature: float = 0.0,
                             seed: int = 0, force_tokens: Optional[torch.Tensor] = None,
                             force_mask: Optional[torch.Tensor] = None, return_logits: bool = False,
-                            top_k: int = 0, top_p: float = 1.0, return_logprobs: bool = False, return_stats=False):
+                            top_k: int = 0, top_p: float = 1.0, return_logprobs: bool = False, return_stats=False, plan=None):
         """The fused CFG decode loop.  top_k / top_p filter the sampled draws (temperature > 0; HF order temperature ->
         top-k -> top-p); (0, 1.0) is the unfiltered sampler.  return_logprobs: also fp32 [B, T], the log-probability of every emitted
         token under softmax(mixed / temperature) before the filters (``pg_request_token_logprobs``); with ``force_mask = zeros`` it is the
         log-likelihood of ``force_tokens``.  return_stats (True, or an int n_alt in 1..8): also (last) the dict of ``_request_stats``
-        over [B, T]: the emitted tokens' entropy, rank and top-n_alt alternatives (``pg_request_token_stats``).  Semantics:
-        include/plangen_hip.h."""
+        over [B, T]: the emitted tokens' entropy, rank and top-n_alt alternatives (``pg_request_token_stats``).  plan (a
+        ``guidance.SamplePlan``): per-image temperature / top_k / top_p / RNG key and a per-(image, step) guidance weight in place of the
+        scalars (``pg_request_sample_plan``; an array the plan leaves out takes the scalar).  Semantics: include/plangen_hip.h."""
         T = self.cfg.img_tokens if T is None else T
         B = self.R // 2
+        if plan is not None and plan.B != B:
+            raise PlanGenError(f"decode_image_tokens: the plan holds {plan.B} images, the batch has {B}")
         out = torch.zeros((B, T), dtype=torch.int32, device=self.device)
         lp = self._request_logprobs((B, T)) if return_logprobs else None
         stt = self._request_stats((B, T), return_stats) if _wants_stats(return_stats) else None
         ft = self._dev(force_tokens, torch.int32) if force_tokens is not None else None
         fm = self._dev(force_mask, torch.uint8) if force_mask is not None else None
         lg = torch.zeros((T, B, self.cfg.img_vocab), dtype=torch.float32, device=self.device) if return_logits else None
+        if plan is not None:      # last of the preparations: nothing between the request and the call that consumes it can raise
+            self._request_sample_plan(plan, T)
         if int(top_k) == 0 and float(top_p) == 1.0:
             self._check(self.lib.pg_decode_image_tokens(self.h, T, float(cfg_weight), float(temperature), int(seed),
                                                         self._p(ft), self._p(fm), self._p(out), self._p(lg), self.stream),
@@ -555,6 +560,32 @@ class Engine:
         self._keep = [ft, fm, out, lg, lp, stt]
         res = (out,) + ((lg,) if return_logits else ()) + ((lp,) if return_logprobs else ()) + ((stt,) if stt is not None else ())
         return res if len(res) > 1 else res[0]
+
+    def _request_sample_plan(self, plan, T: int):
+        """``pg_request_sample_plan`` for the next image decode (the library copies the host arrays before it returns)."""
+        arrs = plan.arrays(T)
+        ptr = lambda a: C.c_void_p(0 if a is None else a.ctypes.data)
+        req = _lib.pg_sample_plan(*(ptr(a) for a in arrs), plan.B, T)
+        self._check(self.lib.pg_request_sample_plan(self.h, C.byref(req), self.stream), "pg_request_sample_plan")
+
+    @staticmethod
+    def cfg_sample_plan_op(partial, S, slab, bias, V, B, out_tok, logits_out, embed_table, x, H, w, temperature, top_k, top_p, key, seed, T, step,
+                           b_off=0, B_total=None, force_tok=None, force_mask=None, filtered=False, stored=False, stream=None) -> int:
+        """``pg_diag_op_cfg_sample_plan`` (diagnostics library): one step of the image sampler under a sample plan, on caller-given device
+        tensors -- the slabs ``partial``, ``out_tok`` int32 [B_total, T], ``logits_out`` fp32 [T, B_total, V] or None, and the plan's device
+        arrays ``w`` fp32 [B_total, T], ``temperature`` fp32 / ``top_k`` int32 / ``top_p`` fp32 / ``key`` int32 [B_total].  Returns the
+        status code (0: PG_OK); the stream is synchronised."""
+        d = _lib.load_diag()
+        fn = d.pg_diag_op_cfg_sample_plan
+        _P, _I = C.c_void_p, C.c_int
+        fn.restype = C.c_int
+        fn.argtypes = [_I, _I, _P, _I, C.c_long, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, C.c_uint64, _I, _I, _I, _I, _P]
+        ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        B_total = b_off + B if B_total is None else B_total
+        stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        return fn(int(bool(filtered)), int(bool(stored)), ptr(partial), S, slab, ptr(bias), V, B, ptr(force_tok), ptr(force_mask), ptr(out_tok),
+                  ptr(logits_out), ptr(embed_table), ptr(x), H, ptr(w), ptr(temperature), ptr(top_k), ptr(top_p), ptr(key), int(seed), T, step,
+                  b_off, B_total, stream)
 
     def _request_logprobs(self, shape) -> torch.Tensor:
         """``pg_request_token_logprobs`` for the next decode / generate call: the fp32 tensor that call fills (NaN where it writes nothing)."""

@@ -90,7 +90,8 @@ class System:
     and text_temperature / text_top_k / text_top_p (sampled layout / caption decode, greedy when absent); select_best (parallel_size > 1:
     keep each prompt's most probable replica, off when absent) and layout_best_of (stage 1: draw N layouts per row and keep the most
     probable, 1 when absent); score_gt_layout (plan / uni_2stage / mmu: also score batch['gt_grounding'], see score_layouts; off when absent);
-    score_gt_image (uni / uni_2stage: also score batch['image'], see score_images; off when absent).
+    score_gt_image (uni / uni_2stage: also score batch['image'], see score_images; off when absent); the sample-plan keys cfg_schedule /
+    cfg_weight_end / cfg_weights / same_noise / cfg_weight_in_box / temperatures / top_ks / top_ps (see build_sample_plan; off when absent).
     """
 
     def __init__(self, cfg: PlanGenConfig, engine: Engine, args: Optional[SimpleNamespace] = None, codec=None):
@@ -100,6 +101,7 @@ class System:
         self.codec = codec                # tokenizer (plangen_amd.textproc.HFCodec / TagWordCodec); None: ids only
         self.last_generated_tokens = None
         self.last_token_stats = None      # args.token_stats: the stats dict [B, T] of the last t2i (+ "summary": image_token_stats_summary)
+        self.last_sample_plan = None      # the sample-plan cfg keys: the record of the last t2i's plan (build_sample_plan), None when no key is set
         self.last_selection = None        # select_best: dict(replica int64 [B0], score fp32 [B0], scores fp32 [p, B0]) of the last t2i
         self.vl_gpt = MultiModalityCausalLM(engine)
         self.args = args or SimpleNamespace(seed=cfg.seed, parallel_size=1, cfg_weight=cfg.cfg_weight,
@@ -123,14 +125,15 @@ class System:
                      gt_labels: Optional[torch.Tensor] = None, force_tokens: Optional[torch.Tensor] = None,
                      n_tokens: Optional[int] = None, return_logits: bool = False, top_k: Optional[int] = None,
                      top_p: Optional[float] = None, replicas: int = 1, alias: bool = True, return_logprobs: bool = False,
-                     return_stats=False):
+                     return_stats=False, plan=None):
         """The 576-step CFG loop, fused on device (one pg_prefill + one pg_decode_image_tokens).
         tokens int32 [2B, L] CFG-interleaved ids, mask [2B, L+T].  temperature<=0 -> greedy.
         top_k / top_p (default: self.args, else off) filter the sampled draws.
         replicas > 1: ``tokens`` is the UN-replicated batch [2B0, L] and the loop runs on replicas * 2B0 rows (row t * 2B0 + r = replica t of
         row r) with every prompt prefilled once (Engine.prefill_replicated); mask / edit_region / gt_labels / force_tokens are the replicated ones.
         return_logprobs: the emitted tokens' log-probabilities fp32 [B, T] are appended to what is returned.
-        return_stats (True, or an int n_alt): the ``Engine._request_stats`` dict over [B, T] is appended (last)."""
+        return_stats (True, or an int n_alt): the ``Engine._request_stats`` dict over [B, T] is appended (last).
+        plan (``guidance.SamplePlan`` over the B images of the loop): per-image sampler parameters, per-step guidance weights."""
         top_k = getattr(self.args, "top_k", 0) if top_k is None else top_k
         top_p = getattr(self.args, "top_p", 1.0) if top_p is None else top_p
         L = tokens.shape[1]
@@ -148,6 +151,8 @@ class System:
         lpkw = {"return_logprobs": True} if return_logprobs else {}        # without it: exactly the call made before scores existed
         if _stats_on(return_stats):
             lpkw["return_stats"] = return_stats
+        if plan is not None:
+            lpkw["plan"] = plan
         return self.engine.decode_image_tokens(n_tokens, cfg_weight, temperature, seed, ft, fm, return_logits, top_k=top_k, top_p=top_p, **lpkw)
 
     @staticmethod
@@ -165,6 +170,74 @@ class System:
                 hit = ((rank < k) & f).sum(1)
                 s[name] = [h / c if c else None for h, c in zip(hit.cpu().tolist(), n.cpu().tolist())]
         return s
+
+    PLAN_KEYS = ("cfg_schedule", "cfg_weight_end", "cfg_weights", "same_noise", "cfg_weight_in_box", "temperatures", "top_ks", "top_ps")
+
+    def plan_keys_set(self) -> List[str]:
+        """The sample-plan cfg keys that are on (cfg_schedule other than 'constant', same_noise true, any other key not None)."""
+        a = self.args
+        on = []
+        for k in self.PLAN_KEYS:
+            v = getattr(a, k, None)
+            if (k == "cfg_schedule" and v not in (None, "constant")) or (k == "same_noise" and bool(v)) or (k not in ("cfg_schedule", "same_noise") and v is not None):
+                on.append(k)
+        return on
+
+    def _prompt_box_texts(self, row_ids) -> List[str]:
+        """The box texts of the ``<ref>..</ref><box>..</box>`` items of one prompt row, found by their tag ids as ``attribute_layout`` finds them."""
+        from .textproc import layout_spans
+        if self.codec is None:
+            raise PlanGenError("cfg_weight_in_box needs a tokenizer (System(codec=...)): the layout's boxes are found by their tag ids")
+        tags = {t: self.codec.token_id(t) for t in ("<ref>", "</ref>", "<box>", "</box>")}
+        return [self.decode_text(row_ids[a:z]) for a, z in layout_spans(row_ids, tags, "box")]
+
+    def build_sample_plan(self, cond_rows, p: int, cfg_weight: float, T: int):
+        """The plan of the cfg keys for ``p`` replicas of the prompts ``cond_rows`` (one id list per prompt) in the replica layout (image t * B0 + i =
+        replica t of prompt i), or (None, None) when no key is set.  Replica t's weight runs by ``cfg_schedule`` from cfg_weights[t] (else cfg_weight)
+        to cfg_weight_end (else it stays); positions inside a box of prompt i's layout take cfg_weight_in_box; temperatures / top_ks / top_ps are
+        per-replica lists; same_noise gives the replicas of prompt i the RNG key of its first replica.  Returns (SamplePlan, record for the batch JSON)."""
+        import numpy as np
+        from . import guidance as G
+        on = self.plan_keys_set()
+        if not on:
+            return None, None
+        a = self.args
+        B0 = len(cond_rows)
+        def per_replica(key):
+            v = getattr(a, key, None)
+            if v is None:
+                return None
+            v = list(v)
+            if len(v) != p:
+                raise PlanGenError(f"{key} holds {len(v)} entries, parallel_size is {p}")
+            return v
+        kind = getattr(a, "cfg_schedule", None) or "constant"
+        starts = per_replica("cfg_weights") or [float(cfg_weight)] * p
+        end = getattr(a, "cfg_weight_end", None)
+        ends = [float(s) if end is None or kind == "constant" else float(end) for s in starts]
+        in_box = getattr(a, "cfg_weight_in_box", None)
+        share = [0.0] * (B0 * p)
+        w = None
+        if kind != "constant" or getattr(a, "cfg_weights", None) is not None or end is not None or in_box is not None:
+            g = self.cfg.grid
+            w = np.stack([G.schedule(kind, starts[t], ends[t], T) for t in range(p) for _ in range(B0)])
+            if in_box is not None:
+                if T != g * g:
+                    raise PlanGenError(f"cfg_weight_in_box needs a full image of {g * g} positions (got T = {T})")
+                for i, row in enumerate(cond_rows):
+                    cells = G.box_weights(self._prompt_box_texts(row), g, 1.0, 0.0, bool(getattr(a, "use_centerhw", False))) > 0
+                    for t in range(p):
+                        w[t * B0 + i, cells] = np.float32(in_box)
+                        share[t * B0 + i] = float(cells.mean())
+        rep = lambda v: None if v is None else np.repeat(np.asarray(v), B0)
+        key = None
+        if bool(getattr(a, "same_noise", False)):
+            key = np.tile(np.arange(B0, dtype=np.int64) + int(getattr(self.engine, "rng_image_offset", 0)), p)
+        plan = G.SamplePlan(cfg_weight=w, temperature=rep(per_replica("temperatures")), top_k=rep(per_replica("top_ks")), top_p=rep(per_replica("top_ps")),
+                            image_key=key)
+        record = dict(schedule=kind, weight_start=[float(v) for v in starts], weight_end=ends, weight_in_box=None if in_box is None else float(in_box),
+                      in_box_share=share, same_noise=bool(getattr(a, "same_noise", False)), keys=on)
+        return plan, record
 
     @staticmethod
     def select_best_replicas(logprobs: torch.Tensor, p: int, scored: Optional[torch.Tensor] = None):
@@ -256,9 +329,15 @@ class System:
                 # the extra replicas get an all-ones region (= nothing forced); the returned mask_image stays the B-row one (:557-560).
                 gt_labels = torch.cat([gt_labels] * p)
                 force_region = torch.cat([edit_region] + [torch.ones_like(edit_region)] * (p - 1))
+        # the sample-plan cfg keys (all off by default, and then nothing changes): one plan over the B0 * p images of the loop
+        L0 = tokens.shape[1]
+        plan, self.last_sample_plan = (None, None)
+        if self.plan_keys_set():
+            cond_rows = [tokens[2 * i][mask[2 * i, :L0].bool()].tolist() for i in range(B0)]
+            plan, self.last_sample_plan = self.build_sample_plan(cond_rows, p, cfg_weight, self.image_token_num_per_image)
         toks = self.sample_image(tokens, mask, cfg_weight, temperature, a.seed,
                                  force_region if gt_labels is not None else None, gt_labels, top_k=top_k, top_p=top_p,
-                                 replicas=p if share else 1, **({"return_logprobs": True} if select else {}),
+                                 replicas=p if share else 1, **({"return_logprobs": True} if select else {}), **({"plan": plan} if plan is not None else {}),
                                  **({"return_stats": want_stats} if stats_on else {}))
         if stats_on:
             toks, stats = toks[:-1], toks[-1]
@@ -412,6 +491,8 @@ class System:
             if self.last_token_stats is not None:
                 out["image_token_stats"] = self.last_token_stats["summary"]
                 out["image_entropy"] = self.last_token_stats["entropy"].view(-1, self.cfg.grid, self.cfg.grid)
+            if self.last_sample_plan is not None:
+                out["sample_plan"] = self.last_sample_plan
             if self.last_selection is not None:
                 out["pr_replica"], out["pr_score"] = self.last_selection["replica"], self.last_selection["score"]
             out["pr_image"] = dec.float()
@@ -445,7 +526,7 @@ class System:
                     extra["gt_layout_logprob"] = out["gt_layout_logprob"]
                 if "gt_image_logprob" in out:
                     extra["gt_image_logprob"] = out["gt_image_logprob"]
-                for k in ("image_token_stats", "text_token_stats"):
+                for k in ("image_token_stats", "text_token_stats", "sample_plan"):
                     if k in out:
                         extra[k] = out[k]
                 if "image_entropy" in out:
@@ -494,6 +575,10 @@ class System:
         Returns dict(sum, mean, n_tokens: one entry per image; logprobs fp32 [B, T], every position): mean = sum / n_tokens (0.0 when
         nothing is scored)."""
         eng = self.engine
+        if self.plan_keys_set():
+            raise PlanGenError(f"score_images / score_gt_image: the fused score head has one cfg_weight and cannot follow a sample plan ({', '.join(self.plan_keys_set())} "
+                               "set).  Score under a plan with the decode loop instead: Engine.decode_image_tokens(force_tokens=codes, "
+                               "force_mask=zeros, return_logprobs=True, plan=...)")
         if not eng._c.with_vq_encoder:
             raise PlanGenError("score_images VQ-encodes batch['image']: the engine must be created with_vq_encoder=True")
         a = self.args

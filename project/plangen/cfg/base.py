@@ -27,6 +27,15 @@ score_gt_image = False                 # uni / uni_2stage: also write gt_image_l
 token_stats = False                    # True, or an int n_alt in 1..8: per-token uncertainty from the decode loops, reduced on the device. uni / uni_2stage / t2i: image_token_stats (per image: mean entropy, mean rank, share of rank-0 positions; with use_teacher_forcing also top1 / top5 over edit_region == 0) in the batch JSON and <batch_idx>_entropy.npy fp32 [B * parallel_size, grid, grid]; plan / uni_2stage stage 1 / mmu: text_token_stats (per row: mean entropy, with n_alt > 0 the alternatives' ids) (an extension beyond the reference)
 layout_attribution = False             # uni / uni_2stage (bf16): after generating, one more teacher-forced prefill on the generated tokens reports the attention the image positions put on every <ref>..</ref><box>..</box> item of the prompt: layout_attribution (per item: phrase, inside = share of its mass inside its own box) in the batch JSON and <batch_idx>_attribution.npy fp32 [B, items, grid, grid] (layer mean; NaN rows where a prompt has fewer items); the prompt capacity grows by the image's length (an extension beyond the reference)
 use_centerhw = False                   # base.py:100: boxes are cx,cy,h,w instead of x1,y1,x2,y2 (read by layout_attribution's box cells)
+# sample plans (an extension beyond the reference; all off by default, and then nothing changes): per-replica sampler parameters and per-step guidance in ONE batch
+cfg_schedule = 'constant'              # 'constant' | 'linear' | 'cosine': the guidance weight runs from cfg_weight to cfg_weight_end over the image positions
+cfg_weight_end = None                  # the schedule's last weight (None: the weight stays)
+cfg_weights = None                     # list of length parallel_size: replica t of every prompt starts at cfg_weights[t] (with and without share_replicas)
+same_noise = False                     # the replicas of a prompt share their RNG key: they differ by their plan only
+cfg_weight_in_box = None               # positions whose cell centre lies in a box of the row's layout use this weight instead of the scheduled one
+temperatures = None                    # per-replica lists like cfg_weights (temperature <= 0: that replica is greedy)
+top_ks = None
+top_ps = None
 use_numhw_tokens = False               # base.py:65: add <h0> <w0> ... <h99> <w99> to the tokenizer (plangen_base.py:120-127)
 use_special_tokens = False             # base.py:69: add <grounding> </grounding> <box> </box> <ref> </ref> to the tokenizer (plangen_base.py:110-118)
 use_teacher_forcing = False            # base.py:36

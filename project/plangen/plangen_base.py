@@ -98,6 +98,7 @@ class System(_HotPath):
                                                    token_stats=getattr(args, "token_stats", False),
                                                    layout_attribution=bool(getattr(args, "layout_attribution", False)),
                                                    use_centerhw=bool(getattr(args, "use_centerhw", False)),
+                                                   **{k: getattr(args, k, None) for k in _HotPath.PLAN_KEYS},
                                                    use_teacher_forcing=args.use_teacher_forcing, share_replicas=cfg.share_replicas,
                                                    debug_max_seq_len=args.debug_max_seq_len, janus_hw=args.janus_hw,
                                                    neg_prompt=getattr(args, "neg_prompt", ""),
