@@ -301,42 +301,24 @@ void launch_text_constrained(hipStream_t s, const TextArgs& a, const TextDfaArgs
 // TEXT_STORE -> txt_mix: the instantiations the top-k / top-p samplers already use) and, after the pick, one 1024-thread block per row reads
 // that row and the emitted token and writes one float: x = y * (1 / temperature) (temperature > 0, else y), NaN as -inf, a max pass and a
 // sum-of-expf pass over the L2-resident row with 16-byte loads, fixed-shape reductions (the result does not depend on scheduling).
-struct LogprobArgs {
-    const float* rows; int V;                                     // [gridDim, V] fp32
-    const SampleParams* sp;                                       // image loop: temperature and T from device memory
-    const TextParams* tp;                                         // text loop: temperature, max_new and eos from device memory
-    float temperature;                                            // operator: from the host
-    const int32_t* tok32;                                         // operator: [gridDim]; image loop: out_tok [B, T]
-    const int64_t* tok64;                                         // text loop: out [B, max_new]
-    const int32_t* n_dec; int b_off;                              // loops: device step counter, first image of this launch
-    float* out;                                                   // operator: [gridDim]; loops: [B, T] / [B, max_new] library-owned
-};
+// The kernels' argument structs and the row reader both reducers share: stored_row.h.
 void launch_token_logprob_op(hipStream_t s, const float* rows, int B, int V, const int32_t* tok, float temperature, float* out);
 // the CFG-mixed rows of this step -> mix [B, V] (cfg_scan_kernel<true>; nothing else is written except the logits_out tap's own values)
 void launch_cfg_store(hipStream_t s, const SampleArgs& a, int B, float* mix);
 void launch_token_logprob_image(hipStream_t s, const SampleArgs& a, int B, const float* mix, float* out);
-struct LogprobArgsPlan : LogprobArgs { const float* plan_temperature; };      // [B_total]: the image loop under a sample plan
 void launch_token_logprob_image_plan(hipStream_t s, const SampleArgsPlan& a, int B, const float* mix, float* out);
 // the reduced text rows of this step (EOS ban and, with d != null, the automaton's mask applied) -> mix [B, V] (the TEXT_STORE scan).  It
 // also leaves chunk maxima in scratch_v / scratch_i: launch it BEFORE the step's own scan, which overwrites them with its winners.
 void launch_text_store(hipStream_t s, const TextArgs& a, const TextDfaArgs* d, int B, float* scratch_v, int* scratch_i, float* mix);
 void launch_token_logprob_text(hipStream_t s, const TextArgs& a, int B, const float* mix, float* out);
 // Per-token uncertainty (pg_request_token_stats / pg_op_token_stats; definition: include/plangen_hip.h; kernel: token_stats.hip).  The second
-// reducer on the stored-row route: the same rows, x, token, step and destination index as LogprobArgs, and per position the log-probability
+// reducer on the stored-row route: the same rows, x, token, step and destination index (stored_row.h), and per position the log-probability
 // (the bits of token_logprob_kernel), the entropy of softmax(x), the emitted token's rank and the n_alt <= 8 largest entries (ids,
 // log-probabilities).  Any output pointer may be null (skipped).  The loops' forms index every array as the log-prob buffer is indexed
 // ([B, T] / [B, max_new], alternatives [.., n_alt]); a finished text row gets logprob 0, entropy 0, rank 0, alt_tok -1, alt_logprob 0.
 struct TokenStatsOut { float* logprob; float* entropy; int32_t* rank; int32_t* alt_tok; float* alt_logprob; int n_alt; };
-struct StatsArgs {
-    const float* rows; int V;                                     // [gridDim, V] fp32
-    const SampleParams* sp; const TextParams* tp; float temperature;      // as LogprobArgs
-    const int32_t* tok32; const int64_t* tok64;
-    const int32_t* n_dec; int b_off;
-    TokenStatsOut o;
-};
 void launch_token_stats_op(hipStream_t s, const float* rows, int B, int V, const int32_t* tok, float temperature, const TokenStatsOut& o);
 void launch_token_stats_image(hipStream_t s, const SampleArgs& a, int B, const float* mix, const TokenStatsOut& o);
-struct StatsArgsPlan : StatsArgs { const float* plan_temperature; };          // as LogprobArgsPlan
 void launch_token_stats_image_plan(hipStream_t s, const SampleArgsPlan& a, int B, const float* mix, const TokenStatsOut& o);
 void launch_token_stats_text(hipStream_t s, const TextArgs& a, int B, const float* mix, const TokenStatsOut& o);
 // Fused lm_head + log-softmax at a target (score_head.hip; contract and geometry in its header): X bf16 [rows, K], W bf16 [V, K] row-major,

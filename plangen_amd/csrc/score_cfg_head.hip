@@ -2,7 +2,7 @@
 // a classifier-free-guidance mix between the accumulators and the fold.  Per scored position i (c = cond_idx[i], u = uncond_idx[i], t = target[i]):
 //
 //   yc_v = sum_k X[c][k] * W[v][k] + bias[v],   yu_v likewise with X[u]     (bf16 operands, fp32 accumulation on the MFMA units; bias fp32 or absent)
-//   y_v  = yu_v + cfg_weight * (yc_v - yu_v)                                (fp32, the expression of cfg_scan_kernel in llm_kernels.hip)
+//   y_v  = yu_v + cfg_weight * (yc_v - yu_v)                                (fp32, the expression of cfg_scan_kernel in sampler.hip)
 //   x_v  = y_v * (1 / temperature)  when temperature > 0, else y_v          (the rounded fp32 product)
 //   out[i] = (x_t - m) - logf(sum_v expf(x_v - m)),  m = max_v x_v;   t outside [0, V) gives -inf
 //

@@ -1,4 +1,4 @@
-// Body of text_scan_kernel / text_scan_dfa_kernel (llm_kernels.hip): included once in each, NOT a header to include elsewhere.
+// Body of text_scan_kernel / text_scan_dfa_kernel (sampler.hip): included once in each, NOT a header to include elsewhere.
 // In scope: TextArgs a; pv, pi, mix; MODE, TAP; constexpr bool DFA; const TextDfaArgs* d (null when DFA is off).
     __shared__ float sv[4]; __shared__ int si[4];
     const int ch = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, step = *a.n_dec;

@@ -1,22 +1,22 @@
-// Per-token uncertainty of one stored row per block (kernels.h StatsArgs; the definition is in include/plangen_hip.h, pg_request_token_stats):
+// Per-token uncertainty of one stored row per block (stored_row.h StatsArgs; the definition is in include/plangen_hip.h, pg_request_token_stats):
 // the emitted token's log-probability, the entropy of the row's softmax, the token's rank and the N largest entries with their
-// log-probabilities.  The second reducer on the stored-row route: same rows, same x = y * (1 / temperature) (NaN as -inf), same way of
-// finding the token, the step and the destination as token_logprob_kernel (llm_kernels.hip), one 1024-thread block per row.
+// log-probabilities.  The second reducer on the stored-row route: it finds its position and reads its row through stored_row.h, as
+// token_logprob_kernel (sampler.hip) does, one 1024-thread block per row.
 // Pass 1: the maximum m and, when alternatives are asked for, every thread's 8 best (value desc, index asc) in a sorted register list;
 //         the lists are merged per wave by 8 rounds of "butterfly for the best head, its owner pops it", the 16 wave lists go through
 //         LDS and wave 0 merges them the same way.  Indices are unique, so the order is total and the result does not depend on timing.
-// Pass 2: s = sum expf(x - m) with the term order of token_logprob_kernel (per thread: aligned vectors, head, tail, each in index order;
-//         xor butterfly over the wave; serial sum of the 16 wave sums), so logprob has that kernel's bits; t = sum expf(x - m) (x - m)
+// Pass 2: s = sum expf(x - m) with the term order of token_logprob_kernel (StoredRow::each; xor butterfly over the wave; serial sum of
+//         the 16 wave sums), so logprob has that kernel's bits; t = sum expf(x - m) (x - m)
 //         and the count of x_v > x_tok are reduced in the same fixed shape.  x = -inf adds 0 to s and t; x == m adds exactly 1 and 0.
 // H = logf(s) - t / s.  m = +inf: only the +inf entries count (s = k, t = 0, H = logf(k)).  No finite entry: H = 0, rank = V.
 #include <type_traits>
 #include "kernels.h"
+#include "stored_row.h"
 
-#define TS_THREADS 1024
-#define TS_WAVES (TS_THREADS / 64)
+#define TS_THREADS SR_THREADS
+#define TS_WAVES SR_WAVES
 #define TS_NALT 8
 #define TS_NOIDX 0x7fffffff
-enum { TS_OP = 0, TS_IMAGE = 1, TS_TEXT = 2, TS_IMAGE_PLAN = 3 };      // TS_IMAGE_PLAN: TS_IMAGE with the image's own temperature (sample plan)
 
 __device__ __forceinline__ bool ts_better(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
 
@@ -52,12 +52,8 @@ __device__ __forceinline__ void ts_wave_merge(float (&v)[TS_NALT], int (&i)[TS_N
     }
 }
 
-// the argument struct of a form, by specialisation (no expression over the unnamed enum in the kernel's signature: its compiler-made name would
-// enter the mangled symbol, and the host and device passes number such names differently)
-template <int FORM> struct TsArgsOf { using type = StatsArgs; };
-template <> struct TsArgsOf<3> { using type = StatsArgsPlan; };
 template <int FORM, bool ALT>
-__global__ __launch_bounds__(TS_THREADS) void token_stats_kernel(typename TsArgsOf<FORM>::type a) {
+__global__ __launch_bounds__(TS_THREADS) void token_stats_kernel(typename SrArgsOf<FORM, StatsArgs, StatsArgsPlan>::type a) {
     __shared__ float red[TS_WAVES];
     __shared__ float red_t[TS_WAVES];
     __shared__ int red_c[TS_WAVES];
@@ -66,64 +62,31 @@ __global__ __launch_bounds__(TS_THREADS) void token_stats_kernel(typename TsArgs
     __shared__ int s_ti[TS_WAVES][TS_NALT];
     const int b = blockIdx.x, tid = threadIdx.x, V = a.V, n_alt = a.o.n_alt;
     int tok; float temperature; long at;
-    if (FORM == TS_OP) { tok = a.tok32[b]; temperature = a.temperature; at = b; }
-    else if (FORM == TS_IMAGE || FORM == TS_IMAGE_PLAN) {
-        const int step = *a.n_dec, T = a.sp->T;
-        if (step >= T) return;
-        at = (long)(b + a.b_off) * T + step;
-        tok = a.tok32[at];
-        if constexpr (FORM == TS_IMAGE_PLAN) temperature = a.plan_temperature[b + a.b_off]; else temperature = a.sp->temperature;
-    } else {
-        const int step = *a.n_dec, max_new = a.tp->max_new;
-        if (step >= max_new) return;
-        const int64_t* o = a.tok64 + (long)b * max_new;
-        at = (long)b * max_new + step;
-        // a finished row emits eos and a row finishes by emitting eos: the row was finished BEFORE this step iff its previous token is eos
-        if (step > 0 && o[step - 1] == (int64_t)a.tp->eos) {
-            if (tid == 0) {
-                if (a.o.logprob) a.o.logprob[at] = 0.f;
-                if (a.o.entropy) a.o.entropy[at] = 0.f;
-                if (a.o.rank) a.o.rank[at] = 0;
-            }
-            if (tid < n_alt) {
-                if (a.o.alt_tok) a.o.alt_tok[at * n_alt + tid] = -1;
-                if (a.o.alt_logprob) a.o.alt_logprob[at * n_alt + tid] = 0.f;
-            }
-            return;
+    const int where = sr_locate<FORM>(a, b, tok, temperature, at);
+    if (where == SR_FINISHED) {
+        if (tid == 0) {
+            if (a.o.logprob) a.o.logprob[at] = 0.f;
+            if (a.o.entropy) a.o.entropy[at] = 0.f;
+            if (a.o.rank) a.o.rank[at] = 0;
         }
-        tok = (int)o[step]; temperature = a.tp->temperature;
+        if (tid < n_alt) {
+            if (a.o.alt_tok) a.o.alt_tok[at * n_alt + tid] = -1;
+            if (a.o.alt_logprob) a.o.alt_logprob[at * n_alt + tid] = 0.f;
+        }
     }
-    const float invT = temperature > 0.f ? 1.f / temperature : 1.f;
-    const float* row = a.rows + (long)b * V;
-    auto xval = [&](float y) -> float { const float x = temperature > 0.f ? __fmul_rn(y, invT) : y; return x != x ? -INFINITY : x; };   // the rounded product, never fused into x - m
-    int head = (int)(((16u - (uint32_t)((uintptr_t)row & 15u)) & 15u) >> 2);
-    if (head > V) head = V;
-    const int nv = (V - head) >> 2, tail0 = head + nv * 4;
-    const f32x4* rv = (const f32x4*)(row + head);
-    constexpr int IT = 8;
+    if (where != SR_LIVE) return;
+    const StoredRow sr(a.rows + (long)b * V, V, temperature);
 
     // ---- pass 1: the maximum and the 8 best
     float lv[TS_NALT]; int li[TS_NALT];
 #pragma unroll
     for (int k = 0; k < TS_NALT; ++k) { lv[k] = -INFINITY; li[k] = TS_NOIDX; }
     float m = -INFINITY;
-    for (int i0 = tid; i0 < nv; i0 += IT * TS_THREADS) {
-        f32x4 c[IT];
-#pragma unroll
-        for (int it = 0; it < IT; ++it) { const int i = i0 + it * TS_THREADS; c[it] = rv[i < nv ? i : nv - 1]; }   // clamped: a repeat does not move a maximum
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = i0 + it * TS_THREADS;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float x = xval(c[it][j]);
-                m = fmaxf(m, x);
-                if (ALT && i < nv) ts_insert(lv, li, x, head + i * 4 + j);  // a repeat must not enter the list twice
-            }
-        }
-    }
-    for (int v = tid; v < head; v += TS_THREADS) { const float x = xval(row[v]); m = fmaxf(m, x); if (ALT) ts_insert(lv, li, x, v); }
-    for (int v = tail0 + tid; v < V; v += TS_THREADS) { const float x = xval(row[v]); m = fmaxf(m, x); if (ALT) ts_insert(lv, li, x, v); }
+    sr.template each<true>(tid, [&](float y, int v, bool fresh) {
+        const float x = sr.xval(y);
+        m = fmaxf(m, x);
+        if (ALT && fresh) ts_insert(lv, li, x, v);                          // a repeat must not enter the list twice
+    });
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
     float fv[TS_NALT]; int fi[TS_NALT];                                    // the block's 8 best: valid in wave 0 after the merge
@@ -150,30 +113,16 @@ __global__ __launch_bounds__(TS_THREADS) void token_stats_kernel(typename TsArgs
     m = s_m;
 
     // ---- pass 2: s (the term order of token_logprob_kernel), t and the rank count
-    const float xt = (tok >= 0 && tok < V) ? xval(row[tok]) : -INFINITY;
+    const float xt = (tok >= 0 && tok < V) ? sr.xval(sr.row[tok]) : -INFINITY;
     float sum = 0.f, tsum = 0.f; int cnt = 0;
-    auto acc = [&](float y) {
-        const float x = xval(y);
+    sr.template each<false>(tid, [&](float y, int, bool) {
+        const float x = sr.xval(y);
         const float d = x - m;
         const float e = x == m ? 1.f : expf(d);
         sum += e;
         if (x != m && e > 0.f) tsum += e * d;                              // x == m: d counts as 0 (also when m is infinite); e == 0: nothing
         cnt += x > xt ? 1 : 0;
-    };
-    for (int i0 = tid; i0 < nv; i0 += IT * TS_THREADS) {
-        f32x4 c[IT];
-#pragma unroll
-        for (int it = 0; it < IT; ++it) { const int i = i0 + it * TS_THREADS; c[it] = rv[i < nv ? i : nv - 1]; }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            if (i0 + it * TS_THREADS < nv) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc(c[it][j]);
-            }
-        }
-    }
-    for (int v = tid; v < head; v += TS_THREADS) acc(row[v]);
-    for (int v = tail0 + tid; v < V; v += TS_THREADS) acc(row[v]);
+    });
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { sum += __shfl_xor(sum, o, 64); tsum += __shfl_xor(tsum, o, 64); cnt += __shfl_xor(cnt, o, 64); }
     if ((tid & 63) == 0) { red[tid >> 6] = sum; red_t[tid >> 6] = tsum; red_c[tid >> 6] = cnt; }
@@ -208,20 +157,20 @@ static void ts_launch(hipStream_t s, int B, const A& l) {
 void launch_token_stats_op(hipStream_t s, const float* rows, int B, int V, const int32_t* tok, float temperature, const TokenStatsOut& o) {
     StatsArgs l{};
     l.rows = rows; l.V = V; l.temperature = temperature; l.tok32 = tok; l.o = o;
-    ts_launch<TS_OP>(s, B, l);
+    ts_launch<SR_OP>(s, B, l);
 }
 void launch_token_stats_image(hipStream_t s, const SampleArgs& a, int B, const float* mix, const TokenStatsOut& o) {
     StatsArgs l{};
     l.rows = mix; l.V = a.V; l.sp = a.p; l.tok32 = a.out_tok; l.n_dec = a.n_dec; l.b_off = a.b_off; l.o = o;
-    ts_launch<TS_IMAGE>(s, B, l);
+    ts_launch<SR_IMAGE>(s, B, l);
 }
 void launch_token_stats_image_plan(hipStream_t s, const SampleArgsPlan& a, int B, const float* mix, const TokenStatsOut& o) {
     StatsArgsPlan l{};
     l.rows = mix; l.V = a.V; l.sp = a.p; l.tok32 = a.out_tok; l.n_dec = a.n_dec; l.b_off = a.b_off; l.o = o; l.plan_temperature = a.plan.temperature;
-    ts_launch<TS_IMAGE_PLAN>(s, B, l);
+    ts_launch<SR_IMAGE_PLAN>(s, B, l);
 }
 void launch_token_stats_text(hipStream_t s, const TextArgs& a, int B, const float* mix, const TokenStatsOut& o) {
     StatsArgs l{};
     l.rows = mix; l.V = a.V; l.tp = a.p; l.tok64 = a.out; l.n_dec = a.n_dec; l.o = o;
-    ts_launch<TS_TEXT>(s, B, l);
+    ts_launch<SR_TEXT>(s, B, l);
 }

@@ -239,6 +239,41 @@ def test_operator_on_crafted_rows(tiny_cfg, tiny_weights):
     ew.close()
 
 
+@pytest.fixture(scope="module")
+def wide_engine(tiny_cfg):
+    """A handle whose text AND image vocabularies admit rows up to SEL_MAXV = 16 384 (operators only: no weights loaded)."""
+    from plangen_amd.config import PlanGenConfig
+    from plangen_amd.engine import Engine
+    e = Engine(PlanGenConfig(**dict(tiny_cfg.model_dict(), vocab=16384, img_vocab=16384)), dtype="f32", max_rows=2, max_prompt=8, max_new=2,
+               max_images=1)
+    yield e
+    e.close()
+
+
+@pytest.mark.parametrize("V", [17, 1000, 4100, 16384])
+def test_image_select_and_text_select_keep_the_same_set(V, wide_engine):
+    """cfg_select_kernel (pg_op_sample_filter) and text_select_kernel (pg_op_text_sample) promise one rule -- the same integer keys, the same
+    64-bit fixed-point masses -- so their kept masks are equal bit for bit, ties at the k-th value and at the top-p boundary and
+    non-finite entries included; on Gaussian rows both are the rule of sampling_filter_ref outside ambiguous(...).
+    V = 16 384 is the largest row of the image kernel and the fullest LDS candidate list of the text kernel."""
+    e = wide_engine
+    inf, nan = float("inf"), float("nan")
+    gauss = torch.randn(3, V, generator=torch.Generator().manual_seed(900 + V)) * 2.4
+    special = torch.randn(3, V, generator=torch.Generator().manual_seed(901 + V)) * 2.4
+    special[0, 1], special[0, 5], special[0, V - 1], special[0, V // 2], special[0, 11] = -inf, inf, nan, inf, nan
+    special[1] = -inf
+    special[2] = 0.375
+    for name, rows in (("gauss", gauss), ("quantised", torch.round(gauss / 0.25) * 0.25), ("special", special)):
+        for temp, k, p in ((1.0, 0, 0.9), (0.7, 50, 1.0), (1.0, 50, 0.9), (1.3, 1000, 0.95), (1.0, V, 0.5), (1.0, 1, 1.0)):
+            img = e.sample_filter(rows, temp, k, p).cpu()
+            txt = e.text_sample(rows, temp, k, p)[0].cpu()
+            assert torch.equal(img, txt), (name, V, temp, k, p, torch.nonzero(img != txt)[:8].tolist())
+            if name == "gauss":
+                amb = ambiguous(rows, temp, k, p)
+                ref = rule_keep(rows, temp, k, p)
+                assert torch.equal(img[~amb], ref[~amb]), (V, temp, k, p, torch.nonzero((img != ref) & ~amb)[:8].tolist())
+
+
 def test_execution_forms_agree_and_graph_replays_new_parameters(tiny_cfg, tiny_weights):
     e = get_engine(tiny_cfg, tiny_weights, "f32")
     ids, pad, _ = _prompt(tiny_cfg, 2, 85)

@@ -122,8 +122,8 @@ HIPCC = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shut
 @pytest.mark.skipif(not HIPCC, reason="hipcc not available")
 def test_text_sampler_kernels_compile_for_gfx950_without_scratch(tmp_path):
     """The code object's metadata (.private_segment_fixed_size) of every text_scan_kernel instantiation and of text_select_kernel."""
-    src = os.path.join(ROOT, "plangen_amd", "csrc", "llm_kernels.hip")
-    asm = str(tmp_path / "llm_kernels.s")
+    src = os.path.join(ROOT, "plangen_amd", "csrc", "sampler.hip")
+    asm = str(tmp_path / "sampler.s")
     p = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-mllvm",
                         "-amdgpu-kernarg-preload-count=16", src, "-o", asm], capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
