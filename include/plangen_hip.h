@@ -163,6 +163,38 @@ int pg_prefill_embeds(pg_handle h, const void* embeds_dev, int embeds_dtype,
                       const int32_t* pad_len_host, int R, int L, int position_mode,
                       void* hidden_out_dev, int hidden_dtype, pg_stream s);
 
+/* Continue the cached sequences with many tokens in one pass (HF: a second  model(inputs_embeds=[R, n, H], past_key_values=...)  call).
+ * cur[r] is the number of K/V slots row r holds: its prompt length plus the decode steps run since (pg_step, or T - 1 / the steps a
+ * pg_decode_image_tokens* / pg_generate_text_* loop ran: the token a loop emitted LAST was never fed back and is not in the cache).
+ * Exactly one of ids_dev int32 [R, Lx] / embeds_dev [R, Lx, hidden] (PG_F32 or PG_BF16) is given, R = the rows of the preceding
+ * prefill.  The first n_new_host[r] columns of row r are its new tokens (LEFT-aligned; columns past them are ignored).  New token i of
+ * row r takes slot cur[r] + i and RoPE position pos_off[r] + cur[r] + i -- the position rule the preceding prefill chose (position_mode)
+ * -- and attends to slots 0 .. cur[r] + i of its own row.  Only the new tokens go through the GEMMs.  Afterwards row r has length
+ * cur[r] + n_new_host[r], the step counters are zero, the input of the first gen_head / lm_head is the final-norm hidden state of each
+ * row's last new token, hidden_out_dev (may be NULL) holds all of them as [R, Lx, hidden] in hidden_dtype (unused columns zero), and
+ * every decode entry point continues exactly as after a prefill of the longer sequences; a decode call (pg_decode_image_tokens*,
+ * pg_generate_text_*, pg_step) whose steps would leave the KV slots (max_prompt + max_new) or the RoPE table is PG_ERR_CAPACITY (host
+ * checks that cannot fire after a plain prefill, whose own limits imply them).  Asynchronous on ``s``: n_new_host travels through pinned staging like pad_len_host.
+ * bf16 handles run the query-offset form of the 128-query flash kernel (flash_prefill = 0 and PG_F32 handles: the generic kernel).
+ * Nothing is launched on a refusal and the handle stays usable:
+ *   PG_ERR_STATE     before a prefill; after pg_prefill_replicated with replicas > 1; when the batch shares its negative prompt (it
+ *                    lives in row 1's slots, which the prefill attention kernels do not follow: prefill with the one-shot
+ *                    pg_set_option("uncond_shared_hint", 0));
+ *   PG_ERR_ARG       an FP8 KV handle (past keys exist only as codes); n_new_host[r] outside [1, Lx]; both or neither input pointer; a
+ *                    dtype other than PG_F32 / PG_BF16; a pending pg_request_attn_spans (consumed by this call, which cannot serve it);
+ *   PG_ERR_CAPACITY  cur[r] + n_new_host[r] exceeds the KV slots, the last position exceeds the RoPE table, or sum n_new_host exceeds
+ *                    the packed-token capacity max_rows * max_prompt. */
+int pg_prefill_extend(pg_handle h, const int32_t* ids_dev /*[R, Lx] or NULL*/, const void* embeds_dev /*[R, Lx, hidden] or NULL*/,
+                      int embeds_dtype, const int32_t* n_new_host /*[R]*/, int Lx, void* hidden_out_dev /*[R, Lx, hidden] or NULL*/,
+                      int hidden_dtype, pg_stream s);
+/* Cut row r back to its first len_host[r] slots, 1 <= len_host[r] <= cur[r] (else PG_ERR_ARG); e.g. back to the prompt after
+ * pg_generate_text_*, whose early-finished rows hold EOS filler.  Zeroes the step counters and recomputes the longest-first row order;
+ * launches only small copies.  Slots past the new length keep stale keys and are never read.  The hidden state the next sample is drawn
+ * from is NOT recomputed: a pg_prefill_extend follows before anything samples, and until it has, pg_decode_image_tokens* and
+ * pg_generate_text_* answer PG_ERR_STATE (pg_step, whose input is the caller's, is allowed).  Refuses the same handle states as
+ * pg_prefill_extend. */
+int pg_rewind(pg_handle h, const int32_t* len_host /*[R]*/, pg_stream s);
+
 /* One decode step behind  language_model.model(inputs_embeds=[R,1,H], past_key_values=...)
  * (plangen_base.py:571-577, i>0): consumes embeds_dev [R, hidden], appends K/V, writes
  * last_hidden_state [R, hidden] (after the final RMSNorm) to hidden_out_dev. */
@@ -606,7 +638,8 @@ int64_t pg_device_bytes(pg_handle h);
  * the same shape, and "kscale"/"vscale" return the scales as fp32 [max_rows, heads, slots]), "x" (residual stream), "xn", "hfin", "gen_table", "pq_table", "qbuf", "obuf",
  * "vit_feat" (SigLIP features of the last pg_vision_encode, after the final LayerNorm, compute dtype [B, P, vit_width]),
  * "score_mid" (gen_head layer-1 output of the last pg_score_image_tokens, compute dtype [rows, gen_head_dim]; PG_ERR_NAME once another
- * scoring call has reused the workspace). */
+ * scoring call has reused the workspace), "len" (int32 [max_rows]: the rows' lengths as the last prefill / pg_prefill_extend / pg_rewind
+ * set them) and "n_dec" (int32 [1]: decode steps run since; len[r] + n_dec = the K/V slots row r holds). */
 int pg_debug_read(pg_handle h, const char* name, int index, void* dst_dev, int64_t max_bytes, pg_stream s);
 
 /* Stand-alone operator entry points (unit parity tests call these through the ABI;

@@ -72,6 +72,8 @@ SYMBOLS = [
     ("pg_prefill", C.c_int, [_P, _P, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
     ("pg_prefill_replicated", C.c_int, [_P, _P, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ("pg_prefill_embeds", C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    ("pg_prefill_extend", C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int32), C.c_int, _P, C.c_int, _P]),
+    ("pg_rewind", C.c_int, [_P, C.POINTER(C.c_int32), _P]),
     ("pg_step", C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P]),
     ("pg_gen_head", C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P]),
     ("pg_gen_embed", C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),

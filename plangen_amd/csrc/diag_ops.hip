@@ -213,6 +213,37 @@ int pg_diag_op_attn_prefill(int is_bf16, int path, const void* qbuf, void* obuf,
     return launched(s);
 }
 
+// Extension attention (pg_prefill_extend) over the packed NEW tokens: path 2 = attn_extend_flash_kernel (bf16), 0 = attn_kernel mode 1.
+// len [R]: the rows' lengths after the extension; n_new [R]: new tokens per row (ignored where row_off is -1).  The packed tokens of row r must
+// be row_off[r] .. row_off[r] + n_new[r] - 1 with tok_j = len[r] - n_new[r] .. len[r] - 1.  Other arguments as pg_diag_op_attn_prefill.
+int pg_diag_op_attn_extend(int is_bf16, int path, const void* qbuf, void* obuf, const void* kc, const void* vc, const int32_t* row_off,
+                           const int32_t* len, const int32_t* n_new, const int32_t* tok_row, const int32_t* tok_j, int R, int max_new, int Ntok,
+                           int nh, int slots, float scale, pg_stream stream) {
+    if (!qbuf || !obuf || !kc || !vc || !row_off || !len || !n_new || !tok_row || !tok_j) return PG_ERR_ARG;
+    if ((path != 0 && path != 2) || (path > 0 && !is_bf16)) return PG_ERR_ARG;
+    if (R < 1 || R > kMaxGridYZ || nh < 1 || nh > kMaxGridYZ || Ntok < 1 || Ntok > 0x7fffffff / 8 || max_new < 1 || max_new > slots) return PG_ERR_ARG;
+    std::vector<int32_t> hoff, hlen, hnew, hrow, hj;
+    if (!to_host(hoff, row_off, R) || !to_host(hlen, len, R) || !to_host(hnew, n_new, R) || !to_host(hrow, tok_row, Ntok) || !to_host(hj, tok_j, Ntok)) return PG_ERR_HIP;
+    for (int m = 0; m < Ntok; ++m)
+        if (hrow[m] < 0 || hrow[m] >= R || hj[m] < 0 || hj[m] >= slots) return PG_ERR_ARG;
+    for (int r = 0; r < R; ++r) {
+        if (hoff[r] < 0) continue;
+        if (hlen[r] < 1 || hlen[r] > slots || hnew[r] < 1 || hnew[r] > hlen[r] || hnew[r] > max_new || (long)hoff[r] + hnew[r] > Ntok) return PG_ERR_ARG;
+        for (int i = 0; i < hnew[r]; ++i)
+            if (hrow[hoff[r] + i] != r || hj[hoff[r] + i] != hlen[r] - hnew[r] + i) return PG_ERR_ARG;
+    }
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    if (path == 2) {
+        launch_attn_extend_flash(s, (const bf16*)qbuf, (bf16*)obuf, (const bf16*)kc, (const bf16*)vc, row_off, len, n_new, R, max_new, nh, slots, scale);
+        return launched(s);
+    }
+    SeqState st{len, nullptr, nullptr, tok_row, tok_j, 0, 1, nullptr};
+    if (is_bf16) launch_attn<bf16>(s, (const bf16*)qbuf, (bf16*)obuf, (const bf16*)kc, (const bf16*)vc, st, 1, Ntok, nh, slots, scale);
+    else launch_attn<float>(s, (const float*)qbuf, (float*)obuf, (const float*)kc, (const float*)vc, st, 1, Ntok, nh, slots, scale);
+    return launched(s);
+}
+
 // SigLIP attention (bf16, heads of 64, non-causal): qk [B * P][2C] (q | k), vt [B][C][P] (V transposed), o [B * P][C].
 // form 1 = the 64-key tile kernel; 4 / 8 / 12 / 16 = the LDS-resident kernel with that many waves (the launcher still falls back to the
 // tile kernel when K / V^T of a head do not fit the LDS).

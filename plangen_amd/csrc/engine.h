@@ -112,6 +112,9 @@ struct pg_engine {
     int R = 0, L = 0, slots = 0; bool prefilled = false;
     int n_dec_host = 0;
     std::vector<int> h_len;
+    // pg_prefill_extend / pg_rewind: host copy of d_pos_off (written by prefill), the new-token counts of the running extension on the device
+    // (d_nnew [max_rows]; ext_nnew is non-null only while pg_prefill_extend runs its layers, like as_run) and their maximum
+    std::vector<int> h_pos_off; int32_t* d_nnew = nullptr; const int32_t* ext_nnew = nullptr; int ext_max_new = 0;
     int32_t *d_len = nullptr, *d_pos_off = nullptr, *d_ndec = nullptr, *d_tok_row = nullptr, *d_tok_j = nullptr,
             *d_tok_src = nullptr, *d_last = nullptr, *d_unf = nullptr, *d_anyunf = nullptr, *d_row_off = nullptr;
     int max_len_host = 0; bool flash_prefill = true;
@@ -286,6 +289,14 @@ struct pg_engine {
     // pad_len: [R0] rows; replicas > 1 (pg_prefill_replicated): the batch is R0 * replicas virtual rows of which only the R0 distinct ones are packed
     int prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtype, const int32_t* pad_len, int R0, int L_,
                 int pmode, void* hidden_out, int hidden_dtype, hipStream_t s, int replicas = 1, int alias = 0, bool replicated_api = false);
+    // cur[r] = h_len[r] + n_dec_host: the K/V slots row r holds.  extend: n_new_host [R] new tokens per row, left-aligned in [R, Lx]
+    bool hfin_stale = false;                                                // pg_rewind ran last: hfin belongs to the sequence it cut, nothing may sample from it
+    int max_pos_end() const { int m = 0; for (int r = 0; r < R && r < (int)h_len.size(); ++r) m = std::max(m, h_pos_off[r] + h_len[r]); return m; }   // RoPE position of the next slot, largest over the rows
+    int check_extendable(const char* who);                                  // PG_OK, or why pg_prefill_extend / pg_rewind refuse the handle's state
+    int set_lengths(const int32_t* s_len, int32_t* s_ord, hipStream_t s);   // h_len, max_len_host, the row order and zeroed step counters, host and device
+    int prefill_extend(const int32_t* ids_dev, const void* emb_dev, int emb_dtype, const int32_t* n_new_host, int Lx, void* hidden_out,
+                       int hidden_dtype, hipStream_t s);
+    int rewind(const int32_t* len_host, hipStream_t s);
     template <typename T> void gemm_residual(hipStream_t s, DecodeView& v, const T* a, const T* W, int M, int N, int K);
     template <typename T> void gemm_llm(hipStream_t s, DecodeView& v, const T* a, const T* W, int M, int N, int K, bool allow_skinny, const void* Wt = nullptr);
     template <typename T> void run_layers(hipStream_t s, DecodeView& v, int M, int mode, T* final_out, int32_t* advance = nullptr);

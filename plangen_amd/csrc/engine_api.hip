@@ -63,6 +63,15 @@ int pg_prefill_embeds(pg_handle h, const void* embeds_dev, int embeds_dtype, con
     if (!h || !embeds_dev || !pad_len_host) return PG_ERR_ARG;
     return h->prefill(nullptr, embeds_dev, embeds_dtype, pad_len_host, R, L, position_mode, hidden_out_dev, hidden_dtype, (hipStream_t)s);
 }
+int pg_prefill_extend(pg_handle h, const int32_t* ids_dev, const void* embeds_dev, int embeds_dtype, const int32_t* n_new_host, int Lx,
+                      void* hidden_out_dev, int hidden_dtype, pg_stream s) { TuneGuard _tg(h);
+    if (!h) return PG_ERR_ARG;
+    return h->prefill_extend(ids_dev, embeds_dev, embeds_dtype, n_new_host, Lx, hidden_out_dev, hidden_dtype, (hipStream_t)s);
+}
+int pg_rewind(pg_handle h, const int32_t* len_host, pg_stream s) {
+    if (!h) return PG_ERR_ARG;
+    return h->rewind(len_host, (hipStream_t)s);
+}
 int pg_step(pg_handle h, const void* embeds_dev, int embeds_dtype, void* hidden_out_dev, int hidden_dtype, pg_stream s) { TuneGuard _tg(h);
     if (!h || !embeds_dev) return PG_ERR_ARG;
     return h->step(embeds_dev, embeds_dtype, hidden_out_dev, hidden_dtype, (hipStream_t)s);
@@ -252,6 +261,8 @@ int pg_debug_read(pg_handle h, const char* name, int index, void* dst_dev, int64
     else if (nm == "pq_table") { src = h->pq_table; n = (int64_t)h->cfg.img_vocab * h->cfg.vq_z * h->esz; }
     else if (nm == "qbuf") { src = h->qbuf; n = (int64_t)h->max_tok * h->HD() * h->esz; }
     else if (nm == "score_mid" && h->sh_mid_bytes > 0) { src = h->sh_ws; n = h->sh_mid_bytes; }
+    else if (nm == "len") { src = h->d_len; n = (int64_t)h->cfg.max_rows * 4; }       // int32 [max_rows]: the rows' lengths at the last prefill / extend / rewind
+    else if (nm == "n_dec") { src = h->d_ndec; n = 4; }                                  // int32 [1]: decode steps run since
     else if (nm == "obuf") { src = h->obuf; n = (int64_t)h->max_tok * h->HD() * h->esz; }
     else if (nm == "vit_feat" && h->cfg.with_vision) {   // SigLIP features (after the final LayerNorm, compute dtype) of the last pg_vision_encode
         const int64_t P = (h->cfg.vit_img / h->cfg.vit_patch) * (h->cfg.vit_img / h->cfg.vit_patch);

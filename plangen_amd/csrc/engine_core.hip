@@ -288,6 +288,7 @@ int pg_engine::create() {
     TRY(dalloc(&d_tok_row, (size_t)max_tok * 4));
     TRY(dalloc(&d_tok_j, (size_t)max_tok * 4));
     TRY(dalloc(&d_tok_src, (size_t)max_tok * 4));
+    TRY(dalloc(&d_nnew, (size_t)cfg.max_rows * 4));
     for (int i = 0; i < 2; ++i) {
         HIPCHK(hipHostMalloc((void**)&h_stage2[i], (size_t)(3 * max_tok + 5 * cfg.max_rows + 16 + 33 * cfg.max_rows) * 4));      // + pg_request_attn_spans: pad_len | lo | hi
         HIPCHK(hipEventCreateWithFlags(&ev_stage[i], hipEventDisableTiming));

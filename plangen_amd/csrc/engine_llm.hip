@@ -105,7 +105,11 @@ void pg_engine::run_layers(hipStream_t s, DecodeView& v, int M, int mode, T* fin
             tic(s);
             bool done = false;
             if constexpr (std::is_same<T, bf16>::value) {
-                if (mode == 1 && flash_prefill) {
+                if (mode == 1 && flash_prefill && ext_nnew) {       // pg_prefill_extend: the packed tokens are the rows' new tokens, behind cached slots
+                    launch_attn_extend_flash(s, (const bf16*)v.qbuf, (bf16*)v.obuf, (const bf16*)kc(v, li), (const bf16*)vc(v, li), d_row_off, v.d_len,
+                                             ext_nnew, v.rows, ext_max_new, cfg.n_heads, slots, scale);
+                    done = true;
+                } else if (mode == 1 && flash_prefill) {
                     launch_attn_prefill_flash(s, (const bf16*)v.qbuf, (bf16*)v.obuf, (const bf16*)kc(v, li), (const bf16*)vc(v, li), d_row_off, v.d_len,
                                               v.rows, max_len_host, cfg.n_heads, slots, scale);
                     done = true;
@@ -248,7 +252,7 @@ int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtyp
     int32_t* const hs = h_stage2[stage_sel];
     if (stage_used[stage_sel]) HIPCHK(hipEventSynchronize(ev_stage[stage_sel]));
     int ntok = 0;
-    h_len.assign(R_, 0);
+    h_len.assign(R_, 0); h_pos_off.assign(R_, 0);
     int32_t* s_len = hs; int32_t* s_off = hs + cfg.max_rows; int32_t* s_last = hs + 2 * cfg.max_rows;
     int32_t* s_roff = hs + 3 * cfg.max_rows; int32_t* s_ord = hs + 4 * cfg.max_rows; max_len_host = 0;
     int32_t* s_row = hs + 5 * cfg.max_rows; int32_t* s_j = s_row + max_tok; int32_t* s_src = s_j + max_tok;
@@ -257,7 +261,7 @@ int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtyp
     for (int r = 0; r < R_; ++r) {
         const int pad = pad_of(r);
         const int len = L_ - pad;
-        h_len[r] = len; s_len[r] = len; s_off[r] = pmode == 0 ? pad : 0;
+        h_len[r] = len; s_len[r] = len; s_off[r] = pmode == 0 ? pad : 0; h_pos_off[r] = s_off[r];
         if (owner(r) != r) { s_last[r] = s_last[owner(r)]; s_roff[r] = -1; continue; }   // aliases its owner's prompt (owner(r) < r)
         s_roff[r] = ntok; if (len > max_len_host) max_len_host = len;
         for (int j = 0; j < len; ++j) { s_row[ntok] = r; s_j[ntok] = j; s_src[ntok] = r * L_ + pad + j; ++ntok; }
@@ -324,7 +328,113 @@ int pg_engine::prefill(const int32_t* ids_dev, const void* emb_dev, int emb_dtyp
     HIPCHK(hipEventRecord(ev_p1, s));
     have_prefill_t = true;
     HIPCHK(hipGetLastError());
-    prefilled = true;
+    prefilled = true; hfin_stale = false;
+    return PG_OK;
+}
+
+// ---- pg_prefill_extend / pg_rewind: continue or shorten the cached sequences.  cur[r] = h_len[r] + n_dec_host is what row r holds: its prompt
+// plus the decode steps run since (the token a loop emitted last was never fed back and has no slot).
+int pg_engine::check_extendable(const char* who) {
+    if (!prefilled) FAIL(PG_ERR_STATE, "%s before pg_prefill", who);
+    if (replicas_n > 1) FAIL(PG_ERR_STATE, "%s after pg_prefill_replicated with replicas > 1: replicas alias their owner's prompt slots", who);
+    if (shared_len > 0)
+        FAIL(PG_ERR_STATE, "%s: the batch shares its negative prompt (it lives in row 1's slots, which the prefill attention kernels do not follow); "
+                           "prefill with the one-shot pg_set_option(\"uncond_shared_hint\", 0)", who);
+    if (kv8) FAIL(PG_ERR_ARG, "%s: an FP8 KV cache keeps past keys as codes only and prefill attention needs bf16", who);
+    return PG_OK;
+}
+// The rows' new lengths (s_len, pinned staging) become the row-set geometry: h_len, max_len_host, the longest-first order of the decode attention
+// (into s_ord, same staging buffer) and step counters at zero.  Small copies and memsets only; the caller records the staging event behind them.
+int pg_engine::set_lengths(const int32_t* s_len, int32_t* s_ord, hipStream_t s) {
+    max_len_host = 0;
+    for (int r = 0; r < R; ++r) { h_len[r] = s_len[r]; s_ord[r] = r; if (h_len[r] > max_len_host) max_len_host = h_len[r]; }
+    std::stable_sort(s_ord, s_ord + R, [&](int a, int b) { return h_len[a] > h_len[b]; });      // shared_len = 0 and no replica groups here
+    order_valid = true; order_rows = R; n_dec_host = 0;
+    HIPCHK(hipMemcpyAsync(d_row_order, s_ord, (size_t)R * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_len, s_len, (size_t)R * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(d_ndec, 0, 64, s));
+    HIPCHK(hipMemsetAsync(d_ndec2, 0, 64, s));
+    return PG_OK;
+}
+
+int pg_engine::prefill_extend(const int32_t* ids_dev, const void* emb_dev, int emb_dtype, const int32_t* n_new, int Lx, void* hidden_out,
+                              int hidden_dtype, hipStream_t s) {
+    const bool as = as_pending; as_pending = false;      // one-shot: consumed before anything can fail; this call cannot serve it
+    if (as) FAIL(PG_ERR_ARG, "pg_request_attn_spans: pg_prefill_extend cannot serve it (only pg_prefill / pg_prefill_embeds pack whole rows)");
+    TRY(check_extendable("pg_prefill_extend"));
+    if ((ids_dev == nullptr) == (emb_dev == nullptr)) FAIL(PG_ERR_ARG, "pg_prefill_extend: exactly one of ids_dev / embeds_dev must be given");
+    if (emb_dev && emb_dtype != PG_F32 && emb_dtype != PG_BF16) FAIL(PG_ERR_ARG, "pg_prefill_extend: embeds_dtype %d is neither PG_F32 nor PG_BF16", emb_dtype);
+    if (hidden_out && hidden_dtype != PG_F32 && hidden_dtype != PG_BF16) FAIL(PG_ERR_ARG, "pg_prefill_extend: hidden_dtype %d is neither PG_F32 nor PG_BF16", hidden_dtype);
+    if (!n_new || Lx < 1) FAIL(PG_ERR_ARG, "pg_prefill_extend: n_new_host is NULL or Lx=%d < 1", Lx);
+    for (int r = 0; r < R; ++r)
+        if (n_new[r] < 1 || n_new[r] > Lx) FAIL(PG_ERR_ARG, "pg_prefill_extend: row %d: n_new %d not in [1, Lx=%d]", r, n_new[r], Lx);
+    long total = 0;
+    for (int r = 0; r < R; ++r) {
+        const long end = (long)h_len[r] + n_dec_host + n_new[r];
+        if (end > slots) FAIL(PG_ERR_CAPACITY, "pg_prefill_extend: row %d: %d cached + %d new tokens exceed the %d KV slots", r, h_len[r] + n_dec_host, n_new[r], slots);
+        if (h_pos_off[r] + end > max_pos) FAIL(PG_ERR_CAPACITY, "pg_prefill_extend: row %d: position %ld exceeds the RoPE table (%d)", r, h_pos_off[r] + end - 1, max_pos);
+        total += n_new[r];
+    }
+    if (total > max_tok) FAIL(PG_ERR_CAPACITY, "pg_prefill_extend: %ld new tokens exceed the packed-token capacity %ld", total, max_tok);
+    HIPCHK(hipSetDevice(dev));
+    stage_sel ^= 1;                                       // pinned staging as in prefill: double-buffered, guarded by an event
+    int32_t* const hs = h_stage2[stage_sel];
+    if (stage_used[stage_sel]) HIPCHK(hipEventSynchronize(ev_stage[stage_sel]));
+    int32_t* s_len = hs; int32_t* s_last = hs + 2 * cfg.max_rows; int32_t* s_roff = hs + 3 * cfg.max_rows; int32_t* s_ord = hs + 4 * cfg.max_rows;
+    int32_t* s_row = hs + 5 * cfg.max_rows; int32_t* s_j = s_row + max_tok; int32_t* s_src = s_j + max_tok;
+    int32_t* s_nnew = hs + 5 * cfg.max_rows + 3 * max_tok + 16;      // the span request's place: no request runs here
+    int ntok = 0, mx = 0;
+    for (int r = 0; r < R; ++r) {
+        const int cur = h_len[r] + n_dec_host, n = n_new[r];
+        s_len[r] = cur + n; s_roff[r] = ntok; s_nnew[r] = n; if (n > mx) mx = n;
+        for (int i = 0; i < n; ++i) { s_row[ntok] = r; s_j[ntok] = cur + i; s_src[ntok] = r * Lx + i; ++ntok; }
+        s_last[r] = ntok - 1;
+    }
+    TRY(set_lengths(s_len, s_ord, s));
+    HIPCHK(hipMemcpyAsync(d_last, s_last, (size_t)R * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_row_off, s_roff, (size_t)R * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_nnew, s_nnew, (size_t)R * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_tok_row, s_row, (size_t)ntok * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_tok_j, s_j, (size_t)ntok * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_tok_src, s_src, (size_t)ntok * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(ev_stage[stage_sel], s));
+    stage_used[stage_sel] = true;
+    if (ids_dev) launch_embed_gather(s, embed, ids_dev, d_tok_src, x, ntok, H(), cfg.vocab);
+    else launch_rows_to_f32(s, emb_dev, emb_dtype == PG_BF16, d_tok_src, x, ntok, H());
+    // only the new tokens go through the GEMMs: packed, tok_j = cur + i, the prefill path of run_layers (RoPE epilogue included); the attention
+    // reads the cached slots in front of them
+    DecodeView v = view(0, R, 0);
+    ext_nnew = d_nnew; ext_max_new = mx;
+    if (bf) run_layers<bf16>(s, v, ntok, 1, (bf16*)xn); else run_layers<float>(s, v, ntok, 1, (float*)xn);
+    ext_nnew = nullptr; ext_max_new = 0;
+    launch_copy_rows(s, xn, d_last, hfin, nullptr, R, (long)H() * esz);      // each row's last new token -> hfin
+    hfin_stale = false;
+    if (hidden_out) {
+        HIPCHK(hipMemsetAsync(hidden_out, 0, (size_t)R * Lx * H() * (hidden_dtype == PG_BF16 ? 2 : 4), s));
+        if (bf) launch_t_to_rows<bf16>(s, (const bf16*)xn, hidden_out, hidden_dtype == PG_BF16, d_tok_src, ntok, H());
+        else launch_t_to_rows<float>(s, (const float*)xn, hidden_out, hidden_dtype == PG_BF16, d_tok_src, ntok, H());
+    }
+    HIPCHK(hipGetLastError());
+    return PG_OK;
+}
+
+// Row r keeps its first len_host[r] slots.  The slots behind them keep their stale keys and are never read (every attention kernel bounds its reads
+// by the lengths on the device); hfin is NOT recomputed -- it belongs to whatever ran last -- so a pg_prefill_extend follows before anything samples (hfin_stale: the
+// decode loops answer PG_ERR_STATE until then; pg_step, which takes its input from the caller, is allowed).
+int pg_engine::rewind(const int32_t* len_host, hipStream_t s) {
+    TRY(check_extendable("pg_rewind"));
+    if (!len_host) FAIL(PG_ERR_ARG, "pg_rewind: len_host is NULL");
+    for (int r = 0; r < R; ++r)
+        if (len_host[r] < 1 || len_host[r] > h_len[r] + n_dec_host) FAIL(PG_ERR_ARG, "pg_rewind: row %d: length %d not in [1, %d]", r, len_host[r], h_len[r] + n_dec_host);
+    HIPCHK(hipSetDevice(dev));
+    stage_sel ^= 1;
+    int32_t* const hs = h_stage2[stage_sel];
+    if (stage_used[stage_sel]) HIPCHK(hipEventSynchronize(ev_stage[stage_sel]));
+    std::copy(len_host, len_host + R, hs);
+    TRY(set_lengths(hs, hs + 4 * cfg.max_rows, s));
+    hfin_stale = true;
+    HIPCHK(hipEventRecord(ev_stage[stage_sel], s));
+    stage_used[stage_sel] = true;
     return PG_OK;
 }
 
@@ -465,6 +575,9 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     if (R % 2) FAIL(PG_ERR_ARG, "CFG decode needs an even number of rows (got %d)", R);
     if (n_dec_host != 0) FAIL(PG_ERR_STATE, "decode loop needs a fresh prefill");
     if (T < 1 || T - 1 > cfg.max_new) FAIL(PG_ERR_CAPACITY, "T=%d exceeds max_new=%d", T, cfg.max_new);
+    if (max_len_host + T - 1 > slots) FAIL(PG_ERR_CAPACITY, "T=%d behind %d cached tokens (pg_prefill_extend) exceeds the %d KV slots", T, max_len_host, slots);
+    if (max_pos_end() + T - 1 > max_pos) FAIL(PG_ERR_CAPACITY, "T=%d from position %d (pg_prefill_extend) exceeds the RoPE table (%d)", T, max_pos_end(), max_pos);
+    if (hfin_stale) FAIL(PG_ERR_STATE, "pg_decode_image_tokens after pg_rewind: a pg_prefill_extend must follow before anything samples");
     if (score && q.lp_cap < (int64_t)(R / 2) * T) FAIL(PG_ERR_ARG, "token log-probs: capacity %lld floats is below B * T = %lld", (long long)q.lp_cap, (long long)(R / 2) * T);
     if (score && lanes_opt == 2) FAIL(PG_ERR_ARG, "token log-probs do not support lanes = 2");
     if (stats && q.ts.capacity < (int64_t)(R / 2) * T) FAIL(PG_ERR_ARG, "token stats: capacity %lld positions is below B * T = %lld", (long long)q.ts.capacity, (long long)(R / 2) * T);
@@ -592,6 +705,8 @@ int pg_engine::step(const void* emb, int emb_dtype, void* hidden_out, int hidden
     if (kv8 && !fuse_rope) FAIL(PG_ERR_ARG, "the FP8 KV cache needs the fused decode attention (fuse_rope)");
     if (group_rows > 0 && !fuse_rope) FAIL(PG_ERR_ARG, "replicas that alias their owner's prompt need the fused decode attention (fuse_rope)");
     if (n_dec_host + 1 > cfg.max_new) FAIL(PG_ERR_CAPACITY, "decode capacity max_new=%d exhausted", cfg.max_new);
+    if (max_len_host + n_dec_host + 1 > slots) FAIL(PG_ERR_CAPACITY, "the %d KV slots are exhausted (%d cached tokens, pg_prefill_extend)", slots, max_len_host + n_dec_host);
+    if (max_pos_end() + n_dec_host + 1 > max_pos) FAIL(PG_ERR_CAPACITY, "position %d (pg_prefill_extend) exceeds the RoPE table (%d)", max_pos_end() + n_dec_host, max_pos);
     HIPCHK(hipSetDevice(dev));
     DecodeView v = view(0, R, 0);
     launch_rows_to_f32(s, emb, emb_dtype == PG_BF16, nullptr, v.x, R, H());
@@ -883,6 +998,9 @@ int pg_engine::text_generate(int max_new, int min_new, int eos, float temp, int 
     if (!cfg.with_lm_head) FAIL(PG_ERR_STATE, "engine created without lm_head");
     if (n_dec_host != 0) FAIL(PG_ERR_STATE, "text decode needs a fresh prefill");
     if (max_new < 1 || max_new > cfg.max_new || max_new > 1000) FAIL(PG_ERR_CAPACITY, "max_new=%d exceeds capacity %d", max_new, cfg.max_new);
+    if (max_len_host + max_new - 1 > slots) FAIL(PG_ERR_CAPACITY, "max_new=%d behind %d cached tokens (pg_prefill_extend) exceeds the %d KV slots", max_new, max_len_host, slots);
+    if (max_pos_end() + max_new - 1 > max_pos) FAIL(PG_ERR_CAPACITY, "max_new=%d from position %d (pg_prefill_extend) exceeds the RoPE table (%d)", max_new, max_pos_end(), max_pos);
+    if (hfin_stale) FAIL(PG_ERR_STATE, "text decode after pg_rewind: a pg_prefill_extend must follow before anything samples");
     if (constrained) {
         if (!dfa_set) FAIL(PG_ERR_STATE, "constrained text decode without an automaton (pg_set_text_dfa)");
         if (dfa_dist_start > max_new) FAIL(PG_ERR_ARG, "max_new=%d is below dist[start_state]=%d: no row could finish", max_new, dfa_dist_start);

@@ -162,6 +162,10 @@ void launch_attn(hipStream_t s, const T* qbuf, T* obuf, const T* kc, const T* vc
 // prefill: causal varlen flash attention on MFMA (bf16, head_dim 128); row_off[r] = first packed token of row r or -1
 void launch_attn_prefill_flash(hipStream_t s, const bf16* qbuf, bf16* obuf, const bf16* kc, const bf16* vc,
                                const int32_t* row_off, const int32_t* len, int R, int max_len, int nh, int slots, float scale);
+// pg_prefill_extend: the 128-query flash kernel with a per-row query offset (attn_extend.hip).  The packed queries of row r are its n_new[r] new
+// tokens (slots len[r] - n_new[r] .. len[r] - 1, len = the length after the extension); new token i sees keys 0 .. len[r] - n_new[r] + i
+void launch_attn_extend_flash(hipStream_t s, const bf16* qbuf, bf16* obuf, const bf16* kc, const bf16* vc, const int32_t* row_off,
+                              const int32_t* len, const int32_t* n_new, int R, int max_new, int nh, int slots, float scale);
 // prefill: attention mass of the query columns [q_col0, q_col0 + n_q) on at most 16 spans per row (attn_span.hip; definition: include/plangen_hip.h,
 // pg_request_attn_spans).  q / K / row_off / len as the flash attention gets them; pad_len / span_lo / span_hi are device arrays ([R], [R][n_spans],
 // columns of the padded frame: slot = column - pad_len[r]); out fp32 [R][n_q][n_spans] (zeroed, then written).  len[r] <= slots is the caller's.

@@ -496,6 +496,44 @@ class Engine:
         self._keep = [embeds, mass]
         return out if attn_spans is None else (out, mass)
 
+    def extend(self, ids: Optional[torch.Tensor] = None, embeds: Optional[torch.Tensor] = None, n_new: Optional[Sequence[int]] = None,
+               return_hidden: bool = False, hidden_dtype=torch.float32):
+        """``pg_prefill_extend``: continue the cached rows with many tokens in one pass.  Exactly one of ``ids`` int [R, Lx] / ``embeds``
+        [R, Lx, hidden]; the first ``n_new[r]`` columns of row r are its new tokens (default: all Lx).  New token i of row r takes slot
+        ``cached_len()[r] + i``, the RoPE position the preceding prefill's rule gives that slot, and attends to everything the row holds.
+        Afterwards every decode entry point continues as after a prefill of the longer rows.  return_hidden: the final-norm hidden states
+        [R, Lx, hidden] of the new tokens (unused columns zero)."""
+        if (ids is None) == (embeds is None):
+            raise PlanGenError("extend: exactly one of ids / embeds must be given")
+        src = self._dev(ids, torch.int32) if ids is not None else self._dev(embeds)
+        if src.dim() != (2 if ids is not None else 3) or src.shape[0] != self.R:
+            raise PlanGenError(f"extend: expected {self.R} rows of [R, Lx{'' if ids is not None else ', hidden'}] (got {tuple(src.shape)})")
+        Lx = src.shape[1]
+        nn = [Lx] * self.R if n_new is None else [int(v) for v in n_new]
+        if len(nn) != self.R:
+            raise PlanGenError(f"extend: n_new has {len(nn)} entries for {self.R} rows")
+        out = torch.empty((self.R, Lx, self.cfg.hidden), dtype=hidden_dtype, device=self.device) if return_hidden else None
+        self._check(self.lib.pg_prefill_extend(self.h, self._p(src) if ids is not None else None, self._p(src) if ids is None else None,
+                                               _dt(src) if ids is None else PG_F32, (C.c_int32 * self.R)(*nn), Lx, self._p(out),
+                                               _dt(out) if out is not None else PG_F32, self.stream), "pg_prefill_extend")
+        self._keep = [src]
+        return out
+
+    def rewind(self, lens: Sequence[int]) -> None:
+        """``pg_rewind``: row r keeps its first ``lens[r]`` cached slots (1 <= lens[r] <= cached_len()[r]).  An :meth:`extend` follows before
+        anything samples: the hidden state the samplers read is not recomputed."""
+        ln = [int(v) for v in lens]
+        if len(ln) != self.R:
+            raise PlanGenError(f"rewind: lens has {len(ln)} entries for {self.R} rows")
+        self._check(self.lib.pg_rewind(self.h, (C.c_int32 * self.R)(*ln), self.stream), "pg_rewind")
+
+    def cached_len(self) -> list:
+        """K/V slots every row holds: its prompt plus the decode steps run since (the token a loop emitted last was never fed back and has no
+        slot).  Reads two small device arrays: synchronises."""
+        ln = self.debug_read("len", 0, self.R, torch.int32)
+        nd = self.debug_read("n_dec", 0, 1, torch.int32)
+        return (ln + nd).tolist()
+
     def step(self, embeds: torch.Tensor, hidden_dtype=torch.float32) -> torch.Tensor:
         embeds = self._dev(embeds).view(self.R, self.cfg.hidden)
         out = torch.empty((self.R, self.cfg.hidden), dtype=hidden_dtype, device=self.device)

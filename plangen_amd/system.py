@@ -102,6 +102,7 @@ class System:
         self.last_generated_tokens = None
         self.last_token_stats = None      # args.token_stats: the stats dict [B, T] of the last t2i (+ "summary": image_token_stats_summary)
         self.last_sample_plan = None      # the sample-plan cfg keys: the record of the last t2i's plan (build_sample_plan), None when no key is set
+        self.last_forced_prefix = None    # prefill_forced_prefix: t0 of the last t2i (0: nothing could be prefilled), None when the key is off
         self.last_selection = None        # select_best: dict(replica int64 [B0], score fp32 [B0], scores fp32 [p, B0]) of the last t2i
         self.vl_gpt = MultiModalityCausalLM(engine)
         self.args = args or SimpleNamespace(seed=cfg.seed, parallel_size=1, cfg_weight=cfg.cfg_weight,
@@ -154,6 +155,31 @@ class System:
         if plan is not None:
             lpkw["plan"] = plan
         return self.engine.decode_image_tokens(n_tokens, cfg_weight, temperature, seed, ft, fm, return_logits, top_k=top_k, top_p=top_p, **lpkw)
+
+    @staticmethod
+    def forced_prefix_len(edit_region: torch.Tensor) -> int:
+        """t0 of ``prefill_forced_prefix``: the smallest raster index, over the batch, with ``edit_region != 0`` (T when no cell of any row
+        is edited).  Every image token in front of it is forced to the ground-truth code in every row."""
+        free = (edit_region.reshape(edit_region.shape[0], -1) != 0).any(0)
+        hit = torch.nonzero(free)
+        return int(hit[0]) if hit.numel() else int(free.numel())
+
+    @torch.no_grad()
+    def sample_image_forced_prefix(self, tokens: torch.Tensor, mask: torch.Tensor, cfg_weight: float, temperature: float, seed: int,
+                                   edit_region: torch.Tensor, gt_labels: torch.Tensor, t0: int, top_k: int = 0, top_p: float = 1.0):
+        """``sample_image`` under teacher forcing with the first ``t0`` image tokens (forced in every row) fed in ONE pass: prefill without the
+        shared negative prompt (an extension cannot follow the aliased rows), ``Engine.extend`` both rows of every pair with
+        prepare_gen_img_embeds(gt[:, :t0]), then T - t0 decode steps with the force arrays sliced.  Sampled draws count their RNG steps from
+        the first DECODED step: another, equally valid noise stream than the unaccelerated loop's; greedy is unaffected."""
+        L = tokens.shape[1]
+        T = gt_labels.shape[1]
+        eng = self.engine
+        eng.prefill(tokens, Engine.pad_len_from_mask(mask, L), position_mode=0, uncond_shared=False)
+        gt = gt_labels.to(eng.device, torch.int32)
+        eng.extend(embeds=eng.gen_embed(gt[:, :t0].repeat_interleave(2, 0)).view(tokens.shape[0], t0, self.cfg.hidden))
+        fm = (edit_region.reshape(gt.shape[0], -1)[:, t0:] != 0).to(torch.uint8).contiguous()
+        dec = eng.decode_image_tokens(T - t0, cfg_weight, temperature, seed, gt[:, t0:].contiguous(), fm, False, top_k=top_k, top_p=top_p)
+        return torch.cat([gt[:, :t0], dec.to(torch.int32)], dim=1)
 
     @staticmethod
     def image_token_stats_summary(stats: dict, forced: Optional[torch.Tensor] = None) -> dict:
@@ -335,10 +361,25 @@ class System:
         if self.plan_keys_set():
             cond_rows = [tokens[2 * i][mask[2 * i, :L0].bool()].tolist() for i in range(B0)]
             plan, self.last_sample_plan = self.build_sample_plan(cond_rows, p, cfg_weight, self.image_token_num_per_image)
-        toks = self.sample_image(tokens, mask, cfg_weight, temperature, a.seed,
-                                 force_region if gt_labels is not None else None, gt_labels, top_k=top_k, top_p=top_p,
-                                 replicas=p if share else 1, **({"return_logprobs": True} if select else {}), **({"plan": plan} if plan is not None else {}),
-                                 **({"return_stats": want_stats} if stats_on else {}))
+        # prefill_forced_prefix (cfg key, default False; use_teacher_forcing only): the image tokens in front of the first edited cell are known
+        # before the loop starts -- one extension instead of t0 decode steps
+        t0 = 0
+        self.last_forced_prefix = None
+        if bool(getattr(a, "prefill_forced_prefix", False)) and gt_labels is not None:
+            clash = [k for k, on in (("select_best", select), ("token_stats", stats_on), ("return_logprobs", bool(getattr(a, "return_logprobs", False))),
+                                     ("a sample plan (" + ", ".join(self.plan_keys_set()) + ")", plan is not None), ("share_replicas", share)) if on]
+            if clash:
+                raise PlanGenError(f"prefill_forced_prefix cannot be combined with {' / '.join(clash)}: the prefilled tokens never pass through the "
+                                   "sampler, so they have no log-probabilities, statistics or plan steps (and replicated prompts cannot be extended)")
+            t0 = min(self.forced_prefix_len(force_region), self.image_token_num_per_image - 1)      # at least one step stays in the loop
+            self.last_forced_prefix = t0
+        if t0 >= 1:
+            toks = self.sample_image_forced_prefix(tokens, mask, cfg_weight, temperature, a.seed, force_region, gt_labels, t0, top_k=top_k, top_p=top_p)
+        else:
+            toks = self.sample_image(tokens, mask, cfg_weight, temperature, a.seed,
+                                     force_region if gt_labels is not None else None, gt_labels, top_k=top_k, top_p=top_p,
+                                     replicas=p if share else 1, **({"return_logprobs": True} if select else {}), **({"plan": plan} if plan is not None else {}),
+                                     **({"return_stats": want_stats} if stats_on else {}))
         if stats_on:
             toks, stats = toks[:-1], toks[-1]
             toks = toks if select else toks[0]
@@ -493,6 +534,8 @@ class System:
                 out["image_entropy"] = self.last_token_stats["entropy"].view(-1, self.cfg.grid, self.cfg.grid)
             if self.last_sample_plan is not None:
                 out["sample_plan"] = self.last_sample_plan
+            if self.last_forced_prefix is not None:
+                out["forced_prefix"] = self.last_forced_prefix
             if self.last_selection is not None:
                 out["pr_replica"], out["pr_score"] = self.last_selection["replica"], self.last_selection["score"]
             out["pr_image"] = dec.float()
@@ -526,7 +569,7 @@ class System:
                     extra["gt_layout_logprob"] = out["gt_layout_logprob"]
                 if "gt_image_logprob" in out:
                     extra["gt_image_logprob"] = out["gt_image_logprob"]
-                for k in ("image_token_stats", "text_token_stats", "sample_plan"):
+                for k in ("image_token_stats", "text_token_stats", "sample_plan", "forced_prefix"):
                     if k in out:
                         extra[k] = out[k]
                 if "image_entropy" in out:
@@ -748,6 +791,69 @@ class System:
         score = total / first.clamp(min=1)
         rows, replica, scores = System.select_best_replicas(score.view(N, 1), n)
         return rows, replica, scores.gather(0, replica.view(1, B))[0]
+
+    @torch.no_grad()
+    def mmu_ask(self, batch: dict, questions: Sequence[dict], max_new_tokens: int = 512, min_new_tokens: int = 0) -> List[list]:
+        """Several questions about the images of one mmu batch, with each row's prompt up to and including its image block prefilled ONCE.
+        ``questions``: one ``prepare_inputs_infer``-style dict per question (input_ids [B, Lq] left-padded, images_seq_mask, attention_mask: what
+        the mmu collate builds for that question; pixel_values / images_emb_mask are taken from ``batch['prepare_inputs_infer']``, the first
+        question's).  Per row the columns in front of ``textproc.image_block_split`` must carry the same ids in every question.  Then per
+        question: ``Engine.rewind`` to the prefix, ``Engine.extend`` with the question's tail tokens, and the text loop ``x2t`` is configured
+        with (greedy, or text_temperature / text_top_k / text_top_p).  Returns one answer list per question: decoded texts with a codec, else
+        the rows' new ids cut at EOS; the raw id tensors stay in ``self.last_ask_ids``."""
+        from .textproc import cut_at_eos, image_block_split
+        eng, dev = self.engine, self.device
+        pin0 = dict(batch["prepare_inputs_infer"])
+        qs = [dict(pin0, **{k: v for k, v in q.items() if k in ("input_ids", "images_seq_mask", "attention_mask")}) for q in questions]
+        if not qs:
+            return []
+        end_id = None
+        if self.codec is not None:
+            from .textproc import IMAGE_END_TAG
+            end_id = self.codec.token_id(IMAGE_END_TAG)
+        B = qs[0]["input_ids"].shape[0]
+        geo = []                                            # per question, per row: (pad, split, L)
+        for q in qs:
+            ids, L = q["input_ids"], q["input_ids"].shape[1]
+            pad = Engine.pad_len_from_mask(q["attention_mask"], L)
+            geo.append([(pad[r], image_block_split(q["images_seq_mask"][r].tolist(), ids[r].tolist(), end_id), L) for r in range(B)])
+        for qi, q in enumerate(qs[1:], 1):
+            for r in range(B):
+                (p0, s0, _), (p1, s1, _) = geo[0][r], geo[qi][r]
+                if s0 - p0 != s1 - p1 or not torch.equal(qs[0]["input_ids"][r, p0:s0].cpu(), q["input_ids"][r, p1:s1].cpu()):
+                    raise PlanGenError(f"mmu_ask: row {r} of question {qi} differs from question 0 in front of the end of its image block")
+        # the shared prefix, from question 0's embeddings (SigLIP + aligner run once), left-padded to the longest prefix
+        emb0 = self.vl_gpt.prepare_inputs_embeds(**{k: v for k, v in qs[0].items() if k != "attention_mask"})
+        plen = [s - p for p, s, _ in geo[0]]
+        Lp = max(plen)
+        pre = torch.zeros((B, Lp, self.cfg.hidden), dtype=emb0.dtype, device=emb0.device)
+        for r, (p, s, _) in enumerate(geo[0]):
+            pre[r, Lp - plen[r]:] = emb0[r, p:s]
+        eng.prefill_embeds(pre, [Lp - n for n in plen], position_mode=1)
+        self.vl_gpt.language_model.model.epoch += 1       # invalidates any sample_image cache token, like generate
+        a = self.args
+        temperature = float(getattr(a, "text_temperature", 0.0))
+        answers, self.last_ask_ids = [], []
+        embed = self.vl_gpt.language_model.get_input_embeddings()
+        for qi, q in enumerate(qs):
+            n_new = [L - s for _, s, L in geo[qi]]
+            if min(n_new) < 1:
+                raise PlanGenError(f"mmu_ask: question {qi} has a row with nothing behind its image block")
+            tail = torch.full((B, max(n_new)), 0, dtype=torch.long)
+            for r, (_, s, L) in enumerate(geo[qi]):
+                tail[r, :n_new[r]] = q["input_ids"][r, s:L].cpu().clamp_min(0)
+            if qi > 0:
+                eng.rewind(plen)
+            eng.extend(embeds=embed(tail.to(dev)), n_new=n_new)
+            if temperature > 0:
+                out = eng.generate_text(max_new_tokens, self.cfg.eos_id, min_new_tokens, temperature=temperature, top_k=int(getattr(a, "text_top_k", 0)),
+                                        top_p=float(getattr(a, "text_top_p", 1.0)), seed=int(getattr(a, "seed", 0)))
+            else:
+                out = eng.generate_text_greedy(max_new_tokens, self.cfg.eos_id, min_new_tokens)
+            self.last_ask_ids.append(out)
+            rows = out.cpu().tolist()
+            answers.append(self.decode_mmu_text_batch(rows) if self.codec is not None else [cut_at_eos(r, self.cfg.eos_id) for r in rows])
+        return answers
 
     @torch.no_grad()
     def x2t(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,

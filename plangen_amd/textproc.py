@@ -93,6 +93,23 @@ def wrap_mmu_prompt_ids(codec, question: str, num_image_tokens: int, answer: str
     return prompt, ids, [t == img for t in ids]
 
 
+def image_block_split(images_seq_mask_row: Sequence[bool], ids_row: Optional[Sequence[int]] = None, image_end_id: Optional[int] = None) -> int:
+    """The column at which an mmu prompt row splits into [everything up to and including the image block | the question's tail]: one past the
+    LAST image slot of ``images_seq_mask_row``, and past the ``<end_of_image>`` tag behind it when ``ids_row`` / ``image_end_id`` are given
+    and the tag is there.  What lies in front of it does not depend on the question (system prompt, role tag, the image), so several
+    questions about one image share its K/V (System.mmu_ask).  Raises ValueError for a row without image slots."""
+    last = -1
+    for j, m in enumerate(images_seq_mask_row):
+        if bool(m):
+            last = j
+    if last < 0:
+        raise ValueError("image_block_split: the row has no image slot")
+    split = last + 1
+    if ids_row is not None and image_end_id is not None and split < len(ids_row) and int(ids_row[split]) == int(image_end_id):
+        split += 1
+    return split
+
+
 def wrap_uni_prompt_ids(codec, caption: str, grounding: Optional[str], in_stage1: bool = False) -> Tuple[str, List[int]]:
     prompt = wrap_uni_prompt_text(caption, grounding, in_stage1)
     ids = list(codec.encode(prompt))

@@ -19,6 +19,7 @@ text_top_k = 0                         # top-k filtering of sampled text tokens 
 text_top_p = 1.0                       # top-p (nucleus) filtering of sampled text tokens (1.0: off)
 layout_grammar = False                 # True: the stage-1 layout decode (uni_2stage, plan) can only emit a well-formed layout string that ends inside max_new_tokens (an extension beyond the reference)
 kv_dtype = 'bf16'                      # KV cache: 'bf16' = the compute dtype; 'fp8' = e4m3 codes + power-of-two scales (about half the cache bytes; an extension beyond the reference)
+prefill_forced_prefix = False         # use_teacher_forcing: feed the image tokens in front of the first edited cell in one pass (Engine.extend) instead of one decode step each; same greedy tokens, sampled draws count RNG steps from the first decoded step
 share_replicas = 0                     # parallel_size > 1: 1 = prefill every prompt once and let its replicas read its K/V in the decode loop (same tokens; an extension beyond the reference)
 select_best = False                    # parallel_size > 1: score every replica by the mean log-probability of its image tokens, VQ-decode and keep only the best one per prompt (an extension beyond the reference)
 layout_best_of = 1                     # uni_2stage / plan with text_temperature > 0: draw this many layouts per row and keep the one with the highest mean token log-probability (an extension beyond the reference)

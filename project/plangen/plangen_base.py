@@ -97,6 +97,7 @@ class System(_HotPath):
                                                    score_gt_image=bool(getattr(args, "score_gt_image", False)),
                                                    token_stats=getattr(args, "token_stats", False),
                                                    layout_attribution=bool(getattr(args, "layout_attribution", False)),
+                                                   prefill_forced_prefix=bool(getattr(args, "prefill_forced_prefix", False)),
                                                    use_centerhw=bool(getattr(args, "use_centerhw", False)),
                                                    **{k: getattr(args, k, None) for k in _HotPath.PLAN_KEYS},
                                                    use_teacher_forcing=args.use_teacher_forcing, share_replicas=cfg.share_replicas,

@@ -225,6 +225,8 @@ def gemm256_ph2_need_factory():
 SPECS = [
     ("attn_prefill", r"attn_prefill_flash2_kernel", dict(kind="fifo", g=4, need=flash2_need, tile_cls=lambda n: n & 1, slot_reuse=lambda c: 4, strict=True,
                                                          why="two barriers per tile: A(t) retires V(t), B(t) retires K(t+1)")),
+    ("attn_extend", r"attn_extend_flash_kernel", dict(kind="fifo", g=4, need=flash2_need, tile_cls=lambda n: n & 1, slot_reuse=lambda c: 4, strict=True,
+                                                      why="flash2's stream and barriers with a per-row query offset (pg_prefill_extend): A(t) retires V(t), B(t) retires K(t+1)")),
     # PH = 2 is the second-to-last template argument (GN, a bool, follows it): ...ELi<PH>ELb<GN>EEv.  The two-phase invariants: plangen_amd/csrc/tile256.h
     ("gemm256", r"gemm256_kernel.*ELi2ELb[01]EEv", dict(kind="fifo", g=2, need="ph2", tile_cls=lambda n: n & 3, slot_reuse=lambda c: 8, strict=True, stagger=True,
                                                  why="two-phase form: half-tiles retired by vmcnt(8) / vmcnt(6) one phase before they are read; a slot is re-staged one barrier "
