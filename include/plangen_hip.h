@@ -245,6 +245,26 @@ int pg_decode_image_tokens(pg_handle h, int T, float cfg_weight, float temperatu
 int pg_decode_image_tokens_filtered(pg_handle h, int T, float cfg_weight, float temperature, int32_t top_k, float top_p,
                                     uint64_t seed, const int32_t* force_tok_dev, const uint8_t* force_mask_dev,
                                     int32_t* out_tok_dev, float* logits_out_dev, pg_stream s);
+/* Dual guidance (an extension beyond the reference; the decomposed form of InstructPix2Pix): the image loop of
+ * pg_decode_image_tokens_filtered over THREE rows per image, after a pg_prefill of R = 3B rows interleaved as
+ *   row 3b     = f: the full prompt (caption + layout)
+ *   row 3b + 1 = p: the caption alone
+ *   row 3b + 2 = u: the negative prompt
+ * with, per image, step and vocabulary entry, in fp32,
+ *   mixed = (u + w_caption * (p - u)) + w_layout * (f - p).
+ * Everything behind the mixed row -- greedy / Gumbel-max draw keyed on (seed, global image, step), top-k / top-p, forcing,
+ * the logits tap [T, B, img_vocab], the token fed back to all three rows -- is pg_decode_image_tokens_filtered's, with
+ * B = R / 3.  Two degenerate cases hold bit for bit against the pair loop on the same logits: p == f gives
+ * u + w_caption * (f - u), p == u gives u + w_layout * (f - u); w_caption == w_layout == w is ordinary CFG up to rounding.
+ * One-shot pg_request_token_logprobs / pg_request_token_stats are honoured (capacity B * T, B = R / 3).  An FP8 KV
+ * cache is allowed.  Refused, nothing launched: R % 3 != 0 (PG_ERR_ARG); a prefill that shared the negative prompt
+ * across odd rows (PG_ERR_STATE: prefill with the one-shot pg_set_option("uncond_shared_hint", 0)); replicas that alias
+ * their owner's prompt (PG_ERR_STATE); lanes = 2 (PG_ERR_ARG); a pending pg_request_sample_plan (PG_ERR_ARG; the plan
+ * is consumed); non-finite weights, top_k / top_p out of range (PG_ERR_ARG); filtering with img_vocab > 16384
+ * (PG_ERR_CAPACITY); and every state pg_decode_image_tokens refuses. */
+int pg_decode_image_tokens_dual(pg_handle h, int T, float w_caption, float w_layout, float temperature, int32_t top_k,
+                                float top_p, uint64_t seed, const int32_t* force_tok_dev, const uint8_t* force_mask_dev,
+                                int32_t* out_tok_dev, float* logits_out_dev, pg_stream s);
 
 /* language_model.generate(inputs_embeds=..., do_sample=False, max_new_tokens=...,
  * eos_token_id=pad_token_id=eos) (System.x2t, plangen_base.py:513-523) after a

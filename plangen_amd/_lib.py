@@ -80,6 +80,7 @@ SYMBOLS = [
     ("pg_embed_tokens", C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
     ("pg_decode_image_tokens", C.c_int, [_P, C.c_int, C.c_float, C.c_float, C.c_uint64, _P, _P, _P, _P, _P]),
     ("pg_decode_image_tokens_filtered", C.c_int, [_P, C.c_int, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_uint64, _P, _P, _P, _P, _P]),
+    ("pg_decode_image_tokens_dual", C.c_int, [_P, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_uint64, _P, _P, _P, _P, _P]),
     ("pg_generate_text_greedy", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int), _P]),
     ("pg_generate_text_sampled", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int32, C.c_float, C.c_uint64, _P, C.POINTER(C.c_int), _P, _P]),
     ("pg_set_text_dfa", C.c_int, [_P, C.POINTER(pg_text_dfa), _P]),

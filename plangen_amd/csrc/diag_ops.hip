@@ -897,6 +897,41 @@ int pg_diag_op_cfg_sample_plan(int filtered, int stored, const float* partial, i
     return finish(s);                                                                                // before the scratch goes away
 }
 
+// One dual-guidance step (tests/test_gpu_dual_ops.py) through launch_cfg3_sample: rows [3B][V] per slab (3b = f, 3b + 1 = p, 3b + 2 = u), slab >= 3 B V, x fp32
+// [3B][H].  filtered != 0: store scan -> select -> pick (V <= SEL_MAXV, temperature > 0); stored != 0: the unfiltered route also runs the store scan.  mix_out
+// fp32 [B][V] or null: the mixed rows the store scan left (filtered or stored).  Everything else as pg_diag_op_cfg_sample.
+int pg_diag_op_cfg3_sample(int filtered, int stored, const float* partial, int S, long slab, const float* bias, int V, int B, const int32_t* force_tok,
+                           const uint8_t* force_mask, int32_t* out_tok, float* logits_out, float* mix_out, const float* embed_table, float* x, int H, float w_caption,
+                           float w_layout, float temperature, uint64_t seed, int top_k, float top_p, int T, int step, int img_off, int b_off, int B_total,
+                           pg_stream stream) {
+    if (!partial || !out_tok || !embed_table || !x || (force_mask && !force_tok)) return PG_ERR_ARG;
+    if (S < 1 || V < 1 || B < 1 || B > kMaxGridYZ / 3 || H < 4 || (H & 3) || T < 1 || step < 0 || img_off < 0 || b_off < 0 || B_total < 1) return PG_ERR_ARG;
+    if ((long)b_off + B > B_total || slab < 3L * B * V || (long)V * H >= (1L << 40) || !aligned16({embed_table, x})) return PG_ERR_ARG;
+    if (logits_out && step >= T) return PG_ERR_ARG;                                                  // the tap has T steps
+    if (!(w_caption == w_caption) || !(w_layout == w_layout) || !(temperature == temperature)) return PG_ERR_ARG;
+    if (filtered && (V > SEL_MAXV || !(temperature > 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f))) return PG_ERR_ARG;
+    if (mix_out && !filtered && !stored) return PG_ERR_ARG;
+    LocalTune lt;
+    const hipStream_t s = (hipStream_t)stream;
+    Scratch sp, dw, nd, pv, pi, mix;
+    if (!sp.get(sizeof(SampleParams)) || !dw.get(sizeof(DualWeights)) || !nd.get(4) || !pv.get((size_t)B * 16 * 4) || !pi.get((size_t)B * 16 * 4)) return PG_ERR_HIP;
+    if ((filtered || stored) && !mix.get((size_t)B * V * 4)) return PG_ERR_HIP;
+    const int32_t hstep = step;
+    if (hipMemcpy(nd.p, &hstep, 4, hipMemcpyHostToDevice) != hipSuccess) return PG_ERR_HIP;
+    SampleParams p{};
+    p.cfg_weight = w_caption; p.temperature = temperature; p.seed = seed; p.T = T; p.has_force = force_tok != nullptr; p.has_mask = force_mask != nullptr;
+    p.img_off = img_off; p.top_k = top_k; p.top_p = top_p;
+    launch_set_sample_params(s, (SampleParams*)sp.p, p);
+    launch_set_dual_weights(s, (DualWeights*)dw.p, DualWeights{w_caption, w_layout});
+    SampleArgs a{};
+    a.logits_partial = partial; a.S = S; a.slab = slab; a.bias = bias; a.V = V; a.p = (const SampleParams*)sp.p;
+    a.force_tok = force_tok; a.force_mask = force_mask; a.out_tok = out_tok; a.logits_out = logits_out;
+    a.embed_table = embed_table; a.x = x; a.H = H; a.n_dec = (const int32_t*)nd.p; a.b_off = b_off; a.B_total = B_total;
+    launch_cfg3_sample(s, a, (const DualWeights*)dw.p, B, filtered != 0, stored != 0, (float*)pv.p, (int*)pi.p, (float*)mix.p);
+    if (mix_out && hipMemcpyAsync(mix_out, mix.p, (size_t)B * V * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return PG_ERR_HIP;
+    return finish(s);                                                                                // before the scratch goes away
+}
+
 // The text sampler's step through launch_text_argmax (mode 0) or launch_text_sample (mode 1: the in-scan Gumbel draw, temperature > 0).  partial fp32: slab s at
 // partial + s * slab, rows [B][V], slab >= B V -- an odd slab or V sends the scan down its scalar branch, multiples of 4 down the 16-byte one (then partial and
 // logits_out are 16-byte aligned).  out int64 [B][max_new] (written when step < max_new); unfinished int32 [B] in / out; logits_out fp32 [max_new][B][V] or null

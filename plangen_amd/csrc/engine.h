@@ -125,6 +125,7 @@ struct pg_engine {
     float* txt_mix = nullptr;                                    // top-k / top-p text sampler: reduced logit rows [max_rows, vocab] (first filtered call)
     float* cfg_mix = nullptr;                                    // top-k / top-p sampler: CFG-mixed rows [max_rows/2, img_vocab] (first filtered call)
     SampleParams* d_sparams = nullptr; TextParams* d_tparams = nullptr;   // per-call parameters the graphs read from HBM
+    DualWeights* d_dual = nullptr;                                // pg_decode_image_tokens_dual: (w_caption, w_layout), read from HBM in the same way
     // grammar-constrained text decode (pg_set_text_dfa): device tables allocated once at the limits (first upload), so a captured step keeps
     // valid addresses when another automaton is uploaded; pinned staging guarded by an event, like the prefill's row metadata
     int16_t* d_dfa_class = nullptr; int16_t* d_dfa_next = nullptr; int32_t* d_dfa_dist = nullptr; TextDfaHdr* d_dfa_hdr = nullptr;
@@ -310,6 +311,8 @@ struct pg_engine {
     template <typename F> int graph_step(hipGraphExec_t& exec, std::vector<int64_t>& cached, const std::vector<int64_t>& key, hipStream_t s, F&& record);
     int decode_image(int T, float cfgw, float temp, int top_k, float top_p, uint64_t seed, const int32_t* force_tok,
                      const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s);
+    int decode_image_dual(int T, float w_caption, float w_layout, float temp, int top_k, float top_p, uint64_t seed, const int32_t* force_tok,
+                          const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s);
     int step(const void* emb, int emb_dtype, void* hidden_out, int hidden_dtype, hipStream_t s);
     int gen_head(const void* h_dev, int h_dtype, float* logits, int R_, hipStream_t s);
     int text_greedy(int max_new, int min_new, int eos, int64_t* out, int* out_len, hipStream_t s) {

@@ -118,6 +118,12 @@ int pg_decode_image_tokens_filtered(pg_handle h, int T, float cfg_weight, float 
     if (!h || !out_tok_dev) return PG_ERR_ARG;
     return h->decode_image(T, cfg_weight, temperature, top_k, top_p, seed, force_tok_dev, force_mask_dev, out_tok_dev, logits_out_dev, (hipStream_t)s);
 }
+int pg_decode_image_tokens_dual(pg_handle h, int T, float w_caption, float w_layout, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                                const int32_t* force_tok_dev, const uint8_t* force_mask_dev, int32_t* out_tok_dev,
+                                float* logits_out_dev, pg_stream s) { TuneGuard _tg(h);
+    if (!h || !out_tok_dev) return PG_ERR_ARG;
+    return h->decode_image_dual(T, w_caption, w_layout, temperature, top_k, top_p, seed, force_tok_dev, force_mask_dev, out_tok_dev, logits_out_dev, (hipStream_t)s);
+}
 int pg_generate_text_greedy(pg_handle h, int max_new, int min_new, int eos_id, int64_t* out_dev, int* out_len_host, pg_stream s) { TuneGuard _tg(h);
     if (!h || !out_dev) return PG_ERR_ARG;
     return h->text_greedy(max_new, min_new, eos_id, out_dev, out_len_host, (hipStream_t)s);

@@ -279,7 +279,7 @@ int pg_engine::create() {
     TRY(dalloc(&cfg_pv, (size_t)cfg.max_rows * 16 * 4));
     TRY(dalloc(&cfg_pi, (size_t)cfg.max_rows * 16 * 4));
     HIPCHK(hipMemset(d_ndec, 0, 64));
-    TRY(dalloc(&d_sparams, 64)); TRY(dalloc(&d_tparams, 64));
+    TRY(dalloc(&d_sparams, 64)); TRY(dalloc(&d_tparams, 64)); TRY(dalloc(&d_dual, 64));
     {
         const size_t nt = (size_t)cfg.max_rows * (cfg.max_new + 1);     // [B, T] with B <= max_rows / 2 ... [R, max_new] for text
         TRY(dalloc(&d_out_tok, nt * 4)); TRY(dalloc(&d_force_tok, nt * 4)); TRY(dalloc(&d_force_mask, nt));

@@ -247,6 +247,13 @@ struct FilterArgs {
 };
 void launch_cfg_sample_filtered(hipStream_t s, const SampleArgs& a, int B, float* scratch_v, int* scratch_i, float* mix);
 struct FilterArgsPlan : FilterArgs { SamplePlanDev plan; };
+// Dual guidance (pg_decode_image_tokens_dual; definition: include/plangen_hip.h): three rows per image -- 3b = f (caption + layout), 3b + 1 = p
+// (caption only), 3b + 2 = u (negative) -- mixed = (u + w_caption (p - u)) + w_layout (f - p).  The same SampleArgs (x: rows [3B, H]; p->cfg_weight
+// unused); the two weights live in device memory of their own, so a captured step replays across calls.  filtered: store scan -> cfg_select_kernel
+// -> pick (V <= SEL_MAXV); stored: the unfiltered route also leaves the mixed rows in mix [B, V].  scratch: >= 16 * B floats and ints.
+struct DualWeights { float w_caption, w_layout; };
+void launch_set_dual_weights(hipStream_t s, DualWeights* dst, DualWeights v);
+void launch_cfg3_sample(hipStream_t s, const SampleArgs& a, const DualWeights* dw, int B, bool filtered, bool stored, float* scratch_v, int* scratch_i, float* mix);
 void launch_sample_filter(hipStream_t s, const float* rows, int B, int V, float temperature, int top_k, float top_p, uint8_t* keep);
 // text token: argmax over vocab of (sum_s partial) per row + EOS bookkeeping, writes out[b, step] (int64) and next-token embedding into x.
 // Per-call parameters (device memory, like SampleParams): temperature <= 0 is the greedy argmax; temperature > 0 draws by Gumbel-max over

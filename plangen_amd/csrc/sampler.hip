@@ -427,6 +427,126 @@ void launch_sample_filter(hipStream_t s, const float* rows, int B, int V, float 
     hipLaunchKernelGGL(cfg_select_kernel<false>, dim3(B), dim3(SEL_THREADS), 0, s, f);
 }
 
+// ------------------------------------------------------------------------------- dual guidance: three rows per image
+// Rows 3b = f (caption + layout), 3b + 1 = p (caption only), 3b + 2 = u (negative):
+//     mixed = (u + w_caption (p - u)) + w_layout (f - p)
+// (pg_decode_image_tokens_dual; definition: include/plangen_hip.h).  cfg3_scan_kernel is cfg_scan_kernel over triples -- the same grid, the same
+// load discipline (bias and the three rows of up to four slabs for four vocabulary entries in flight before the first use), the same slab sum
+// (bias first, then slabs in index order: a row of the triple has the bits the pair scan gives that row), the same tap, store, perturbation
+// and winner reduction -- and cfg3_pick_kernel is cfg_pick_kernel writing three rows of x.  Separate kernels: the pair instantiations are not
+// touched.  The two weights come from device memory (DualWeights), like every per-call value; p->cfg_weight is not read.
+template <bool STORE>
+__global__ __launch_bounds__(256) void cfg3_scan_kernel(SampleArgs a, const DualWeights* __restrict__ dw, float* __restrict__ pv, int* __restrict__ pi,
+                                                        float* __restrict__ mix) {
+    __shared__ float sv[4]; __shared__ int si[4];
+    const int b = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x, step = *a.n_dec;
+    const int bg = b + a.b_off, B = a.B_total;            // global image index
+    const int per = (a.V + CFG_CHUNKS - 1) / CFG_CHUNKS, v0 = ch * per, v1 = min(a.V, v0 + per);
+    const long rf = (long)(3 * b) * a.V;
+    float best = -INFINITY; int bi = 0x7fffffff;
+    const float temperature = a.p->temperature, w_c = dw->w_caption, w_l = dw->w_layout;
+    const uint64_t stream = (uint64_t)(bg + a.p->img_off) * 1000003ull + step;
+    const uint64_t seed = a.p->seed;
+    const float invT = temperature > 0.f ? 1.f / temperature : 1.f;
+    constexpr int IT = 4;
+    const float* bias0 = a.bias ? a.bias : a.logits_partial + rf;     // no bias: any mapped address, value discarded
+    const int ofpu[3] = {0, a.V, 2 * a.V};                            // f, p, u: adjacent rows
+    for (int vb = v0 + tid; vb < v1; vb += IT * 256) {
+        float bb[IT], fpu[IT][3];
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+            const int v = vb + it * 256, vc = v < v1 ? v : v1 - 1;
+            bb[it] = bias0[vc];
+        }
+        float t[IT][4][3];
+        const int smax = a.S > 0 ? a.S - 1 : 0;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+            const int v = vb + it * 256, vc = v < v1 ? v : v1 - 1;
+            const float* pp = a.logits_partial + rf + vc;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float* q = pp + (long)(u < smax ? u : smax) * a.slab;       // slab index clamped: branch-free loads
+                t[it][u][0] = q[0]; t[it][u][1] = q[a.V]; t[it][u][2] = q[2 * a.V];
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+            const int v = vb + it * 256, vc = v < v1 ? v : v1 - 1;
+            fpu[it][0] = a.bias ? bb[it] : 0.f; fpu[it][1] = fpu[it][0]; fpu[it][2] = fpu[it][0];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) if (u < a.S) { fpu[it][0] += t[it][u][0]; fpu[it][1] += t[it][u][1]; fpu[it][2] += t[it][u][2]; }
+            if (a.S > 4) sum_slabs<3>(a.logits_partial + rf + vc + 4 * a.slab, a.slab, a.S - 4, ofpu, fpu[it]);
+        }
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+            const int v = vb + it * 256;
+            if (v < v1) {
+                const float f = fpu[it][0], p = fpu[it][1], u = fpu[it][2];
+                float mixed = (u + w_c * (p - u)) + w_l * (f - p);
+                if (a.logits_out) a.logits_out[((long)step * B + bg) * a.V + v] = mixed;
+                if (STORE) { mix[(long)b * a.V + v] = mixed; continue; }
+                if (temperature > 0.f) mixed = gumbel_perturb(mixed, invT, seed, stream, v);
+                if (mixed > best) { best = mixed; bi = v; }
+            }
+        }
+    }
+    if (STORE) return;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
+        argmax_combine(best, bi, ov, oi);
+    }
+    if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+        float v = sv[0]; int i = si[0];
+        for (int k = 1; k < 4; ++k) argmax_combine(v, i, sv[k], si[k]);
+        pv[b * CFG_CHUNKS + ch] = v; pi[b * CFG_CHUNKS + ch] = i;
+    }
+}
+__global__ __launch_bounds__(256) void cfg3_pick_kernel(SampleArgs a, const float* __restrict__ pv, const int* __restrict__ pi) {
+    __shared__ int s_tok;
+    const int b = blockIdx.x, tid = threadIdx.x, step = *a.n_dec;
+    if (tid == 0) {
+        float v = pv[b * CFG_CHUNKS]; int i = pi[b * CFG_CHUNKS];
+        for (int k = 1; k < CFG_CHUNKS; ++k) argmax_combine(v, i, pv[b * CFG_CHUNKS + k], pi[b * CFG_CHUNKS + k]);
+        i = i < 0 ? 0 : (i >= a.V ? a.V - 1 : i);
+        int emit = i, feed = i;
+        const long bg = b + a.b_off;
+        const int T = a.p->T;
+        if (step < T && a.p->has_force) {
+            const int f = a.force_tok[bg * T + step];
+            if (a.p->has_mask) { if (a.force_mask[bg * T + step] == 0) { emit = f; feed = f; } }
+            else feed = f;
+        }
+        if (step < T) a.out_tok[bg * T + step] = emit;
+        feed = feed < 0 ? 0 : (feed >= a.V ? a.V - 1 : feed);
+        s_tok = feed;
+    }
+    __syncthreads();
+    const float* src = a.embed_table + (long)s_tok * a.H;
+    float* x0 = a.x + (long)(3 * b) * a.H;
+    for (int i = tid * 4; i < a.H; i += 1024) {
+        const f32x4 v = *(const f32x4*)(src + i);
+        *(f32x4*)(x0 + i) = v;
+        *(f32x4*)(x0 + a.H + i) = v;
+        *(f32x4*)(x0 + 2 * a.H + i) = v;
+    }
+}
+__global__ void set_dual_weights_kernel(DualWeights* dst, DualWeights v) { *dst = v; }
+void launch_set_dual_weights(hipStream_t s, DualWeights* dst, DualWeights v) { hipLaunchKernelGGL(set_dual_weights_kernel, dim3(1), dim3(1), 0, s, dst, v); }
+// One dual step.  filtered: store scan -> cfg_select_kernel<false> (it reads mix) -> pick.  Otherwise [stored: store scan ->] scan -> pick.
+void launch_cfg3_sample(hipStream_t s, const SampleArgs& a, const DualWeights* dw, int B, bool filtered, bool stored, float* scratch_v, int* scratch_i, float* mix) {
+    if (filtered || stored) hipLaunchKernelGGL(cfg3_scan_kernel<true>, dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, dw, scratch_v, scratch_i, mix);
+    if (filtered) {
+        FilterArgs f{};
+        f.mix = mix; f.V = a.V; f.p = a.p; f.pv = scratch_v; f.pi = scratch_i; f.n_dec = a.n_dec; f.b_off = a.b_off;
+        hipLaunchKernelGGL(cfg_select_kernel<false>, dim3(B), dim3(SEL_THREADS), 0, s, f);
+    } else hipLaunchKernelGGL(cfg3_scan_kernel<false>, dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, dw, scratch_v, scratch_i, (float*)nullptr);
+    hipLaunchKernelGGL(cfg3_pick_kernel, dim3(B), dim3(256), 0, s, a, scratch_v, scratch_i);
+}
+
 // text token (HF generate): greedy = argmax over vocab; sampled = Gumbel-max over logits / T (== multinomial(softmax(logits / T)));
 // finished rows emit eos, unfinished &= (tok != eos).  Two stages like the image sampler: grid (CFG_CHUNKS, B) scans V/CFG_CHUNKS logits with
 // 16-byte loads (split-K slabs summed in slab order), one block per row combines the winners (lowest index on ties =

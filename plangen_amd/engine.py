@@ -599,6 +599,51 @@ class Engine:
         res = (out,) + ((lg,) if return_logits else ()) + ((lp,) if return_logprobs else ()) + ((stt,) if stt is not None else ())
         return res if len(res) > 1 else res[0]
 
+    def decode_image_tokens_dual(self, T: Optional[int] = None, w_caption: float = 5.0, w_layout: float = 5.0, temperature: float = 0.0,
+                                 seed: int = 0, force_tokens: Optional[torch.Tensor] = None, force_mask: Optional[torch.Tensor] = None,
+                                 return_logits: bool = False, top_k: int = 0, top_p: float = 1.0, return_logprobs: bool = False,
+                                 return_stats=False):
+        """The fused decode loop under dual guidance (``pg_decode_image_tokens_dual``), after a prefill of R = 3B rows with
+        ``uncond_shared=False``: row 3b = caption + layout (f), 3b + 1 = caption only (p), 3b + 2 = negative (u);
+        ``mixed = (u + w_caption (p - u)) + w_layout (f - p)``.  Everything else -- shapes of the results, forcing, top_k / top_p,
+        return_logprobs, return_stats -- as :meth:`decode_image_tokens` with B = R / 3.  No sample plan."""
+        T = self.cfg.img_tokens if T is None else T
+        if self.R % 3:
+            raise PlanGenError(f"decode_image_tokens_dual: the batch has {self.R} rows, not a multiple of three")
+        B = self.R // 3
+        out = torch.zeros((B, T), dtype=torch.int32, device=self.device)
+        lp = self._request_logprobs((B, T)) if return_logprobs else None
+        stt = self._request_stats((B, T), return_stats) if _wants_stats(return_stats) else None
+        ft = self._dev(force_tokens, torch.int32) if force_tokens is not None else None
+        fm = self._dev(force_mask, torch.uint8) if force_mask is not None else None
+        lg = torch.zeros((T, B, self.cfg.img_vocab), dtype=torch.float32, device=self.device) if return_logits else None
+        self._check(self.lib.pg_decode_image_tokens_dual(self.h, T, float(w_caption), float(w_layout), float(temperature), int(top_k), float(top_p),
+                                                         int(seed), self._p(ft), self._p(fm), self._p(out), self._p(lg), self.stream),
+                    "pg_decode_image_tokens_dual")
+        self._keep = [ft, fm, out, lg, lp, stt]
+        res = (out,) + ((lg,) if return_logits else ()) + ((lp,) if return_logprobs else ()) + ((stt,) if stt is not None else ())
+        return res if len(res) > 1 else res[0]
+
+    @staticmethod
+    def cfg3_sample_op(partial, S, slab, bias, V, B, out_tok, logits_out, embed_table, x, H, w_caption, w_layout, temperature, seed, T, step,
+                       top_k=0, top_p=1.0, img_off=0, b_off=0, B_total=None, force_tok=None, force_mask=None, filtered=False, stored=False,
+                       mix_out=None, stream=None) -> int:
+        """``pg_diag_op_cfg3_sample`` (diagnostics library): one dual-guidance step of the image sampler on caller-given device tensors -- the
+        slabs ``partial`` (rows [3B, V] per slab: 3b = f, 3b + 1 = p, 3b + 2 = u), ``out_tok`` int32 [B_total, T], ``logits_out`` fp32
+        [T, B_total, V] or None, ``x`` fp32 [3B, H], ``mix_out`` fp32 [B, V] or None (the stored rows; needs filtered or stored).  Returns the
+        status code (0: PG_OK); the stream is synchronised."""
+        d = _lib.load_diag()
+        fn = d.pg_diag_op_cfg3_sample
+        _P, _I, _F = C.c_void_p, C.c_int, C.c_float
+        fn.restype = C.c_int
+        fn.argtypes = [_I, _I, _P, _I, C.c_long, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _F, C.c_uint64, _I, _F, _I, _I, _I, _I, _I, _P]
+        ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        B_total = b_off + B if B_total is None else B_total
+        stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        return fn(int(bool(filtered)), int(bool(stored)), ptr(partial), S, slab, ptr(bias), V, B, ptr(force_tok), ptr(force_mask), ptr(out_tok),
+                  ptr(logits_out), ptr(mix_out), ptr(embed_table), ptr(x), H, float(w_caption), float(w_layout), float(temperature), int(seed),
+                  int(top_k), float(top_p), T, step, img_off, b_off, B_total, stream)
+
     def _request_sample_plan(self, plan, T: int):
         """``pg_request_sample_plan`` for the next image decode (the library copies the host arrays before it returns)."""
         arrs = plan.arrays(T)

@@ -62,6 +62,29 @@ def t2i_infer_collate_batch(cond_ids: Sequence[Sequence[int]], neg_ids, pad_id: 
     return ids.int(), mask.int()
 
 
+def t2i_dual_collate_batch(cond_ids: Sequence[Sequence[int]], caption_ids: Sequence[Sequence[int]], neg_ids, pad_id: int, img_tokens: int,
+                           debug_max_seq_len: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The batch of the dual-guidance loop: triples.  Row 3k = the full prompt (caption + layout), 3k + 1 = the caption-only prompt,
+    3k + 2 = the negative prompt (one shared, or one per sample, as in ``t2i_infer_collate_batch``); every row left-padded to the longest.
+    Returns ids int32 [3B, L] and mask int32 [3B, L + img_tokens] (image part all ones)."""
+    bs = len(cond_ids)
+    if len(caption_ids) != bs:
+        raise PlanGenError(f"one caption-only prompt per sample expected (got {len(caption_ids)} for {bs})")
+    per_sample = len(neg_ids) > 0 and isinstance(neg_ids[0], (list, tuple, torch.Tensor))
+    negs = [list(n) for n in neg_ids] if per_sample else [list(neg_ids)] * bs
+    if len(negs) != bs:
+        raise PlanGenError("one negative prompt per sample expected")
+    caps = [list(c) for c in caption_ids]
+    L = max(max(map(len, cond_ids)), max(map(len, caps)), max(map(len, negs)))
+    if debug_max_seq_len is not None:
+        L = debug_max_seq_len
+    parts = [pad_input_ids(rows, pad_id, L) for rows in (cond_ids, caps, negs)]
+    ones = torch.ones((bs, img_tokens), dtype=torch.int32)
+    ids = torch.stack([i for i, _ in parts], dim=1).view(bs * 3, -1)
+    mask = torch.stack([torch.cat([m, ones], -1) for _, m in parts], dim=1).view(bs * 3, -1)
+    return ids.int(), mask.int()
+
+
 def _stats_on(v) -> bool:
     """The ``token_stats`` key / ``return_stats`` argument: False (or None) is off, True is n_alt = 0, an int is n_alt."""
     return v is not None and v is not False
@@ -92,6 +115,8 @@ class System:
     probable, 1 when absent); score_gt_layout (plan / uni_2stage / mmu: also score batch['gt_grounding'], see score_layouts; off when absent);
     score_gt_image (uni / uni_2stage: also score batch['image'], see score_images; off when absent); the sample-plan keys cfg_schedule /
     cfg_weight_end / cfg_weights / same_noise / cfg_weight_in_box / temperatures / top_ks / top_ps (see build_sample_plan; off when absent).
+    cfg_weight_layout (uni / uni_2stage; absent or None: off): dual guidance -- three rows per image, cfg_weight weighs the caption and this key the
+    layout (see t2i_dual).
     """
 
     def __init__(self, cfg: PlanGenConfig, engine: Engine, args: Optional[SimpleNamespace] = None, codec=None):
@@ -104,6 +129,8 @@ class System:
         self.last_sample_plan = None      # the sample-plan cfg keys: the record of the last t2i's plan (build_sample_plan), None when no key is set
         self.last_forced_prefix = None    # prefill_forced_prefix: t0 of the last t2i (0: nothing could be prefilled), None when the key is off
         self.last_selection = None        # select_best: dict(replica int64 [B0], score fp32 [B0], scores fp32 [p, B0]) of the last t2i
+        self.last_dual_guidance = None    # cfg_weight_layout: dict(w_caption, w_layout) of the last t2i_dual, None when the key is off
+        self.last_logprobs = None         # t2i_dual(return_logprobs=True): fp32 [B * p, T] of the last t2i_dual, None without it
         self.vl_gpt = MultiModalityCausalLM(engine)
         self.args = args or SimpleNamespace(seed=cfg.seed, parallel_size=1, cfg_weight=cfg.cfg_weight,
                                             temperature=cfg.temperature, top_k=cfg.top_k, top_p=cfg.top_p, use_teacher_forcing=False,
@@ -412,6 +439,102 @@ class System:
                                                          mode="bilinear", align_corners=False).to(dec)
         return dec, mask_image
 
+    # -------------------------------------------------------------- dual guidance
+    DUAL_REFUSED_KEYS = ("share_replicas", "prefill_forced_prefix", "select_best", "token_stats", "score_gt_image")
+
+    def dual_weight_layout(self) -> Optional[float]:
+        """The ``cfg_weight_layout`` cfg key: None (absent or None) is off, and then nothing changes."""
+        v = getattr(self.args, "cfg_weight_layout", None)
+        return None if v is None else float(v)
+
+    def check_dual_keys(self) -> None:
+        """The cfg keys the dual loop does not serve, refused by name before anything runs."""
+        a = self.args
+        on = [k for k in self.DUAL_REFUSED_KEYS if (_stats_on(getattr(a, k, False)) if k == "token_stats" else bool(int(getattr(a, k, 0) or 0)))]
+        on += self.plan_keys_set()
+        if on:
+            raise PlanGenError(f"cfg_weight_layout (dual guidance) cannot be combined with {' / '.join(on)}: the three-row loop has no replica sharing, "
+                               "no sample plan, no prefilled prefix and no statistics; select_best and score_gt_image would score another distribution")
+
+    def t2i_dual_collate_batch(self, cond_ids, caption_ids, neg_ids):
+        return t2i_dual_collate_batch(cond_ids, caption_ids, neg_ids, self.cfg.pad_id, self.image_token_num_per_image, self.args.debug_max_seq_len)
+
+    @torch.no_grad()
+    def t2i_dual(self, tokens3: torch.Tensor, mask3: torch.Tensor, w_caption: Optional[float] = None, w_layout: Optional[float] = None,
+                 temperature: Optional[float] = None, gt_image: Optional[torch.Tensor] = None, edit_region: Optional[torch.Tensor] = None,
+                 parallel_size: Optional[int] = None, top_k: Optional[int] = None, top_p: Optional[float] = None, return_logprobs: bool = False):
+        """``t2i`` under dual guidance: tokens3 int32 [3B, L] / mask3 [3B, L + T] are triples (``t2i_dual_collate_batch``: full prompt, caption-only
+        prompt, negative prompt); mixed = u + w_caption (p - u) + w_layout (f - p) with w_caption = args.cfg_weight and w_layout =
+        args.cfg_weight_layout unless given.  One prefill with uncond_shared=False, ``Engine.decode_image_tokens_dual``, then the VQ decoder.
+        Teacher forcing (use_teacher_forcing + gt_image + edit_region) takes the force arguments of ``t2i``; parallel_size > 1 replicates the triples
+        (first replica forced, the others free); top_k / top_p as in ``t2i``.  return_logprobs: the emitted tokens' log-probabilities fp32
+        [B * p, T] stay in ``self.last_logprobs`` (None otherwise).  Returns ``(dec, mask_image)`` like ``t2i``."""
+        a = self.args
+        self.check_dual_keys()
+        w_caption = a.cfg_weight if w_caption is None else w_caption
+        w_layout = self.dual_weight_layout() if w_layout is None else w_layout
+        if w_layout is None:
+            raise PlanGenError("t2i_dual needs w_layout (or the cfg key cfg_weight_layout)")
+        temperature = a.temperature if temperature is None else temperature
+        p = a.parallel_size if parallel_size is None else parallel_size
+        top_k = getattr(a, "top_k", 0) if top_k is None else top_k
+        top_p = getattr(a, "top_p", 1.0) if top_p is None else top_p
+        want_lp = bool(return_logprobs)
+        if tokens3.shape[0] % 3:
+            raise PlanGenError(f"t2i_dual: {tokens3.shape[0]} rows are not triples")
+        B0 = tokens3.shape[0] // 3
+        if 3 * B0 * p > self.engine.max_rows:
+            raise PlanGenError(f"cfg_weight_layout (dual guidance): 3 x {B0} prompts x parallel_size {p} = {3 * B0 * p} rows exceed the engine's "
+                               f"max_rows={self.engine.max_rows}")
+        gt_labels = None
+        if a.use_teacher_forcing and gt_image is not None:
+            gi = gt_image.to(torch.bfloat16) if self.engine.dtype == "bf16" else gt_image
+            gt_labels = self.vl_gpt.gen_vision_model.encode(gi)[-1][-1].reshape(gt_image.shape[0], -1).to(torch.int32)
+        force_region = edit_region
+        if p > 1:
+            tokens3, mask3 = torch.cat([tokens3] * p), torch.cat([mask3] * p)
+            if gt_labels is not None:          # as in t2i: only the first replica of every image is teacher-forced
+                gt_labels = torch.cat([gt_labels] * p)
+                force_region = torch.cat([edit_region] + [torch.ones_like(edit_region)] * (p - 1))
+        L = tokens3.shape[1]
+        self.engine.prefill(tokens3, Engine.pad_len_from_mask(mask3, L), position_mode=0, uncond_shared=False)
+        ft = fm = None
+        if gt_labels is not None and force_region is not None:
+            ft, fm = gt_labels, (force_region.reshape(gt_labels.shape[0], -1) != 0).to(torch.uint8)
+        res = self.engine.decode_image_tokens_dual(None, w_caption, w_layout, temperature, a.seed, ft, fm, False, top_k=top_k, top_p=top_p,
+                                                   **({"return_logprobs": True} if want_lp else {}))
+        toks, self.last_logprobs = (res if want_lp else (res, None))
+        self.last_dual_guidance = dict(w_caption=float(w_caption), w_layout=float(w_layout))
+        dec = self.vl_gpt.gen_vision_model.decode_code(toks.to(dtype=torch.int), shape=[B0 * p, self.cfg.img_dim, self.cfg.grid, self.cfg.grid])
+        self.last_generated_tokens = toks
+        mask_image = None
+        if a.use_teacher_forcing and edit_region is not None:
+            er = edit_region.to(dec.device)
+            bs, g = er.shape[0], self.cfg.grid
+            mask_image = torch.nn.functional.interpolate(er.reshape(bs, 1, g, g).repeat(1, 3, 1, 1).float(), size=(a.janus_hw, a.janus_hw),
+                                                         mode="bilinear", align_corners=False).to(dec)
+        return dec, mask_image
+
+    def _cfg_prompt_dual(self, batch: dict) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The triples of the image stage under dual guidance: the rows ``_cfg_prompt`` builds, and between them the caption-only row
+        wrap_uni_prompt(base_caption[i], '') -- the form the negative prompt uses for an absent layout -- or batch['caption_inputs_ids'] (one id
+        list per sample) for callers who stay on ids -> (ids [3B, L], mask [3B, L + T])."""
+        ids2, mask2 = self._cfg_prompt(batch)
+        L = ids2.shape[1]
+        rows = [ids2[r][mask2[r, :L].bool()].tolist() for r in range(ids2.shape[0])]
+        bs = len(rows) // 2
+        caps = batch.get("caption_inputs_ids")
+        if caps is not None:
+            caps = [[int(t) for t in c] for c in caps]
+        elif batch.get("base_caption") is not None and self.codec is not None:
+            caps = [self.wrap_uni_prompt(c, "")[1].tolist() for c in batch["base_caption"]]
+        else:
+            raise PlanGenError("cfg_weight_layout (dual guidance) needs the caption-only prompts: batch['caption_inputs_ids'], or batch['base_caption'] "
+                               "with a tokenizer (System(codec=...))")
+        if len(caps) != bs:
+            raise PlanGenError(f"cfg_weight_layout (dual guidance): {len(caps)} caption-only prompts for {bs} samples")
+        return self.t2i_dual_collate_batch(rows[0::2], caps, rows[1::2])
+
     # -------------------------------------------------------------- a12: text either side of the path
     def wrap_uni_prompt(self, caption: str, grounding: Optional[str] = None, in_stage1: bool = False):
         """plangen_base.py:232-261 -> (prompt string, ids LongTensor)."""
@@ -526,8 +649,17 @@ class System:
         if pred_image:
             if not use_uni_prompt_in_t2i:
                 raise PlanGenError("use_uni_prompt_in_t2i=False: the reference asserts False on this branch too (plangen_base.py:645-648)")
-            cfg_ids, cfg_mask = self._cfg_prompt(batch)
-            dec, edit_mask = self.t2i(cfg_ids, cfg_mask, gt_image=batch.get("image"), edit_region=batch.get("edit_region"))
+            self.last_dual_guidance = None
+            if self.dual_weight_layout() is not None:
+                # cfg_weight_layout (cfg key, absent / None: off): triples and the dual loop; cfg_weight is the caption weight
+                self.check_dual_keys()
+                self.last_token_stats = self.last_sample_plan = self.last_forced_prefix = self.last_selection = None
+                ids3, mask3 = self._cfg_prompt_dual(batch)
+                dec, edit_mask = self.t2i_dual(ids3, mask3, gt_image=batch.get("image"), edit_region=batch.get("edit_region"))
+                out["dual_guidance"] = self.last_dual_guidance
+            else:
+                cfg_ids, cfg_mask = self._cfg_prompt(batch)
+                dec, edit_mask = self.t2i(cfg_ids, cfg_mask, gt_image=batch.get("image"), edit_region=batch.get("edit_region"))
             out["pr_tokens"] = self.last_generated_tokens
             if self.last_token_stats is not None:
                 out["image_token_stats"] = self.last_token_stats["summary"]
@@ -569,7 +701,7 @@ class System:
                     extra["gt_layout_logprob"] = out["gt_layout_logprob"]
                 if "gt_image_logprob" in out:
                     extra["gt_image_logprob"] = out["gt_image_logprob"]
-                for k in ("image_token_stats", "text_token_stats", "sample_plan", "forced_prefix"):
+                for k in ("image_token_stats", "text_token_stats", "sample_plan", "dual_guidance", "forced_prefix"):
                     if k in out:
                         extra[k] = out[k]
                 if "image_entropy" in out:
