@@ -4,7 +4,7 @@
 // the understanding path's input-side kernels (SigLIP LayerNorm / patchify / add_pos, the VQ encoder's conv_in and nearest-code search, l2norm_rows, the
 // two-level batched GEMM of SigLIP's scores and P . V: tests/test_gpu_vision_ops.py) and of the decode GEMM dispatch itself -- launch_gemm_skinny /
 // launch_gemm_skinny_swiglu on the tiled copy or on row-major weights, with the caller's split count and stream_gemm mask: tests/test_gpu_skinny_ops.py --
-// and of the samplers' draw -- launch_cfg_sample / launch_cfg_sample_filtered and launch_text_argmax / launch_text_sample on the caller's slabs: tests/test_gpu_draws.py --
+// and of the samplers' draw -- launch_cfg_step and launch_text_argmax / launch_text_sample on the caller's slabs: tests/test_gpu_draws.py --
 // and of the weight converters pg_engine::load_tensor launches and the row movers of every prefill / step / score call (tests/test_gpu_load_ops.py) --
 // for the operator tests.  Each one points the calling thread's pg_tune at a local PgTune (no diagnostics hooks, one kernel-form selector set), calls the PRODUCTION launcher and restores
 // pg_tune.  Shapes the kernels do not support are refused with PG_ERR_ARG and never launched.  Head dimension: 128 for the LLM kernels (implied
@@ -594,6 +594,28 @@ struct Scratch {
     bool get(size_t bytes) { return hipMalloc(&p, bytes) == hipSuccess; }
     ~Scratch() { if (p) (void)hipFree(p); }
 };
+// What the three image sampler step operators allocate and fill alike: SampleParams (p.has_force / has_mask from the pointers), the step counter,
+// the 16 B winner slots, the mixed rows when the route stores them, and the SampleArgs over the caller's buffers.  Lives until finish(s).
+struct SamplerStep {
+    Scratch sp, nd, pv, pi, mix;
+    SampleArgs a{};
+    int setup(hipStream_t s, SampleParams p, bool need_mix, const float* partial, int S, long slab, const float* bias, int V, int B, const int32_t* force_tok,
+              const uint8_t* force_mask, int32_t* out_tok, float* logits_out, const float* embed_table, float* x, int H, int step, int b_off, int B_total) {
+        if (!sp.get(sizeof(SampleParams)) || !nd.get(4) || !pv.get((size_t)B * 16 * 4) || !pi.get((size_t)B * 16 * 4)) return PG_ERR_HIP;
+        if (need_mix && !mix.get((size_t)B * V * 4)) return PG_ERR_HIP;
+        const int32_t hstep = step;
+        if (hipMemcpy(nd.p, &hstep, 4, hipMemcpyHostToDevice) != hipSuccess) return PG_ERR_HIP;
+        p.has_force = force_tok != nullptr; p.has_mask = force_mask != nullptr;
+        launch_set_sample_params(s, (SampleParams*)sp.p, p);
+        a.logits_partial = partial; a.S = S; a.slab = slab; a.bias = bias; a.V = V; a.p = (const SampleParams*)sp.p;
+        a.force_tok = force_tok; a.force_mask = force_mask; a.out_tok = out_tok; a.logits_out = logits_out;
+        a.embed_table = embed_table; a.x = x; a.H = H; a.n_dec = (const int32_t*)nd.p; a.b_off = b_off; a.B_total = B_total;
+        return PG_OK;
+    }
+    void launch(hipStream_t s, const SamplePlanDev* plan, const DualWeights* dw, int rows_per_image, int B, bool filtered, bool stored) {
+        launch_cfg_step(s, a, plan, dw, rows_per_image, B, filtered, stored, (float*)pv.p, (int*)pi.p, (float*)mix.p);
+    }
+};
 }  // namespace
 extern "C" {
 
@@ -830,7 +852,7 @@ int pg_diag_op_gemm_skinny(int form, int stream_gemm, const void* x, const void*
 }
 
 // ------------------------------------------------------------------------------------------------ the samplers' draw (tests/test_gpu_draws.py)
-// The image sampler's step through its production launchers: launch_cfg_sample, or launch_cfg_sample_filtered when filtered != 0, on the caller's buffers.
+// The image sampler's step through its production launcher, launch_cfg_step (the filtered route when filtered != 0), on the caller's buffers.
 // partial fp32: slab s at partial + s * slab, rows [2B][V] (row 2b = cond, 2b + 1 = uncond), slab >= 2 B V; bias fp32 [V] or null; force_tok int32 [B_total][T] or
 // null (has_force), force_mask uint8 [B_total][T] or null (has_mask; needs force_tok); out_tok int32 [B_total][T]; logits_out fp32 [T][B_total][V] or null (then
 // step < T); embed_table fp32 [V][H]; x fp32 [2B][H].  The launch covers images [b_off, b_off + B) of B_total.  SampleParams, the step counter, the 16 B winner
@@ -846,26 +868,17 @@ int pg_diag_op_cfg_sample(int filtered, const float* partial, int S, long slab, 
     if (filtered && (V > SEL_MAXV || !(temperature > 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f))) return PG_ERR_ARG;
     LocalTune lt;
     const hipStream_t s = (hipStream_t)stream;
-    Scratch sp, nd, pv, pi, mix;
-    if (!sp.get(sizeof(SampleParams)) || !nd.get(4) || !pv.get((size_t)B * 16 * 4) || !pi.get((size_t)B * 16 * 4)) return PG_ERR_HIP;
-    if (filtered && !mix.get((size_t)B * V * 4)) return PG_ERR_HIP;
-    const int32_t hstep = step;
-    if (hipMemcpy(nd.p, &hstep, 4, hipMemcpyHostToDevice) != hipSuccess) return PG_ERR_HIP;
     SampleParams p{};
-    p.cfg_weight = cfg_weight; p.temperature = temperature; p.seed = seed; p.T = T; p.has_force = force_tok != nullptr; p.has_mask = force_mask != nullptr;
-    p.img_off = img_off; p.top_k = top_k; p.top_p = top_p;
-    launch_set_sample_params(s, (SampleParams*)sp.p, p);
-    SampleArgs a{};
-    a.logits_partial = partial; a.S = S; a.slab = slab; a.bias = bias; a.V = V; a.p = (const SampleParams*)sp.p;
-    a.force_tok = force_tok; a.force_mask = force_mask; a.out_tok = out_tok; a.logits_out = logits_out;
-    a.embed_table = embed_table; a.x = x; a.H = H; a.n_dec = (const int32_t*)nd.p; a.b_off = b_off; a.B_total = B_total;
-    if (filtered) launch_cfg_sample_filtered(s, a, B, (float*)pv.p, (int*)pi.p, (float*)mix.p);
-    else launch_cfg_sample(s, a, B, (float*)pv.p, (int*)pi.p);
+    p.cfg_weight = cfg_weight; p.temperature = temperature; p.seed = seed; p.T = T; p.img_off = img_off; p.top_k = top_k; p.top_p = top_p;
+    SamplerStep st;
+    const int rc = st.setup(s, p, filtered != 0, partial, S, slab, bias, V, B, force_tok, force_mask, out_tok, logits_out, embed_table, x, H, step, b_off, B_total);
+    if (rc != PG_OK) return rc;
+    st.launch(s, nullptr, nullptr, 2, B, filtered != 0, false);
     return finish(s);                                                                                // before the scratch goes away
 }
 
 // pg_diag_op_cfg_sample under a sample plan (tests/test_gpu_sample_plan_ops.py): device plan arrays in place of the five scalars -- w fp32 [B_total][T],
-// temperature fp32 / top_k int32 / top_p fp32 / key int32 [B_total], all indexed by the global image b_off + b -- through launch_cfg_sample_plan.  filtered != 0
+// temperature fp32 / top_k int32 / top_p fp32 / key int32 [B_total], all indexed by the global image b_off + b -- through launch_cfg_step's planned route.  filtered != 0
 // takes the store -> select -> pick route (the caller says so: the arrays live on the device; V <= SEL_MAXV); stored != 0 also runs the store scan on the
 // unfiltered route.  Everything else as pg_diag_op_cfg_sample.
 int pg_diag_op_cfg_sample_plan(int filtered, int stored, const float* partial, int S, long slab, const float* bias, int V, int B, const int32_t* force_tok,
@@ -880,24 +893,17 @@ int pg_diag_op_cfg_sample_plan(int filtered, int stored, const float* partial, i
     if (filtered && V > SEL_MAXV) return PG_ERR_ARG;
     LocalTune lt;
     const hipStream_t s = (hipStream_t)stream;
-    Scratch sp, nd, pv, pi, mix;
-    if (!sp.get(sizeof(SampleParams)) || !nd.get(4) || !pv.get((size_t)B * 16 * 4) || !pi.get((size_t)B * 16 * 4)) return PG_ERR_HIP;
-    if ((filtered || stored) && !mix.get((size_t)B * V * 4)) return PG_ERR_HIP;
-    const int32_t hstep = step;
-    if (hipMemcpy(nd.p, &hstep, 4, hipMemcpyHostToDevice) != hipSuccess) return PG_ERR_HIP;
     SampleParams p{};
-    p.seed = seed; p.T = T; p.has_force = force_tok != nullptr; p.has_mask = force_mask != nullptr; p.top_p = 1.f;
-    launch_set_sample_params(s, (SampleParams*)sp.p, p);
-    SampleArgsPlan a{};
-    a.logits_partial = partial; a.S = S; a.slab = slab; a.bias = bias; a.V = V; a.p = (const SampleParams*)sp.p;
-    a.force_tok = force_tok; a.force_mask = force_mask; a.out_tok = out_tok; a.logits_out = logits_out;
-    a.embed_table = embed_table; a.x = x; a.H = H; a.n_dec = (const int32_t*)nd.p; a.b_off = b_off; a.B_total = B_total;
-    a.plan = SamplePlanDev{w_dev, temperature_dev, top_k_dev, top_p_dev, key_dev};
-    launch_cfg_sample_plan(s, a, B, filtered != 0, stored != 0, (float*)pv.p, (int*)pi.p, (float*)mix.p);
+    p.seed = seed; p.T = T; p.top_p = 1.f;
+    SamplerStep st;
+    const int rc = st.setup(s, p, filtered || stored, partial, S, slab, bias, V, B, force_tok, force_mask, out_tok, logits_out, embed_table, x, H, step, b_off, B_total);
+    if (rc != PG_OK) return rc;
+    const SamplePlanDev plan{w_dev, temperature_dev, top_k_dev, top_p_dev, key_dev};
+    st.launch(s, &plan, nullptr, 2, B, filtered != 0, stored != 0);
     return finish(s);                                                                                // before the scratch goes away
 }
 
-// One dual-guidance step (tests/test_gpu_dual_ops.py) through launch_cfg3_sample: rows [3B][V] per slab (3b = f, 3b + 1 = p, 3b + 2 = u), slab >= 3 B V, x fp32
+// One dual-guidance step (tests/test_gpu_dual_ops.py) through launch_cfg_step at three rows per image: rows [3B][V] per slab (3b = f, 3b + 1 = p, 3b + 2 = u), slab >= 3 B V, x fp32
 // [3B][H].  filtered != 0: store scan -> select -> pick (V <= SEL_MAXV, temperature > 0); stored != 0: the unfiltered route also runs the store scan.  mix_out
 // fp32 [B][V] or null: the mixed rows the store scan left (filtered or stored).  Everything else as pg_diag_op_cfg_sample.
 int pg_diag_op_cfg3_sample(int filtered, int stored, const float* partial, int S, long slab, const float* bias, int V, int B, const int32_t* force_tok,
@@ -913,22 +919,16 @@ int pg_diag_op_cfg3_sample(int filtered, int stored, const float* partial, int S
     if (mix_out && !filtered && !stored) return PG_ERR_ARG;
     LocalTune lt;
     const hipStream_t s = (hipStream_t)stream;
-    Scratch sp, dw, nd, pv, pi, mix;
-    if (!sp.get(sizeof(SampleParams)) || !dw.get(sizeof(DualWeights)) || !nd.get(4) || !pv.get((size_t)B * 16 * 4) || !pi.get((size_t)B * 16 * 4)) return PG_ERR_HIP;
-    if ((filtered || stored) && !mix.get((size_t)B * V * 4)) return PG_ERR_HIP;
-    const int32_t hstep = step;
-    if (hipMemcpy(nd.p, &hstep, 4, hipMemcpyHostToDevice) != hipSuccess) return PG_ERR_HIP;
     SampleParams p{};
-    p.cfg_weight = w_caption; p.temperature = temperature; p.seed = seed; p.T = T; p.has_force = force_tok != nullptr; p.has_mask = force_mask != nullptr;
-    p.img_off = img_off; p.top_k = top_k; p.top_p = top_p;
-    launch_set_sample_params(s, (SampleParams*)sp.p, p);
+    p.cfg_weight = w_caption; p.temperature = temperature; p.seed = seed; p.T = T; p.img_off = img_off; p.top_k = top_k; p.top_p = top_p;
+    SamplerStep st;
+    Scratch dw;
+    if (!dw.get(sizeof(DualWeights))) return PG_ERR_HIP;
+    const int rc = st.setup(s, p, filtered || stored, partial, S, slab, bias, V, B, force_tok, force_mask, out_tok, logits_out, embed_table, x, H, step, b_off, B_total);
+    if (rc != PG_OK) return rc;
     launch_set_dual_weights(s, (DualWeights*)dw.p, DualWeights{w_caption, w_layout});
-    SampleArgs a{};
-    a.logits_partial = partial; a.S = S; a.slab = slab; a.bias = bias; a.V = V; a.p = (const SampleParams*)sp.p;
-    a.force_tok = force_tok; a.force_mask = force_mask; a.out_tok = out_tok; a.logits_out = logits_out;
-    a.embed_table = embed_table; a.x = x; a.H = H; a.n_dec = (const int32_t*)nd.p; a.b_off = b_off; a.B_total = B_total;
-    launch_cfg3_sample(s, a, (const DualWeights*)dw.p, B, filtered != 0, stored != 0, (float*)pv.p, (int*)pi.p, (float*)mix.p);
-    if (mix_out && hipMemcpyAsync(mix_out, mix.p, (size_t)B * V * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return PG_ERR_HIP;
+    st.launch(s, nullptr, (const DualWeights*)dw.p, 3, B, filtered != 0, stored != 0);
+    if (mix_out && hipMemcpyAsync(mix_out, st.mix.p, (size_t)B * V * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return PG_ERR_HIP;
     return finish(s);                                                                                // before the scratch goes away
 }
 

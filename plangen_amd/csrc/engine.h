@@ -309,6 +309,15 @@ struct pg_engine {
     int hop_in(hipStream_t s);
     int hop_out(hipStream_t ws, hipStream_t s);
     template <typename F> int graph_step(hipGraphExec_t& exec, std::vector<int64_t>& cached, const std::vector<int64_t>& key, hipStream_t s, F&& record);
+    // the image decode loop behind both entry points: what the entry point is and allows; everything else is the call's own arguments
+    struct ImageLoopSpec {
+        const char* name;                                         // the entry point, for messages
+        int rows_per_image;                                       // 2: cond / uncond; 3: dual guidance
+        float w, w_layout;                                        // cfg_weight, or (w_caption, w_layout)
+        bool takes_plan, two_lanes, shared_negative, aliased_replicas;
+    };
+    int image_loop(const ImageLoopSpec& sp, int T, float temp, int top_k, float top_p, uint64_t seed, const int32_t* force_tok, const uint8_t* force_mask,
+                   int32_t* out_tok, float* logits_out, hipStream_t s);
     int decode_image(int T, float cfgw, float temp, int top_k, float top_p, uint64_t seed, const int32_t* force_tok,
                      const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s);
     int decode_image_dual(int T, float w_caption, float w_layout, float temp, int top_k, float top_p, uint64_t seed, const int32_t* force_tok,

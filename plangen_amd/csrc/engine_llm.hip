@@ -561,31 +561,45 @@ int pg_engine::request_sample_plan(const pg_sample_plan* pl, hipStream_t s) {
     return PG_OK;
 }
 
-int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_p, uint64_t seed, const int32_t* force_tok,
-                            const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s) {
+// The image decode loop of both entry points: rows_per_image rows per image through the stack, one sampler step per token.  Everything around
+// the sampler step is row-agnostic; the spec says what the entry point allows and whose name the messages carry.
+int pg_engine::image_loop(const ImageLoopSpec& sp, int T, float temp, int top_k, float top_p, uint64_t seed, const int32_t* force_tok,
+                          const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s) {
+    const int rpi = sp.rows_per_image;
+    const bool dual = rpi == 3;
     const TokenRequests q = take_requests();      // the one-shot log-prob and stats requests: consumed whatever this call answers
     const bool score = q.lp_out != nullptr, stats = q.stats;
-    const bool plan = plan_req.pending; plan_req.pending = false;      // pg_request_sample_plan: one-shot in the same way
+    const bool plan = plan_req.pending; plan_req.pending = false;      // pg_request_sample_plan: one-shot in the same way (consumed, then refused, where no plan is taken)
     if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(PG_ERR_ARG, "top_k=%d must be >= 0 and top_p=%g in (0, 1]", top_k, (double)top_p);
-    if (!prefilled) FAIL(PG_ERR_STATE, "pg_decode_image_tokens before pg_prefill");
+    if (dual && (!std::isfinite(sp.w) || !std::isfinite(sp.w_layout))) FAIL(PG_ERR_ARG, "%s: w_caption and w_layout must be finite", sp.name);
+    if (!prefilled) FAIL(PG_ERR_STATE, "%s before pg_prefill", sp.name);
+    if (plan && !sp.takes_plan) FAIL(PG_ERR_ARG, "%s does not take a sample plan (pg_request_sample_plan); the plan is dropped", sp.name);
     if (kv8 && !fuse_rope) FAIL(PG_ERR_ARG, "the FP8 KV cache needs the fused decode attention (fuse_rope)");
+    if (lanes_opt == 2 && !sp.two_lanes) FAIL(PG_ERR_ARG, "%s does not support lanes = 2", sp.name);
     if (kv8 && lanes_opt == 2) FAIL(PG_ERR_ARG, "the FP8 KV cache does not support lanes = 2");
+    if (group_rows > 0 && !sp.aliased_replicas) FAIL(PG_ERR_STATE, "%s does not support replicas that alias their owner's prompt (pg_prefill_replicated, alias = 1)", sp.name);
     if (group_rows > 0 && lanes_opt == 2) FAIL(PG_ERR_ARG, "replicas that alias their owner's prompt (pg_prefill_replicated, alias = 1) do not support lanes = 2");
     if (group_rows > 0 && !fuse_rope) FAIL(PG_ERR_ARG, "replicas that alias their owner's prompt need the fused decode attention (fuse_rope)");
-    if (R % 2) FAIL(PG_ERR_ARG, "CFG decode needs an even number of rows (got %d)", R);
+    if (R % rpi) {
+        if (dual) FAIL(PG_ERR_ARG, "dual-guidance decode needs a multiple of three rows (got %d)", R);
+        FAIL(PG_ERR_ARG, "CFG decode needs an even number of rows (got %d)", R);
+    }
+    if (shared_len > 0 && !sp.shared_negative)
+        FAIL(PG_ERR_STATE, "%s: the prefill shared the negative prompt across odd rows, which are not the negative rows of "
+                           "triples; prefill with uncond_shared=False (the one-shot pg_set_option(\"uncond_shared_hint\", 0))", sp.name);
     if (n_dec_host != 0) FAIL(PG_ERR_STATE, "decode loop needs a fresh prefill");
     if (T < 1 || T - 1 > cfg.max_new) FAIL(PG_ERR_CAPACITY, "T=%d exceeds max_new=%d", T, cfg.max_new);
     if (max_len_host + T - 1 > slots) FAIL(PG_ERR_CAPACITY, "T=%d behind %d cached tokens (pg_prefill_extend) exceeds the %d KV slots", T, max_len_host, slots);
     if (max_pos_end() + T - 1 > max_pos) FAIL(PG_ERR_CAPACITY, "T=%d from position %d (pg_prefill_extend) exceeds the RoPE table (%d)", T, max_pos_end(), max_pos);
-    if (hfin_stale) FAIL(PG_ERR_STATE, "pg_decode_image_tokens after pg_rewind: a pg_prefill_extend must follow before anything samples");
-    if (score && q.lp_cap < (int64_t)(R / 2) * T) FAIL(PG_ERR_ARG, "token log-probs: capacity %lld floats is below B * T = %lld", (long long)q.lp_cap, (long long)(R / 2) * T);
+    if (hfin_stale) FAIL(PG_ERR_STATE, "%s after pg_rewind: a pg_prefill_extend must follow before anything samples", sp.name);
+    const int B = R / rpi;
+    if (score && q.lp_cap < (int64_t)B * T) FAIL(PG_ERR_ARG, "token log-probs: capacity %lld floats is below B * T = %lld", (long long)q.lp_cap, (long long)B * T);
     if (score && lanes_opt == 2) FAIL(PG_ERR_ARG, "token log-probs do not support lanes = 2");
-    if (stats && q.ts.capacity < (int64_t)(R / 2) * T) FAIL(PG_ERR_ARG, "token stats: capacity %lld positions is below B * T = %lld", (long long)q.ts.capacity, (long long)(R / 2) * T);
+    if (stats && q.ts.capacity < (int64_t)B * T) FAIL(PG_ERR_ARG, "token stats: capacity %lld positions is below B * T = %lld", (long long)q.ts.capacity, (long long)B * T);
     if (stats && lanes_opt == 2) FAIL(PG_ERR_ARG, "token stats do not support lanes = 2");
-    if (plan && (plan_req.B != R / 2 || plan_req.T != T)) FAIL(PG_ERR_ARG, "sample plan: requested for B=%d, T=%d, the call has B=%d, T=%d", plan_req.B, plan_req.T, R / 2, T);
+    if (plan && (plan_req.B != B || plan_req.T != T)) FAIL(PG_ERR_ARG, "sample plan: requested for B=%d, T=%d, the call has B=%d, T=%d", plan_req.B, plan_req.T, B, T);
     if (plan && lanes_opt == 2) FAIL(PG_ERR_ARG, "sample plans do not support lanes = 2");
     HIPCHK(hipSetDevice(dev));
-    const int B = R / 2;
     // the route of a planned call, from the host copies: filtered when any image is sampled with an active top-k / top-p
     bool plan_filtered = false;
     if (plan) {
@@ -612,6 +626,7 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     if (filtered && !plan) {
         if (cfg.img_vocab > SEL_MAXV) FAIL(PG_ERR_CAPACITY, "top-k / top-p sampler supports img_vocab <= %d (got %d)", SEL_MAXV, cfg.img_vocab);
     }
+    // cfg_mix is sized for max_rows / 2 images, which covers max_rows / 3
     if ((filtered || stored) && !cfg_mix) TRY(dalloc(&cfg_mix, (size_t)(cfg.max_rows / 2) * cfg.img_vocab * 4, false));
     // a lane is a view of its row range, built once: the loop writes no engine member (a second view is built, and unused, with one lane)
     DecodeView lane[2] = {view(0, nl == 2 ? R / 2 : R, 0), view(R / 2, R / 2, 1)};
@@ -621,26 +636,24 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     sa.bias = gh_b2; sa.V = cfg.img_vocab; sa.p = d_sparams;
     sa.force_tok = d_force_tok; sa.force_mask = d_force_mask; sa.out_tok = d_out_tok; sa.logits_out = logits_out;
     sa.embed_table = gen_table; sa.H = Hh; sa.B_total = B;
+    const SamplePlanDev pd = plan ? plan_dev() : SamplePlanDev{};
     auto sample = [&](hipStream_t st, DecodeView& v) {
         tc_on = time_attn && (n_dec_host % (time_stride > 0 ? time_stride : 1)) == 0;
         tic(st);
         if (bf) head_logits<bf16>(st, v, (const bf16*)v.hfin, v.rows); else head_logits<float>(st, v, (const float*)v.hfin, v.rows);
         toc(st, TC_HEAD, ((double)G * Hh + (double)cfg.img_vocab * G) * (double)esz);
-        sa.logits_partial = v.part; sa.S = v.S_last; sa.slab = v.slab_last; sa.x = v.x; sa.n_dec = v.d_ndec; sa.b_off = v.r0 / 2;
+        sa.logits_partial = v.part; sa.S = v.S_last; sa.slab = v.slab_last; sa.x = v.x; sa.n_dec = v.d_ndec; sa.b_off = v.r0 / rpi;
+        const int Bv = v.rows / rpi;
         tic(st);
-        if (plan) {          // the planned instantiations of the same launches
-            SampleArgsPlan pa{}; static_cast<SampleArgs&>(pa) = sa; pa.plan = plan_dev();
-            launch_cfg_sample_plan(st, pa, v.rows / 2, filtered, stored, v.cfg_pv, v.cfg_pi, v.cfg_mix);
-            if (score) launch_token_logprob_image_plan(st, pa, v.rows / 2, v.cfg_mix, d_logprob);
-            if (stats) launch_token_stats_image_plan(st, pa, v.rows / 2, v.cfg_mix, stats_out(q.ts.n_alt));
+        launch_cfg_step(st, sa, plan ? &pd : nullptr, d_dual, rpi, Bv, filtered, stored, v.cfg_pv, v.cfg_pi, v.cfg_mix);
+        // the two reducers read the row, the token, T and the temperature (the plan's, with a plan): nothing pair-shaped
+        if (plan) {
+            SampleArgsPlan pa{}; static_cast<SampleArgs&>(pa) = sa; pa.plan = pd;
+            if (score) launch_token_logprob_image_plan(st, pa, Bv, v.cfg_mix, d_logprob);
+            if (stats) launch_token_stats_image_plan(st, pa, Bv, v.cfg_mix, stats_out(q.ts.n_alt));
         } else {
-            if (filtered) launch_cfg_sample_filtered(st, sa, v.rows / 2, v.cfg_pv, v.cfg_pi, v.cfg_mix);
-            else {
-                if (stored) launch_cfg_store(st, sa, v.rows / 2, v.cfg_mix);    // the filtered route already leaves the mixed rows in cfg_mix
-                launch_cfg_sample(st, sa, v.rows / 2, v.cfg_pv, v.cfg_pi);
-            }
-            if (score) launch_token_logprob_image(st, sa, v.rows / 2, v.cfg_mix, d_logprob);
-            if (stats) launch_token_stats_image(st, sa, v.rows / 2, v.cfg_mix, stats_out(q.ts.n_alt));
+            if (score) launch_token_logprob_image(st, sa, Bv, v.cfg_mix, d_logprob);
+            if (stats) launch_token_stats_image(st, sa, Bv, v.cfg_mix, stats_out(q.ts.n_alt));
         }
         toc(st, TC_SAMPLE, (double)v.S_last * v.rows * cfg.img_vocab * 4.0);
         tc_on = false;
@@ -664,12 +677,13 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     };
     HIPCHK(hipEventRecord(ev_t0, ws));
     {   // per-call parameters and the caller's forcing tensors -> library-owned device memory (what the graph reads)
-        SampleParams sp{}; sp.cfg_weight = cfgw; sp.temperature = temp; sp.seed = seed; sp.T = T;
-        sp.has_force = force_tok != nullptr; sp.has_mask = force_mask != nullptr; sp.img_off = rng_image_offset;
-        sp.top_k = top_k; sp.top_p = top_p;
-        launch_set_sample_params(ws, d_sparams, sp);
+        SampleParams p{}; p.cfg_weight = sp.w; p.temperature = temp; p.seed = seed; p.T = T;
+        p.has_force = force_tok != nullptr; p.has_mask = force_mask != nullptr; p.img_off = rng_image_offset;
+        p.top_k = top_k; p.top_p = top_p;
+        launch_set_sample_params(ws, d_sparams, p);
+        if (dual) launch_set_dual_weights(ws, d_dual, DualWeights{sp.w, sp.w_layout});
         if (plan) HIPCHK(hipStreamWaitEvent(ws, ev_plan, 0));      // the request may have staged its arrays on another stream
-        if (plan) launch_plan_fill(ws, plan_dev(), plan_req.mask, B, T, cfgw, temp, top_k, top_p, rng_image_offset);      // the arrays the plan left out
+        if (plan) launch_plan_fill(ws, pd, plan_req.mask, B, T, sp.w, temp, top_k, top_p, rng_image_offset);      // the arrays the plan left out
         if (force_tok) HIPCHK(hipMemcpyAsync(d_force_tok, force_tok, (size_t)B * T * 4, hipMemcpyDeviceToDevice, ws));
         if (force_mask) HIPCHK(hipMemcpyAsync(d_force_mask, force_mask, (size_t)B * T, hipMemcpyDeviceToDevice, ws));
     }
@@ -677,9 +691,10 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     if (T > 1) n_dec_host++;
     int i = 1;
     if (graph) {
-        // shapes and kernel selection only: seeds, temperatures, T and the caller's buffers reach the kernels through
+        // shapes and kernel selection only: seeds, temperatures, weights, T and the caller's buffers reach the kernels through
         // device memory, so a bench / serving loop replays ONE instantiated graph across calls
-        std::vector<int64_t> key = {R, (int64_t)bf, (int64_t)logits_out, (int64_t)shared_len, (int64_t)fuse_rope, (int64_t)nl,
+        std::vector<int64_t> key = {rpi,                         // pairs or triples: the same R never replays the other loop's step
+                                    R, (int64_t)bf, (int64_t)logits_out, (int64_t)shared_len, (int64_t)fuse_rope, (int64_t)nl,
                                     (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch, (int64_t)skip_attn, (int64_t)filtered,
                                     (int64_t)group_rows,         // replica geometry: never replay a graph across different aliasing
                                     (int64_t)score,              // the scored step holds two more launches
@@ -699,101 +714,17 @@ int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_
     HIPCHK(hipGetLastError());
     return PG_OK;
 }
-
-// pg_decode_image_tokens_dual: decode_image's loop over triples of rows (3b = caption + layout, 3b + 1 = caption only, 3b + 2 = negative) with the
-// cfg3 sampler launches; one lane, no plan, no shared or replicated prompts.  Everything around the sampler is row-agnostic.
+int pg_engine::decode_image(int T, float cfgw, float temp, int top_k, float top_p, uint64_t seed, const int32_t* force_tok,
+                            const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s) {
+    return image_loop(ImageLoopSpec{"pg_decode_image_tokens", 2, cfgw, 0.f, true, true, true, true}, T, temp, top_k, top_p, seed, force_tok, force_mask,
+                      out_tok, logits_out, s);
+}
+// pg_decode_image_tokens_dual: triples of rows (3b = caption + layout, 3b + 1 = caption only, 3b + 2 = negative); one lane, no plan, no shared or
+// replicated prompts
 int pg_engine::decode_image_dual(int T, float w_caption, float w_layout, float temp, int top_k, float top_p, uint64_t seed, const int32_t* force_tok,
                                  const uint8_t* force_mask, int32_t* out_tok, float* logits_out, hipStream_t s) {
-    const TokenRequests q = take_requests();      // the one-shot log-prob and stats requests: consumed whatever this call answers
-    const bool score = q.lp_out != nullptr, stats = q.stats;
-    const bool plan = plan_req.pending; plan_req.pending = false;      // one-shot in the same way: consumed, then refused below
-    if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(PG_ERR_ARG, "top_k=%d must be >= 0 and top_p=%g in (0, 1]", top_k, (double)top_p);
-    if (!std::isfinite(w_caption) || !std::isfinite(w_layout)) FAIL(PG_ERR_ARG, "pg_decode_image_tokens_dual: w_caption and w_layout must be finite");
-    if (!prefilled) FAIL(PG_ERR_STATE, "pg_decode_image_tokens_dual before pg_prefill");
-    if (plan) FAIL(PG_ERR_ARG, "pg_decode_image_tokens_dual does not take a sample plan (pg_request_sample_plan); the plan is dropped");
-    if (kv8 && !fuse_rope) FAIL(PG_ERR_ARG, "the FP8 KV cache needs the fused decode attention (fuse_rope)");
-    if (lanes_opt == 2) FAIL(PG_ERR_ARG, "pg_decode_image_tokens_dual does not support lanes = 2");
-    if (group_rows > 0) FAIL(PG_ERR_STATE, "pg_decode_image_tokens_dual does not support replicas that alias their owner's prompt (pg_prefill_replicated, alias = 1)");
-    if (R % 3) FAIL(PG_ERR_ARG, "dual-guidance decode needs a multiple of three rows (got %d)", R);
-    if (shared_len > 0)
-        FAIL(PG_ERR_STATE, "pg_decode_image_tokens_dual: the prefill shared the negative prompt across odd rows, which are not the negative rows of "
-                           "triples; prefill with uncond_shared=False (the one-shot pg_set_option(\"uncond_shared_hint\", 0))");
-    if (n_dec_host != 0) FAIL(PG_ERR_STATE, "decode loop needs a fresh prefill");
-    if (T < 1 || T - 1 > cfg.max_new) FAIL(PG_ERR_CAPACITY, "T=%d exceeds max_new=%d", T, cfg.max_new);
-    if (max_len_host + T - 1 > slots) FAIL(PG_ERR_CAPACITY, "T=%d behind %d cached tokens (pg_prefill_extend) exceeds the %d KV slots", T, max_len_host, slots);
-    if (max_pos_end() + T - 1 > max_pos) FAIL(PG_ERR_CAPACITY, "T=%d from position %d (pg_prefill_extend) exceeds the RoPE table (%d)", T, max_pos_end(), max_pos);
-    if (hfin_stale) FAIL(PG_ERR_STATE, "pg_decode_image_tokens_dual after pg_rewind: a pg_prefill_extend must follow before anything samples");
-    const int B = R / 3;
-    if (score && q.lp_cap < (int64_t)B * T) FAIL(PG_ERR_ARG, "token log-probs: capacity %lld floats is below B * T = %lld", (long long)q.lp_cap, (long long)B * T);
-    if (stats && q.ts.capacity < (int64_t)B * T) FAIL(PG_ERR_ARG, "token stats: capacity %lld positions is below B * T = %lld", (long long)q.ts.capacity, (long long)B * T);
-    if (force_mask && !force_tok) FAIL(PG_ERR_ARG, "force_mask needs force_tok");
-    // top-k / top-p only act on sampled draws (greedy ignores them, as HF's warpers do)
-    const bool filtered = temp > 0.f && (top_k > 0 || top_p < 1.f);
-    if (filtered && cfg.img_vocab > SEL_MAXV) FAIL(PG_ERR_CAPACITY, "top-k / top-p sampler supports img_vocab <= %d (got %d)", SEL_MAXV, cfg.img_vocab);
-    HIPCHK(hipSetDevice(dev));
-    TRY(reserve_requests(q));
-    const bool stored = score || stats;
-    const bool graph = use_graph && !time_attn && T > 2;
-    // cfg_mix is sized for max_rows / 2 images, which covers max_rows / 3
-    if ((filtered || stored) && !cfg_mix) TRY(dalloc(&cfg_mix, (size_t)(cfg.max_rows / 2) * cfg.img_vocab * 4, false));
-    DecodeView v = view(0, R, 0);
-    const int Hh = H(), G = cfg.gen_head_dim;
-    SampleArgs sa{};
-    sa.bias = gh_b2; sa.V = cfg.img_vocab; sa.p = d_sparams;
-    sa.force_tok = d_force_tok; sa.force_mask = d_force_mask; sa.out_tok = d_out_tok; sa.logits_out = logits_out;
-    sa.embed_table = gen_table; sa.H = Hh; sa.B_total = B;
-    auto sample = [&](hipStream_t st) {
-        tc_on = time_attn && (n_dec_host % (time_stride > 0 ? time_stride : 1)) == 0;
-        tic(st);
-        if (bf) head_logits<bf16>(st, v, (const bf16*)v.hfin, v.rows); else head_logits<float>(st, v, (const float*)v.hfin, v.rows);
-        toc(st, TC_HEAD, ((double)G * Hh + (double)cfg.img_vocab * G) * (double)esz);
-        sa.logits_partial = v.part; sa.S = v.S_last; sa.slab = v.slab_last; sa.x = v.x; sa.n_dec = v.d_ndec; sa.b_off = 0;
-        tic(st);
-        launch_cfg3_sample(st, sa, d_dual, B, filtered, stored, v.cfg_pv, v.cfg_pi, v.cfg_mix);
-        // the two reducers read the row, the token, T and the temperature: nothing pair-shaped
-        if (score) launch_token_logprob_image(st, sa, B, v.cfg_mix, d_logprob);
-        if (stats) launch_token_stats_image(st, sa, B, v.cfg_mix, stats_out(q.ts.n_alt));
-        toc(st, TC_SAMPLE, (double)v.S_last * v.rows * cfg.img_vocab * 4.0);
-        tc_on = false;
-    };
-    if (time_attn) { tc_used = 0; tc_meta.clear(); }
-    hipStream_t ws = s;
-    if (graph) { TRY(hop_in(s)); ws = istream; }
-    auto iteration = [&](bool with_forward) -> int {
-        sample(ws);
-        if (with_forward) forward_decode(ws, v);
-        return PG_OK;
-    };
-    HIPCHK(hipEventRecord(ev_t0, ws));
-    {   // per-call parameters and the caller's forcing tensors -> library-owned device memory (what the graph reads)
-        SampleParams sp{}; sp.cfg_weight = w_caption; sp.temperature = temp; sp.seed = seed; sp.T = T;
-        sp.has_force = force_tok != nullptr; sp.has_mask = force_mask != nullptr; sp.img_off = rng_image_offset;
-        sp.top_k = top_k; sp.top_p = top_p;
-        launch_set_sample_params(ws, d_sparams, sp);
-        launch_set_dual_weights(ws, d_dual, DualWeights{w_caption, w_layout});
-        if (force_tok) HIPCHK(hipMemcpyAsync(d_force_tok, force_tok, (size_t)B * T * 4, hipMemcpyDeviceToDevice, ws));
-        if (force_mask) HIPCHK(hipMemcpyAsync(d_force_mask, force_mask, (size_t)B * T, hipMemcpyDeviceToDevice, ws));
-    }
-    TRY(iteration(T > 1));
-    if (T > 1) n_dec_host++;
-    int i = 1;
-    if (graph) {
-        // -3: no pair key starts with a negative row count.  Shapes and kernel selection only, as in decode_image
-        std::vector<int64_t> key = {-3, R, (int64_t)bf, (int64_t)logits_out, (int64_t)fuse_rope, (int64_t)(lpt_order && order_valid), (int64_t)tune_epoch,
-                                    (int64_t)skip_attn, (int64_t)filtered, (int64_t)score, (int64_t)(stats ? 1 + q.ts.n_alt : 0)};
-        for (; i < T - 1; ++i) { TRY(graph_step(gexec, gkey, key, ws, [&] { return iteration(true); })); n_dec_host++; }
-    } else {
-        for (; i < T - 1; ++i) { TRY(iteration(true)); n_dec_host++; }
-    }
-    if (T > 1) TRY(iteration(false));
-    HIPCHK(hipMemcpyAsync(out_tok, d_out_tok, (size_t)B * T * 4, hipMemcpyDeviceToDevice, ws));
-    if (score) HIPCHK(hipMemcpyAsync(q.lp_out, d_logprob, (size_t)B * T * 4, hipMemcpyDeviceToDevice, ws));
-    if (stats) TRY(stats_copy_out(q.ts, B, T, T, ws));
-    HIPCHK(hipEventRecord(ev_t1, ws));
-    TRY(hop_out(ws, s));
-    have_decode_t = true;
-    HIPCHK(hipGetLastError());
-    return PG_OK;
+    return image_loop(ImageLoopSpec{"pg_decode_image_tokens_dual", 3, w_caption, w_layout, false, false, false, false}, T, temp, top_k, top_p, seed,
+                      force_tok, force_mask, out_tok, logits_out, s);
 }
 
 int pg_engine::step(const void* emb, int emb_dtype, void* hidden_out, int hidden_dtype, hipStream_t s) {

@@ -230,12 +230,20 @@ struct SamplePlanDev { const float* w; const float* temperature; const int32_t* 
 struct SampleArgsPlan : SampleArgs { SamplePlanDev plan; };
 // bit i of mask: array i (w, temperature, top_k, top_p, key) was given by the request and is already in place.  Fills the others.
 void launch_plan_fill(hipStream_t s, const SamplePlanDev& d, int mask, int B, int T, float cfg_weight, float temperature, int top_k, float top_p, int img_off);
-// the planned step: filtered = some image of the plan is sampled with top_k > 0 or top_p < 1 (decided on the host); stored = also leave the mixed rows in mix
-void launch_cfg_sample_plan(hipStream_t s, const SampleArgsPlan& a, int B, bool filtered, bool stored, float* scratch_v, int* scratch_i, float* mix);
-// scratch: >= 16*B floats and ints
-void launch_cfg_sample(hipStream_t s, const SampleArgs& a, int B, float* scratch_v, int* scratch_i);
+// Dual guidance (pg_decode_image_tokens_dual; definition: include/plangen_hip.h): three rows per image -- 3b = f (caption + layout), 3b + 1 = p
+// (caption only), 3b + 2 = u (negative) -- mixed = (u + w_caption (p - u)) + w_layout (f - p).  The same SampleArgs (x: rows [3B, H]; p->cfg_weight
+// unused); the two weights live in device memory of their own, so a captured step replays across calls.
+struct DualWeights { float w_caption, w_layout; };
+struct SampleArgsDual : SampleArgs { const DualWeights* dw; };
+void launch_set_dual_weights(hipStream_t s, DualWeights* dst, DualWeights v);
+// One step of the image sampler over B images of rows_per_image rows: 2 (cond / uncond; plan: the planned instantiations, or null) or 3 (dual
+// guidance: dw, no plan).  filtered (decided on the host: some image is sampled with top_k > 0 or top_p < 1; V <= SEL_MAXV): store scan ->
+// cfg_select_kernel -> pick; otherwise scan -> pick, and stored puts the store scan in front, which leaves the mixed rows in mix [B, V] as the
+// filtered route does.  scratch: >= 16 * B floats and ints.
+void launch_cfg_step(hipStream_t s, const SampleArgs& a, const SamplePlanDev* plan, const DualWeights* dw, int rows_per_image, int B, bool filtered,
+                     bool stored, float* scratch_v, int* scratch_i, float* mix);
 // top-k / top-p sampler (temperature > 0; p->top_k, p->top_p): the scan writes the CFG-mixed rows to mix [B, V] (V <= SEL_MAXV),
-// one 1024-thread block per image selects the kept set and draws from it, then the same pick / feedback tail as launch_cfg_sample
+// one 1024-thread block per image selects the kept set and draws from it, then the same pick / feedback tail as the unfiltered route
 #define SEL_MAXV 16384
 struct FilterArgs {
     const float* mix; int V;                                      // rows [gridDim, V]
@@ -245,15 +253,7 @@ struct FilterArgs {
     float* pv; int* pi;                                           // sampler: winner -> stage-1 winner slots (null: no draw)
     const int32_t* n_dec; int b_off;
 };
-void launch_cfg_sample_filtered(hipStream_t s, const SampleArgs& a, int B, float* scratch_v, int* scratch_i, float* mix);
 struct FilterArgsPlan : FilterArgs { SamplePlanDev plan; };
-// Dual guidance (pg_decode_image_tokens_dual; definition: include/plangen_hip.h): three rows per image -- 3b = f (caption + layout), 3b + 1 = p
-// (caption only), 3b + 2 = u (negative) -- mixed = (u + w_caption (p - u)) + w_layout (f - p).  The same SampleArgs (x: rows [3B, H]; p->cfg_weight
-// unused); the two weights live in device memory of their own, so a captured step replays across calls.  filtered: store scan -> cfg_select_kernel
-// -> pick (V <= SEL_MAXV); stored: the unfiltered route also leaves the mixed rows in mix [B, V].  scratch: >= 16 * B floats and ints.
-struct DualWeights { float w_caption, w_layout; };
-void launch_set_dual_weights(hipStream_t s, DualWeights* dst, DualWeights v);
-void launch_cfg3_sample(hipStream_t s, const SampleArgs& a, const DualWeights* dw, int B, bool filtered, bool stored, float* scratch_v, int* scratch_i, float* mix);
 void launch_sample_filter(hipStream_t s, const float* rows, int B, int V, float temperature, int top_k, float top_p, uint8_t* keep);
 // text token: argmax over vocab of (sum_s partial) per row + EOS bookkeeping, writes out[b, step] (int64) and next-token embedding into x.
 // Per-call parameters (device memory, like SampleParams): temperature <= 0 is the greedy argmax; temperature > 0 draws by Gumbel-max over
@@ -308,14 +308,12 @@ void launch_set_text_op_params(hipStream_t s, TextParams* dst, TextParams v, int
 // mode: 0 greedy, 1 Gumbel-max in the scan, 2 scan -> mix -> text_select_kernel (as pg_engine::text_generate picks them)
 void launch_text_constrained(hipStream_t s, const TextArgs& a, const TextDfaArgs& d, int B, int mode, float* scratch_v, int* scratch_i, float* mix);
 // Token log-probabilities (pg_request_token_logprobs / pg_op_token_logprob; definition: include/plangen_hip.h).  The stored-row route: when a
-// call asks for scores, the loop also leaves the row y the draw is made from in the samplers' row workspace (cfg_scan_kernel<true> -> cfg_mix,
+// call asks for scores, the loop also leaves the row y the draw is made from in the samplers' row workspace (the STORE scan of launch_cfg_step -> cfg_mix,
 // TEXT_STORE -> txt_mix: the instantiations the top-k / top-p samplers already use) and, after the pick, one 1024-thread block per row reads
 // that row and the emitted token and writes one float: x = y * (1 / temperature) (temperature > 0, else y), NaN as -inf, a max pass and a
 // sum-of-expf pass over the L2-resident row with 16-byte loads, fixed-shape reductions (the result does not depend on scheduling).
 // The kernels' argument structs and the row reader both reducers share: stored_row.h.
 void launch_token_logprob_op(hipStream_t s, const float* rows, int B, int V, const int32_t* tok, float temperature, float* out);
-// the CFG-mixed rows of this step -> mix [B, V] (cfg_scan_kernel<true>; nothing else is written except the logits_out tap's own values)
-void launch_cfg_store(hipStream_t s, const SampleArgs& a, int B, float* mix);
 void launch_token_logprob_image(hipStream_t s, const SampleArgs& a, int B, const float* mix, float* out);
 void launch_token_logprob_image_plan(hipStream_t s, const SampleArgsPlan& a, int B, const float* mix, float* out);
 // the reduced text rows of this step (EOS ban and, with d != null, the automaton's mask applied) -> mix [B, V] (the TEXT_STORE scan).  It

@@ -8,11 +8,17 @@
 #include "stored_row.h"
 
 // ------------------------------------------------------------------------------- CFG + sample
-// One block per image b (rows 2b = cond, 2b+1 = uncond).  mixed = u + w (c - u)
-// (plangen_base.py:587); greedy: first index of the max (torch.argmax tie rule);
-// temperature > 0: Gumbel-max == multinomial(softmax(mixed / T)).  Then the chosen (or
-// forced) token's precomputed gen_aligner(gen_embed(tok)) row is written to both CFG rows
-// of the residual stream (plangen_base.py:602-604).
+// One block per image b over its NR adjacent rows of the logits.
+//   NR = 2 (pg_decode_image_tokens): rows 2b = cond, 2b + 1 = uncond; mixed = u + w (c - u) (plangen_base.py:587), w = p->cfg_weight or the
+//       plan's w[bg][step].
+//   NR = 3 (pg_decode_image_tokens_dual; definition: include/plangen_hip.h): rows 3b = f (caption + layout), 3b + 1 = p (caption only),
+//       3b + 2 = u (negative); mixed = (u + w_caption (p - u)) + w_layout (f - p), the two weights from device memory (DualWeights), like
+//       every per-call value; p->cfg_weight is not read.
+// Greedy: first index of the max (torch.argmax tie rule); temperature > 0: Gumbel-max == multinomial(softmax(mixed / T)).  Then the chosen
+// (or forced) token's precomputed gen_aligner(gen_embed(tok)) row is written to all NR rows of the residual stream (plangen_base.py:602-604).
+// Everything but the guidance source and the mixing expression is one body: the chunking, the load discipline, the slab sum (bias first, then
+// slabs in index order: a row of a triple has the bits the pair scan gives that row), the tap, the store, the perturbation, the winner
+// reduction and the forcing rules.
 __device__ __forceinline__ void argmax_combine(float& v, int& i, float ov, int oi) {
     if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
 }
@@ -26,68 +32,87 @@ __device__ __forceinline__ float gumbel_perturb(float mixed, float invT, uint64_
     const float uu = rng_uniform(seed, stream, v);
     return mixed * invT - __logf(-__logf(uu));
 }
-// STORE (filtered sampler): also write the CFG-mixed row to mix [B, V] and leave the draw to cfg_select_kernel
-// PLAN (pg_request_sample_plan): the block's image reads its own temperature, key and this step's weight from the plan's device arrays, once,
-// in front of the loop; everything else is the same code.  The plain instantiations take the plain SampleArgs.
-template <bool STORE, bool PLAN = false>
-__global__ __launch_bounds__(256) void cfg_scan_kernel(typename std::conditional<PLAN, SampleArgsPlan, SampleArgs>::type a, float* __restrict__ pv,
-                                                       int* __restrict__ pi, float* __restrict__ mix) {
+// The scan's argument struct: the plain SampleArgs, with the plan's arrays (PLAN) or the dual weights' address (NR = 3) behind it.
+template <int NR, bool PLAN> struct CfgScanArgs { using type = typename std::conditional<PLAN, SampleArgsPlan, SampleArgs>::type; };
+template <> struct CfgScanArgs<3, false> { using type = SampleArgsDual; };
+// STORE (filtered sampler, stored-row route): write the mixed row to mix [B, V] and nothing else but the tap; the draw is left to cfg_select_kernel
+// or to the scan that follows.  PLAN (pg_request_sample_plan, NR = 2): the block's image reads its own temperature, key and this step's weight
+// from the plan's device arrays, once, in front of the loop.
+template <int NR, bool STORE, bool PLAN = false>
+__global__ __launch_bounds__(256) void cfg_scan_kernel(typename CfgScanArgs<NR, PLAN>::type a, float* __restrict__ pv, int* __restrict__ pi,
+                                                       float* __restrict__ mix) {
+    static_assert(NR == 2 || (NR == 3 && !PLAN), "pairs (plain or planned) and plain triples");
     __shared__ float sv[4]; __shared__ int si[4];
     const int b = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x, step = *a.n_dec;
     const int bg = b + a.b_off, B = a.B_total;            // global image index (lane-independent results)
     const int per = (a.V + CFG_CHUNKS - 1) / CFG_CHUNKS, v0 = ch * per, v1 = min(a.V, v0 + per);
-    const long rc = (long)(2 * b) * a.V, ru = (long)(2 * b + 1) * a.V;
+    const long r0 = (long)(NR * b) * a.V;
     float best = -INFINITY; int bi = 0x7fffffff;
-    float temperature, cfg_weight; uint64_t stream;
+    float temperature, cfg_weight = 0.f, w_c = 0.f, w_l = 0.f; uint64_t stream;
     if constexpr (PLAN) {
         const int T = a.p->T;
         temperature = a.plan.temperature[bg];
         cfg_weight = a.plan.w[(long)bg * T + (step < T ? step : T - 1)];
         stream = (uint64_t)a.plan.key[bg] * 1000003ull + step;
     } else {
-        temperature = a.p->temperature; cfg_weight = a.p->cfg_weight;
+        temperature = a.p->temperature;
+        if constexpr (NR == 3) { w_c = a.dw->w_caption; w_l = a.dw->w_layout; } else cfg_weight = a.p->cfg_weight;
         stream = (uint64_t)(bg + a.p->img_off) * 1000003ull + step;
     }
     const uint64_t seed = a.p->seed;
     const float invT = temperature > 0.f ? 1.f / temperature : 1.f;
-    // four vocabulary entries per thread per pass, ALL their loads (bias, cond / uncond row of every slab) issued before the first use
+    // four vocabulary entries per thread per pass, ALL their loads (bias, the NR rows of every slab) issued before the first use
     // (indices clamped into the chunk): one memory round trip per pass instead of one per entry
     constexpr int IT = 4;
-    const float* bias0 = a.bias ? a.bias : a.logits_partial + rc;     // no bias: any mapped address, value discarded
-    const int ocu[2] = {0, a.V};                                      // cond row, uncond row (adjacent rows)
+    const float* bias0 = a.bias ? a.bias : a.logits_partial + r0;     // no bias: any mapped address, value discarded
+    int off[NR];                                                      // the image's rows are adjacent
+#pragma unroll
+    for (int r = 0; r < NR; ++r) off[r] = r * a.V;
     for (int vb = v0 + tid; vb < v1; vb += IT * 256) {
-        float bb[IT], cu[IT][2];
+        float bb[IT], row[IT][NR];
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
             const int v = vb + it * 256, vc = v < v1 ? v : v1 - 1;
             bb[it] = bias0[vc];
         }
-        float t[IT][4][2];
+        float t[IT][4][NR];
         const int smax = a.S > 0 ? a.S - 1 : 0;
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
             const int v = vb + it * 256, vc = v < v1 ? v : v1 - 1;
-            const float* pp = a.logits_partial + rc + vc;
+            const float* pp = a.logits_partial + r0 + vc;
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const float* q = pp + (long)(u < smax ? u : smax) * a.slab;       // slab index clamped: branch-free loads
-                t[it][u][0] = q[0]; t[it][u][1] = q[a.V];
+#pragma unroll
+                for (int r = 0; r < NR; ++r) t[it][u][r] = q[r * a.V];
             }
         }
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
             const int v = vb + it * 256, vc = v < v1 ? v : v1 - 1;
-            cu[it][0] = a.bias ? bb[it] : 0.f; cu[it][1] = cu[it][0];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) if (u < a.S) { cu[it][0] += t[it][u][0]; cu[it][1] += t[it][u][1]; }
-            if (a.S > 4) sum_slabs<2>(a.logits_partial + rc + vc + 4 * a.slab, a.slab, a.S - 4, ocu, cu[it]);
+            for (int r = 0; r < NR; ++r) row[it][r] = a.bias ? bb[it] : 0.f;
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (u < a.S) {
+#pragma unroll
+                    for (int r = 0; r < NR; ++r) row[it][r] += t[it][u][r];
+                }
+            if (a.S > 4) sum_slabs<NR>(a.logits_partial + r0 + vc + 4 * a.slab, a.slab, a.S - 4, off, row[it]);
         }
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
             const int v = vb + it * 256;
             if (v < v1) {
-                const float c = cu[it][0], u = cu[it][1];
-                float mixed = u + cfg_weight * (c - u);
+                float mixed;
+                if constexpr (NR == 3) {
+                    const float f = row[it][0], p = row[it][1], u = row[it][2];
+                    mixed = (u + w_c * (p - u)) + w_l * (f - p);
+                } else {
+                    const float c = row[it][0], u = row[it][1];
+                    mixed = u + cfg_weight * (c - u);
+                }
                 if (a.logits_out) a.logits_out[((long)step * B + bg) * a.V + v] = mixed;
                 if (STORE) { mix[(long)b * a.V + v] = mixed; continue; }
                 if (temperature > 0.f) mixed = gumbel_perturb(mixed, invT, seed, stream, v);
@@ -109,6 +134,7 @@ __global__ __launch_bounds__(256) void cfg_scan_kernel(typename std::conditional
         pv[b * CFG_CHUNKS + ch] = v; pi[b * CFG_CHUNKS + ch] = i;
     }
 }
+template <int NR>
 __global__ __launch_bounds__(256) void cfg_pick_kernel(SampleArgs a, const float* __restrict__ pv, const int* __restrict__ pi) {
     __shared__ int s_tok;
     const int b = blockIdx.x, tid = threadIdx.x, step = *a.n_dec;
@@ -130,21 +156,17 @@ __global__ __launch_bounds__(256) void cfg_pick_kernel(SampleArgs a, const float
     }
     __syncthreads();
     const float* src = a.embed_table + (long)s_tok * a.H;
-    float* x0 = a.x + (long)(2 * b) * a.H;
+    float* x0 = a.x + (long)(NR * b) * a.H;
     for (int i = tid * 4; i < a.H; i += 1024) {
         const f32x4 v = *(const f32x4*)(src + i);
-        *(f32x4*)(x0 + i) = v;
-        *(f32x4*)(x0 + a.H + i) = v;
+#pragma unroll
+        for (int r = 0; r < NR; ++r) *(f32x4*)(x0 + r * a.H + i) = v;
     }
 }
 __global__ void set_sample_params_kernel(SampleParams* dst, SampleParams v) { *dst = v; }
 void launch_set_sample_params(hipStream_t s, SampleParams* dst, SampleParams v) { hipLaunchKernelGGL(set_sample_params_kernel, dim3(1), dim3(1), 0, s, dst, v); }
 __global__ void set_text_params_kernel(TextParams* dst, TextParams v) { *dst = v; }
 void launch_set_text_params(hipStream_t s, TextParams* dst, TextParams v) { hipLaunchKernelGGL(set_text_params_kernel, dim3(1), dim3(1), 0, s, dst, v); }
-void launch_cfg_sample(hipStream_t s, const SampleArgs& a, int B, float* scratch_v, int* scratch_i) {
-    hipLaunchKernelGGL(cfg_scan_kernel<false>, dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i, (float*)nullptr);
-    hipLaunchKernelGGL(cfg_pick_kernel, dim3(B), dim3(256), 0, s, a, scratch_v, scratch_i);
-}
 
 // ------------------------------------------------------------------------------- top-k / top-p sampler
 // One 1024-thread block per image over its row x = mixed * invT (kept in LDS as the raw mixed values).
@@ -387,23 +409,25 @@ __global__ __launch_bounds__(SEL_THREADS) void cfg_select_kernel(typename std::c
         f.pv[b * CFG_CHUNKS + tid] = v; f.pi[b * CFG_CHUNKS + tid] = i;
     }
 }
-void launch_cfg_sample_filtered(hipStream_t s, const SampleArgs& a, int B, float* scratch_v, int* scratch_i, float* mix) {
-    hipLaunchKernelGGL(cfg_scan_kernel<true>, dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i, mix);
-    FilterArgs f{};
-    f.mix = mix; f.V = a.V; f.p = a.p; f.pv = scratch_v; f.pi = scratch_i; f.n_dec = a.n_dec; f.b_off = a.b_off;
-    hipLaunchKernelGGL(cfg_select_kernel<false>, dim3(B), dim3(SEL_THREADS), 0, s, f);
-    hipLaunchKernelGGL(cfg_pick_kernel, dim3(B), dim3(256), 0, s, a, scratch_v, scratch_i);
-}
-// The planned step.  Filtered route: store scan -> planned select -> pick (the mixed rows are in mix afterwards).  Otherwise: [store scan ->] scan -> pick.
-void launch_cfg_sample_plan(hipStream_t s, const SampleArgsPlan& a, int B, bool filtered, bool stored, float* scratch_v, int* scratch_i, float* mix) {
-    const SampleArgs& base = a;
-    if (filtered || stored) hipLaunchKernelGGL((cfg_scan_kernel<true, true>), dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i, mix);
+// One step of the image sampler.  filtered: store scan -> select (it reads mix and leaves the winner in slot 0) -> pick, never a second scan.
+// Otherwise [stored: store scan ->] scan -> pick.  The store scan writes no winner slots.
+template <int NR, bool PLAN, class A>
+static void cfg_step(hipStream_t s, const A& a, int B, bool filtered, bool stored, float* scratch_v, int* scratch_i, float* mix) {
+    const dim3 grid(CFG_CHUNKS, B);
+    if (filtered || stored) hipLaunchKernelGGL((cfg_scan_kernel<NR, true, PLAN>), grid, dim3(256), 0, s, a, (float*)nullptr, (int*)nullptr, mix);
     if (filtered) {
-        FilterArgsPlan f{};
-        f.mix = mix; f.V = a.V; f.p = a.p; f.pv = scratch_v; f.pi = scratch_i; f.n_dec = a.n_dec; f.b_off = a.b_off; f.plan = a.plan;
-        hipLaunchKernelGGL(cfg_select_kernel<true>, dim3(B), dim3(SEL_THREADS), 0, s, f);
-    } else hipLaunchKernelGGL((cfg_scan_kernel<false, true>), dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, scratch_v, scratch_i, (float*)nullptr);
-    hipLaunchKernelGGL(cfg_pick_kernel, dim3(B), dim3(256), 0, s, base, scratch_v, scratch_i);
+        typename std::conditional<PLAN, FilterArgsPlan, FilterArgs>::type f{};
+        f.mix = mix; f.V = a.V; f.p = a.p; f.pv = scratch_v; f.pi = scratch_i; f.n_dec = a.n_dec; f.b_off = a.b_off;
+        if constexpr (PLAN) f.plan = a.plan;
+        hipLaunchKernelGGL(cfg_select_kernel<PLAN>, dim3(B), dim3(SEL_THREADS), 0, s, f);
+    } else hipLaunchKernelGGL((cfg_scan_kernel<NR, false, PLAN>), grid, dim3(256), 0, s, a, scratch_v, scratch_i, (float*)nullptr);
+    hipLaunchKernelGGL(cfg_pick_kernel<NR>, dim3(B), dim3(256), 0, s, static_cast<const SampleArgs&>(a), scratch_v, scratch_i);
+}
+void launch_cfg_step(hipStream_t s, const SampleArgs& a, const SamplePlanDev* plan, const DualWeights* dw, int rows_per_image, int B, bool filtered,
+                     bool stored, float* scratch_v, int* scratch_i, float* mix) {
+    if (rows_per_image == 3) { SampleArgsDual d{}; static_cast<SampleArgs&>(d) = a; d.dw = dw; cfg_step<3, false>(s, d, B, filtered, stored, scratch_v, scratch_i, mix); }
+    else if (plan) { SampleArgsPlan p{}; static_cast<SampleArgs&>(p) = a; p.plan = *plan; cfg_step<2, true>(s, p, B, filtered, stored, scratch_v, scratch_i, mix); }
+    else cfg_step<2, false>(s, a, B, filtered, stored, scratch_v, scratch_i, mix);
 }
 // the arrays a plan left out <- the call's scalars (key: global image index + img_off); one thread per (image, step)
 __global__ __launch_bounds__(256) void plan_fill_kernel(SamplePlanDev d, int mask, int B, int T, float cfg_weight, float temperature, int top_k, float top_p,
@@ -427,125 +451,8 @@ void launch_sample_filter(hipStream_t s, const float* rows, int B, int V, float 
     hipLaunchKernelGGL(cfg_select_kernel<false>, dim3(B), dim3(SEL_THREADS), 0, s, f);
 }
 
-// ------------------------------------------------------------------------------- dual guidance: three rows per image
-// Rows 3b = f (caption + layout), 3b + 1 = p (caption only), 3b + 2 = u (negative):
-//     mixed = (u + w_caption (p - u)) + w_layout (f - p)
-// (pg_decode_image_tokens_dual; definition: include/plangen_hip.h).  cfg3_scan_kernel is cfg_scan_kernel over triples -- the same grid, the same
-// load discipline (bias and the three rows of up to four slabs for four vocabulary entries in flight before the first use), the same slab sum
-// (bias first, then slabs in index order: a row of the triple has the bits the pair scan gives that row), the same tap, store, perturbation
-// and winner reduction -- and cfg3_pick_kernel is cfg_pick_kernel writing three rows of x.  Separate kernels: the pair instantiations are not
-// touched.  The two weights come from device memory (DualWeights), like every per-call value; p->cfg_weight is not read.
-template <bool STORE>
-__global__ __launch_bounds__(256) void cfg3_scan_kernel(SampleArgs a, const DualWeights* __restrict__ dw, float* __restrict__ pv, int* __restrict__ pi,
-                                                        float* __restrict__ mix) {
-    __shared__ float sv[4]; __shared__ int si[4];
-    const int b = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x, step = *a.n_dec;
-    const int bg = b + a.b_off, B = a.B_total;            // global image index
-    const int per = (a.V + CFG_CHUNKS - 1) / CFG_CHUNKS, v0 = ch * per, v1 = min(a.V, v0 + per);
-    const long rf = (long)(3 * b) * a.V;
-    float best = -INFINITY; int bi = 0x7fffffff;
-    const float temperature = a.p->temperature, w_c = dw->w_caption, w_l = dw->w_layout;
-    const uint64_t stream = (uint64_t)(bg + a.p->img_off) * 1000003ull + step;
-    const uint64_t seed = a.p->seed;
-    const float invT = temperature > 0.f ? 1.f / temperature : 1.f;
-    constexpr int IT = 4;
-    const float* bias0 = a.bias ? a.bias : a.logits_partial + rf;     // no bias: any mapped address, value discarded
-    const int ofpu[3] = {0, a.V, 2 * a.V};                            // f, p, u: adjacent rows
-    for (int vb = v0 + tid; vb < v1; vb += IT * 256) {
-        float bb[IT], fpu[IT][3];
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int v = vb + it * 256, vc = v < v1 ? v : v1 - 1;
-            bb[it] = bias0[vc];
-        }
-        float t[IT][4][3];
-        const int smax = a.S > 0 ? a.S - 1 : 0;
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int v = vb + it * 256, vc = v < v1 ? v : v1 - 1;
-            const float* pp = a.logits_partial + rf + vc;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float* q = pp + (long)(u < smax ? u : smax) * a.slab;       // slab index clamped: branch-free loads
-                t[it][u][0] = q[0]; t[it][u][1] = q[a.V]; t[it][u][2] = q[2 * a.V];
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int v = vb + it * 256, vc = v < v1 ? v : v1 - 1;
-            fpu[it][0] = a.bias ? bb[it] : 0.f; fpu[it][1] = fpu[it][0]; fpu[it][2] = fpu[it][0];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) if (u < a.S) { fpu[it][0] += t[it][u][0]; fpu[it][1] += t[it][u][1]; fpu[it][2] += t[it][u][2]; }
-            if (a.S > 4) sum_slabs<3>(a.logits_partial + rf + vc + 4 * a.slab, a.slab, a.S - 4, ofpu, fpu[it]);
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int v = vb + it * 256;
-            if (v < v1) {
-                const float f = fpu[it][0], p = fpu[it][1], u = fpu[it][2];
-                float mixed = (u + w_c * (p - u)) + w_l * (f - p);
-                if (a.logits_out) a.logits_out[((long)step * B + bg) * a.V + v] = mixed;
-                if (STORE) { mix[(long)b * a.V + v] = mixed; continue; }
-                if (temperature > 0.f) mixed = gumbel_perturb(mixed, invT, seed, stream, v);
-                if (mixed > best) { best = mixed; bi = v; }
-            }
-        }
-    }
-    if (STORE) return;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-        argmax_combine(best, bi, ov, oi);
-    }
-    if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-        float v = sv[0]; int i = si[0];
-        for (int k = 1; k < 4; ++k) argmax_combine(v, i, sv[k], si[k]);
-        pv[b * CFG_CHUNKS + ch] = v; pi[b * CFG_CHUNKS + ch] = i;
-    }
-}
-__global__ __launch_bounds__(256) void cfg3_pick_kernel(SampleArgs a, const float* __restrict__ pv, const int* __restrict__ pi) {
-    __shared__ int s_tok;
-    const int b = blockIdx.x, tid = threadIdx.x, step = *a.n_dec;
-    if (tid == 0) {
-        float v = pv[b * CFG_CHUNKS]; int i = pi[b * CFG_CHUNKS];
-        for (int k = 1; k < CFG_CHUNKS; ++k) argmax_combine(v, i, pv[b * CFG_CHUNKS + k], pi[b * CFG_CHUNKS + k]);
-        i = i < 0 ? 0 : (i >= a.V ? a.V - 1 : i);
-        int emit = i, feed = i;
-        const long bg = b + a.b_off;
-        const int T = a.p->T;
-        if (step < T && a.p->has_force) {
-            const int f = a.force_tok[bg * T + step];
-            if (a.p->has_mask) { if (a.force_mask[bg * T + step] == 0) { emit = f; feed = f; } }
-            else feed = f;
-        }
-        if (step < T) a.out_tok[bg * T + step] = emit;
-        feed = feed < 0 ? 0 : (feed >= a.V ? a.V - 1 : feed);
-        s_tok = feed;
-    }
-    __syncthreads();
-    const float* src = a.embed_table + (long)s_tok * a.H;
-    float* x0 = a.x + (long)(3 * b) * a.H;
-    for (int i = tid * 4; i < a.H; i += 1024) {
-        const f32x4 v = *(const f32x4*)(src + i);
-        *(f32x4*)(x0 + i) = v;
-        *(f32x4*)(x0 + a.H + i) = v;
-        *(f32x4*)(x0 + 2 * a.H + i) = v;
-    }
-}
 __global__ void set_dual_weights_kernel(DualWeights* dst, DualWeights v) { *dst = v; }
 void launch_set_dual_weights(hipStream_t s, DualWeights* dst, DualWeights v) { hipLaunchKernelGGL(set_dual_weights_kernel, dim3(1), dim3(1), 0, s, dst, v); }
-// One dual step.  filtered: store scan -> cfg_select_kernel<false> (it reads mix) -> pick.  Otherwise [stored: store scan ->] scan -> pick.
-void launch_cfg3_sample(hipStream_t s, const SampleArgs& a, const DualWeights* dw, int B, bool filtered, bool stored, float* scratch_v, int* scratch_i, float* mix) {
-    if (filtered || stored) hipLaunchKernelGGL(cfg3_scan_kernel<true>, dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, dw, scratch_v, scratch_i, mix);
-    if (filtered) {
-        FilterArgs f{};
-        f.mix = mix; f.V = a.V; f.p = a.p; f.pv = scratch_v; f.pi = scratch_i; f.n_dec = a.n_dec; f.b_off = a.b_off;
-        hipLaunchKernelGGL(cfg_select_kernel<false>, dim3(B), dim3(SEL_THREADS), 0, s, f);
-    } else hipLaunchKernelGGL(cfg3_scan_kernel<false>, dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, dw, scratch_v, scratch_i, (float*)nullptr);
-    hipLaunchKernelGGL(cfg3_pick_kernel, dim3(B), dim3(256), 0, s, a, scratch_v, scratch_i);
-}
 
 // text token (HF generate): greedy = argmax over vocab; sampled = Gumbel-max over logits / T (== multinomial(softmax(logits / T)));
 // finished rows emit eos, unfinished &= (tok != eos).  Two stages like the image sampler: grid (CFG_CHUNKS, B) scans V/CFG_CHUNKS logits with
@@ -872,9 +779,6 @@ void launch_token_logprob_op(hipStream_t s, const float* rows, int B, int V, con
     LogprobArgs l{};
     l.rows = rows; l.V = V; l.temperature = temperature; l.tok32 = tok; l.out = out;
     hipLaunchKernelGGL(token_logprob_kernel<SR_OP>, dim3(B), dim3(SR_THREADS), 0, s, l);
-}
-void launch_cfg_store(hipStream_t s, const SampleArgs& a, int B, float* mix) {
-    hipLaunchKernelGGL(cfg_scan_kernel<true>, dim3(CFG_CHUNKS, B), dim3(256), 0, s, a, (float*)nullptr, (int*)nullptr, mix);
 }
 void launch_token_logprob_image(hipStream_t s, const SampleArgs& a, int B, const float* mix, float* out) {
     LogprobArgs l{};

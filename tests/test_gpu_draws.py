@@ -250,7 +250,7 @@ def test_image_special_values(V, E_g):
 
 @pytest.mark.parametrize("V", [17, 1000, 16384])
 def test_image_filtered_draw_is_the_models_draw_over_the_kept_set(V, E_g, tiny_cfg):
-    """launch_cfg_sample_filtered: the token is the model's draw restricted to the kept mask pg_op_sample_filter returns for the same row, and it is the
+    """The filtered route of launch_cfg_step: the token is the model's draw restricted to the kept mask pg_op_sample_filter returns for the same row, and it is the
     unfiltered operator's token whenever that one is kept."""
     from plangen_amd.config import PlanGenConfig
     from plangen_amd.engine import Engine

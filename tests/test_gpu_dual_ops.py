@@ -1,5 +1,5 @@
-"""GPU: one step of the image sampler under dual guidance (pg_diag_op_cfg3_sample -> launch_cfg3_sample: cfg3_scan_kernel, the unchanged cfg_select_kernel,
-cfg3_pick_kernel) against the host model of tests/dual_ref.py.  The tapped row is compared with == on dyadic slabs and weights; greedy tokens bind always; a
+"""GPU: one step of the image sampler under dual guidance (pg_diag_op_cfg3_sample -> launch_cfg_step at three rows per image: cfg_scan_kernel<3>, the
+cfg_select_kernel of the pair route, cfg_pick_kernel<3>) against the host model of tests/dual_ref.py.  The tapped row is compared with == on dyadic slabs and weights; greedy tokens bind always; a
 sampled draw binds where the model's fp64 lead exceeds the device's arithmetic (draw_ref.decided with the E_g that tests/test_gpu_draws.py measures), at most
 draw_ref.UNDECIDED_CAP of a parametrisation's draws may be open.  The degenerate cases are compared bit for bit with the pair operator on the same slabs."""
 import numpy as np

@@ -320,3 +320,45 @@ def test_pair_call_unchanged_after_dual_calls(tiny_cfg, tiny_weights):
                 _S.setdefault("pair_bf16", toks.cpu())
                 assert torch.equal(toks.cpu(), _S["pair_bf16"])
         e.set_option("use_graph", 0)
+
+
+def test_graph_alternation_between_the_pair_and_dual_loops(tiny_cfg, tiny_weights):
+    """One f32 handle, use_graph on, T = 4 (a graph needs T > 2), the six rows of _triples read as three pairs or two triples: pair, dual, pair, dual,
+    each after its own prefill, each with its own seed, all four through the raw entry points into the SAME token and tap buffers.  Both loops keep their
+    step graph in one slot under one key, and with these calls every field of that key but the rows per image is equal (R = 6, the tap's address, no shared
+    prompt, unfiltered), so a key that did not tell pairs from triples would replay the other loop's step.  Tokens and tapped logits of each call equal,
+    bit for bit, the same call alone on a fresh handle."""
+    import call_sequences as cs
+    T4, V = 4, tiny_cfg.img_vocab
+    ids3, _, pad3 = _triples(tiny_cfg)
+
+    def call(e, bufs, form, seed):
+        out, lg = bufs
+        nb = 3 if form == "pair" else 2
+        e.set_option("use_graph", 1)
+        e.prefill(ids3, pad3, position_mode=0, uncond_shared=False)
+        out.fill_(-1); lg.fill_(float("nan"))
+        if form == "pair":
+            rc = e.lib.pg_decode_image_tokens(e.h, T4, WC, 1.0, seed, None, None, out.data_ptr(), lg.data_ptr(), e.stream)
+        else:
+            rc = e.lib.pg_decode_image_tokens_dual(e.h, T4, WC, WL, 1.0, 0, 1.0, seed, None, None, out.data_ptr(), lg.data_ptr(), e.stream)
+        e._check(rc, form)
+        torch.cuda.synchronize()
+        return out[:nb * T4].cpu().clone(), lg[:T4 * nb * V].cpu().clone()
+
+    def bufs(e):
+        return torch.zeros(3 * T4, dtype=torch.int32, device=e.device), torch.zeros(T4 * 3 * V, dtype=torch.float32, device=e.device)
+
+    calls = (("pair", 21), ("dual", 22), ("pair", 23), ("dual", 24))
+    try:
+        vet = cs.make_engine(tiny_cfg, tiny_weights, "f32")
+        vb = bufs(vet)
+        got = [call(vet, vb, form, seed) for form, seed in calls]
+        for (form, seed), (tok, lg) in zip(calls, got):
+            fresh = cs.make_engine(tiny_cfg, tiny_weights, "f32")
+            ftok, flg = call(fresh, bufs(fresh), form, seed)
+            fresh.close(); cs._OPEN.remove(fresh)
+            assert bool((tok >= 0).all()) and bool(torch.isfinite(lg).all()), (form, seed)
+            assert torch.equal(tok, ftok) and torch.equal(lg.view(torch.int32), flg.view(torch.int32)), (form, seed)
+    finally:
+        cs.close_all()

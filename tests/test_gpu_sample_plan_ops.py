@@ -1,4 +1,4 @@
-"""GPU: one step of the image sampler under a sample plan (pg_diag_op_cfg_sample_plan -> launch_cfg_sample_plan: the planned instantiations of cfg_scan_kernel
+"""GPU: one step of the image sampler under a sample plan (pg_diag_op_cfg_sample_plan -> launch_cfg_step with a plan: the planned instantiations of cfg_scan_kernel
 and cfg_select_kernel, then cfg_pick_kernel) against the host model of tests/plan_ref.py.  The tapped row is compared with == on dyadic slabs; a sampled draw binds
 where the model's fp64 lead exceeds the device's arithmetic (draw_ref.decided with the E_g that tests/test_gpu_draws.py measures), at most
 draw_ref.UNDECIDED_CAP of a parametrisation's draws may be open; greedy images bind always."""
